@@ -9,7 +9,13 @@ CSR slice (gnnvc_attach_graph_slice) and full-size replicated feature buffers â€
 over xGMI between stages (only their live columns once a forward has shown which those are); total work is
 fixed, so scaling is "strong".
 
-What the ONE JSON line on rank 0 says (contract in the project brief, read as VERDICT r1 asked):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) builds the graph, attaches it, runs the graph's first three forwards
+(which build the per-graph plans) and W warm-ups, times K steps and prints the line: value, ms_per_step, the first
+forwards' times, the forward-level roofline fraction and the plans in force.  Everything below that takes runs of its own
+(stage_ms, per-kernel times, measured traffic, the fresh-engine variants, host path, the workloads block, the CPU baseline
+and the parity checks) runs only with --full.  --dump-outputs DIR writes the last timed step's outputs (see dump_outputs).
+
+What the ONE JSON line on rank 0 says with --full (contract in the project brief, read as VERDICT r1 asked):
   value / ms_per_step   the STEADY STATE of a graph that is scored again and again: the engine builds per-graph
                         plans inside a graph's first forwards, the timed region starts after them.
   first_forward_ms      what a caller gets who hands over a fresh graph and scores it once â€” the reference's own
@@ -130,12 +136,46 @@ def kernel_algorithmic_bytes(name: str, n: int, nnz: int, calls_per_forward: flo
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_SAMPLE_ROWS = 2_000_000     # rows kept of each output when the whole would not fit (the same rows for every output)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir: str, arrays: dict, n: int, dev) -> dict:
+    """--dump-outputs: every array of `arrays` (name -> device tensor with n rows) as <out_dir>/<name>.npy in float32.  When
+    they would exceed DUMP_LIMIT_BYTES together, the same fixed, seeded sample of DUMP_SAMPLE_ROWS rows (ascending) of each
+    is written instead, and the row ids as <out_dir>/sample_rows.npy (float64)."""
+    import numpy as np
+    import torch
+    d = pathlib.Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    rows = idx = None
+    if total > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, min(n, DUMP_SAMPLE_ROWS), replace=False))
+        idx = torch.from_numpy(rows).to(dev)
+        np.save(d / "sample_rows.npy", rows.astype(np.float64))
+    for name, a in arrays.items():
+        v = a if idx is None else a[idx]
+        np.save(d / f"{name}.npy", v.to(torch.float32).cpu().numpy())
+    return {"files": sorted(arrays) + ([] if rows is None else ["sample_rows"]),
+            "rows": n if rows is None else int(len(rows)), "sampled": rows is not None}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="er10m", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-stage and per-kernel times, measured traffic, first-forward "
+                         "variants, host path, the other workloads, the CPU baseline and the parity checks (the --no-* "
+                         "options below select among them); without it a run sets up, warms up, times the steps and "
+                         "prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32; a fixed, seeded "
+                         "sample of rows when the whole would exceed 64 MB, its row ids in DIR/sample_rows.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the oracle parity checks")
     ap.add_argument("--no-variants", action="store_true", help="skip first_forward_ms / plain_forward_ms (N = 1)")
     ap.add_argument("--no-lds-table", action="store_true", help="F = 1 stage without the LDS-table plan")
@@ -281,15 +321,16 @@ def main() -> int:
     csr_bytes_rank = csr_bytes_full
     t0 = time.time()
     if multi:
-        # Reference for the self-check, while the whole graph still exists on this rank: a plain single-GPU forward
+        # --full: reference for the self-check, while the whole graph still exists on this rank: a plain single-GPU forward
         # (setup only).  Then the rank cuts its slice out, lets the whole graph go and attaches the slice: from here on
         # its CSR memory is 1 / P of the graph's.
-        ref_scores = torch.zeros(n, dtype=torch.float32, device=dev)
-        e0 = make_engine()
-        attach_whole(e0)
-        e0.forward_device(x.data_ptr(), ref_scores.data_ptr(), 0)
-        e0.synchronize()
-        e0.close()
+        if args.full:
+            ref_scores = torch.zeros(n, dtype=torch.float32, device=dev)
+            e0 = make_engine()
+            attach_whole(e0)
+            e0.forward_device(x.data_ptr(), ref_scores.data_ptr(), 0)
+            e0.synchronize()
+            e0.close()
         sl = D.slice_csr(n, g.rowptr, g.col, g.w, g.nw, lo, hi, pad=ggt.COL_PAD)
         csr_bytes_rank = sl.nbytes()
         g.rowptr = g.col = g.w = g.nw = None
@@ -422,9 +463,18 @@ def main() -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # what a caller of the timed path receives from its last step (one GPU: scores + logits; N > 1: the scores every rank
+    # holds after the final all-gather, logits are not gathered), before anything else runs on the GPU
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"scores": fwd_scores, "logits": fwd_logits} if not multi
+                              else {"scores": bufs.scores[:n]}, n, dev)
+
     exchange_ok = D.exchange_verified(bufs) if codec is not None else True   # no shipped row hid a non-zero
 
-    if not multi:
+    if not multi and not args.full:
+        stage_ms = None
+    elif not multi:
         # the engine's own HIP events (same stream) around each stage of ONE more forward right after the timed region (option
         # "forward_timing" 2: the timed forwards record no events â€” four records were 5.5 us of a small forward); the mean step
         # time of the K timed forwards is ms_per_step
@@ -447,7 +497,7 @@ def main() -> int:
     # out of the timed region itself: between the short rounds of the last stage they cost ~0.1 ms per forward; the traced
     # loop's own time per step is reported next to ms_per_step.)
     kernels, dominant, traced_ms = {}, None, None
-    if args.kernel_trace and not multi:
+    if args.full and args.kernel_trace and not multi:
         eng.set_option("kernel_trace", 1)
         step(None)
         torch.cuda.synchronize()
@@ -481,7 +531,7 @@ def main() -> int:
                                         "bytes â€” the plan in force serves its gathers from a table swept through L2 / LDS "
                                         "(DESIGN.md Â§5); the forward-level fraction and the measured traffic are the bounds")
 
-    traffic, traffic_src = measured_traffic(args.workload) if not multi else (None, None)
+    traffic, traffic_src = measured_traffic(args.workload) if (args.full and not multi) else (None, None)
     plans = {"compact_gather_f16": bool(eng.get_info("compact_gather_active")),
              "pruned_adjacency": {f"stage{st}": ({"entries_kept": eng.get_info(f"pruned_entries_stage{st}"),
                                                   "zero_row_vertices": eng.get_info(f"pruned_vertices_stage{st}"),
@@ -536,12 +586,15 @@ def main() -> int:
         "plan": plans,
     }
 
+    if dumped is not None:
+        out["outputs"] = dumped
     if multi:
-        # self-check: the partitioned result on THIS rank against the plain single-GPU forward of the whole graph that
-        # this GPU ran during setup (before it let the whole graph go)
-        bad = (bufs.scores[:n].view(torch.int32) != ref_scores.view(torch.int32)).sum().to(torch.int64)
-        dist.all_reduce(bad, op=dist.ReduceOp.SUM)
-        out["parity"] = {"partitioned_vs_single_gpu_score_bit_mismatches_all_ranks": int(bad.item())}
+        # --full self-check: the partitioned result on THIS rank against the plain single-GPU forward of the whole graph
+        # that this GPU ran during setup (before it let the whole graph go)
+        if ref_scores is not None:
+            bad = (bufs.scores[:n].view(torch.int32) != ref_scores.view(torch.int32)).sum().to(torch.int64)
+            dist.all_reduce(bad, op=dist.ReduceOp.SUM)
+            out["parity"] = {"partitioned_vs_single_gpu_score_bit_mismatches_all_ranks": int(bad.item())}
         per_rank = torch.zeros(world, dtype=torch.int64, device=dev)
         per_rank[rank] = csr_bytes_rank
         dist.all_reduce(per_rank)
@@ -570,7 +623,7 @@ def main() -> int:
                              "first_forward_over_steady": early_ms[0] / ms_per_step,
                              "note": "attach = device-side checks + row classes + the plans built at hand-off + every buffer of the "
                                      "forward (a fresh engine: allocations included); device-resident CSR, no PCIe copy in it"}
-        if not args.no_variants:
+        if args.full and not args.no_variants:
             out.update(forward_variants(make_engine, attach_whole, x, n, dev))
             # hipMalloc on this stack now and then takes 100+ ms for no reason of ours (seen on the first and on the sixth engine
             # of a process): the hand-off numbers are the MEDIAN of the timed engine's and two more fresh engines' (all listed)
@@ -593,7 +646,7 @@ def main() -> int:
             out["score_once"].update({"attach_ms": med[0], "first_forward_ms": med[1], "attach_plus_first_forward_ms": med[0] + med[1],
                                       "first_forward_over_steady": med[1] / ms_per_step,
                                       "trials_attach_first_ms": [[round(a, 3), round(f, 3)] for a, f in trials]})
-        if args.host_path or not args.no_host_path:
+        if args.host_path or (args.full and not args.no_host_path):
             # PCIe-inclusive path (host x in, host scores + logits out); never `value`
             xh = x.cpu().numpy()
             keep = eng.forward(xh)          # the caller's output buffers, reused like the reference's `out` matrix
@@ -606,12 +659,12 @@ def main() -> int:
         # millisecond, and the launching thread shares this process's CPU quota with the oracle's 16 OpenMP workers and
         # OpenBLAS's spinning pool once those have run (power-law graph: 0.98 ms per forward before them, 1.50 after).
         checks = []
-        if not args.no_workloads and args.workload == "er10m":
+        if args.full and not args.no_workloads and args.workload == "er10m":
             out["workloads"] = {}
             for name in [w for w in args.workloads.split(",") if w]:
                 out["workloads"][name], chk = side_workload(name, args, dev, make_engine, ggt)
                 checks.append((name, chk))
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], out["cpu_baseline_openmp_aggregation"], out["parity"], handoff = \
                 cpu_baseline(args, dev, eng, ggt, g, x, fwd_logits, make_engine)
             out["score_once"].update(handoff)
@@ -678,6 +731,7 @@ def multi_handle_run(args, dev, g, desc, result_fd):
     for _ in range(args.steps):
         e.forward_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())
     ms = (time.perf_counter() - t) * 1e3 / args.steps
+    dumped = dump_outputs(args.dump_outputs, {"scores": sc, "logits": lg}, n, dev) if args.dump_outputs else None
     bad = int((lg.view(torch.int32) != ref_lg.view(torch.int32)).sum())
     bad_sc = int((sc.view(torch.int32) != ref_sc.view(torch.int32)).sum())
     info = {k: e.get_info(k) for k in ("multi_pieces", "multi_packed_stage0", "multi_packed_stage1", "multi_packed_columns_stage0",
@@ -722,6 +776,8 @@ def multi_handle_run(args, dev, g, desc, result_fd):
                                                  "other parts idle: HIP events on its stream, median"},
            "parity": {"logit_bit_mismatches_vs_single_engine": bad, "score_bit_mismatches_vs_single_engine": bad_sc,
                       "first_forward_logit_bit_mismatches_vs_single_engine": first_bad, "logits_checked": n}}
+    if dumped is not None:
+        out["outputs"] = dumped
     sys.stdout.flush()
     os.write(result_fd, (json.dumps(out) + "\n").encode())
     return 0 if (bad == 0 and bad_sc == 0 and first_bad == 0) else 4

@@ -1,9 +1,10 @@
 #!/bin/bash
+mkdir -p results
 # ms_per_step / first_forward_ms / plain_forward_ms of the named workloads (no CPU legs): bench_quick.sh TAG w1 w2 ...
 TAG=$1; shift
 for w in "$@"; do
-  timeout -k 10 400 python bench.py --workload $w --no-cpu-baseline --no-host-path --no-workloads --kernel-trace 0 > gpurun_out/bq_${TAG}_$w.json 2> gpurun_out/bq_${TAG}_$w.log
-  python - "$w" gpurun_out/bq_${TAG}_$w.json <<'PY'
+  timeout -k 10 400 python bench.py --full --workload $w --no-cpu-baseline --no-host-path --no-workloads --kernel-trace 0 > results/bq_${TAG}_$w.json 2> results/bq_${TAG}_$w.log
+  python - "$w" results/bq_${TAG}_$w.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -2,14 +2,15 @@
 set -u
 w=$1; ctr=$2; shift 2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+mkdir -p results
 tag=${TAG:-pmc_$w}
-rm -rf gpurun_out/$tag
-rocprofv3 --pmc $ctr --output-format csv -d gpurun_out/$tag -- python3 bench.py --no-cpu-baseline --no-variants --kernel-trace 0 --workload $w --steps 2 --warmup 1 "$@" > gpurun_out/$tag.log 2>&1
-cp $(find gpurun_out/$tag -name "*counter_collection.csv" | head -1) gpurun_out/$tag.csv
+rm -rf results/$tag
+rocprofv3 --pmc $ctr --output-format csv -d results/$tag -- python3 bench.py --full --no-cpu-baseline --no-variants --kernel-trace 0 --workload $w --steps 2 --warmup 1 "$@" > results/$tag.log 2>&1
+cp $(find results/$tag -name "*counter_collection.csv" | head -1) results/$tag.csv
 python3 - <<PY
 import csv, collections
 last = {}
-for r in csv.DictReader(open("gpurun_out/$tag.csv")):
+for r in csv.DictReader(open("results/$tag.csv")):
     n = r["Kernel_Name"]
     if "gnnvc" not in n: continue
     k = n[n.index("k_"):].split("(")[0].replace(" ", "")

@@ -11,7 +11,7 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 for w in er10m rmat22; do
   for m in 0 1 2; do
     tag=${w}_m${m}
-    args="--workload $w --mfma $m --no-lds-table --no-compact --no-cpu-baseline --no-variants --kernel-trace 0"
+    args="--full --workload $w --mfma $m --no-lds-table --no-compact --no-cpu-baseline --no-variants --kernel-trace 0"
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$tag" -- python3 bench.py $args --steps 10 > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
         --output-format csv -d "$OUT/pmc_$tag" -- python3 bench.py $args --steps 2 --warmup 1 > "$OUT/pmc_$tag.json" 2> "$OUT/pmc_$tag.err"

@@ -16,12 +16,12 @@ pass() { dir=$1; name=$2; args=$3; shift 3; echo "pass $dir/$name"; rm -rf "$OUT
          timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$dir/$name" -- python3 tools/pmc_probe.py $args > "$OUT/$dir/$name.log" 2>&1; }
 if has trace; then
   rm -rf "$OUT/trace"
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --no-cpu-baseline --no-variants --no-workloads --no-host-path > "$OUT/bench_under_rocprof.log" 2>&1
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --full --no-cpu-baseline --no-variants --no-workloads --no-host-path > "$OUT/bench_under_rocprof.log" 2>&1
 fi
 for w in er20k er100k rmat22 powerlaw1m; do   # kernel stats of the other workloads' steady state (the same bench command, one workload)
   if has trace_$w || has trace; then
     rm -rf "$OUT/trace_$w"
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$w" -- python3 bench.py --workload $w --steps 50 --no-cpu-baseline --no-variants --no-workloads --no-host-path > "$OUT/bench_under_rocprof_$w.log" 2>&1
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$w" -- python3 bench.py --full --workload $w --steps 50 --no-cpu-baseline --no-variants --no-workloads --no-host-path > "$OUT/bench_under_rocprof_$w.log" 2>&1
   fi
 done
 if has er10m; then
