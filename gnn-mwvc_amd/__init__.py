@@ -7,5 +7,5 @@ Layout:
   engine.py  ctypes binding of the C ABI (include/gnnvc.h) for tests and the bench
   data/      the trained model in the reference's text format
 """
-from .engine import (Engine, EngineRowCodec, GnnvcError, build_library, default_model_text, library_path,  # noqa: F401
-                     load_library)
+from .engine import (ERR_AUDIT, Engine, EngineRowCodec, GnnvcError, build_library, default_model_text,  # noqa: F401
+                     library_path, load_library)

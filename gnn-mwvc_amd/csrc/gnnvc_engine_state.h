@@ -408,6 +408,30 @@ struct gnnvc_engine {
     DevBuf<uint32_t> dev_info;
     double handoff_build_ms = 0.0;
 
+    // On-device audit (options "audit_*"; k_audit_stage): every opt_audit_period-th call of a forward entry point has each
+    // fused stage it runs recomputed by code that uses none of the plans and compared bit for bit, right behind the stage and
+    // before the next one is queued; the call reads the records back once, at its end (one stream synchronisation).
+    uint32_t opt_audit_period = 0;           // 0 = off
+    int opt_audit_repair = 0;                // 1 = the audit's values are written over mismatching ones, the call succeeds
+    int opt_audit_flip_stage = -1;           // test hook: in an audited call of this stage whose rows hold opt_audit_flip_row, flip
+    uint32_t opt_audit_flip_row = 0;         // ... the lowest mantissa bit of output (row, 0) between the stage and its audit
+    int opt_audit_quiet = 0;                 // record mismatches without returning them (the parts of a multi-device handle)
+    int opt_audit_log = 0;                   // one stderr line per audited call with the counters (drivers that cannot read them)
+    uint64_t audit_calls = 0;                // forward entry-point calls since the period was set
+    bool audit_now = false;                  // the call at hand is audited
+    struct AuditCheck {
+        int stage;
+        uint32_t lo, hi;
+        std::string plan;                    // what produced the stage (StageChoice, views, side queues)
+    };
+    std::vector<AuditCheck> audit_pending;   // the checks of the call at hand: record i of audit_rec is check i's
+    DevBuf<unsigned long long> audit_rec;
+    PinBuf<unsigned long long> audit_pin;
+    uint64_t audit_runs = 0, audit_failures = 0, audit_repairs = 0, audit_nan_pairs = 0;
+    long audit_last_stage = -1, audit_last_row = -1, audit_last_col = -1, audit_last_mismatches = 0;
+    uint32_t audit_last_fused = 0, audit_last_plain = 0;
+    bool stage_wide = false;                 // the last launch_main ran the stage on wide tiles (audit reports)
+
     std::string err;
 };
 

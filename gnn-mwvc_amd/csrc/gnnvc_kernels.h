@@ -140,6 +140,17 @@ struct VerdictWords {
 };
 hipError_t write_verdicts(const VerdictWords &vw, uint32_t *out_dev, hipStream_t stream);
 
+// On-device audit (option "audit_period", k_audit_stage): stage sp recomputed for rows [row_lo, row_hi) from `in` by code that
+// uses none of the plans (the graph's rowptr / col / w / nw only), every value of out (and logits, when non-null, for the sigmoid
+// stage) compared bit for bit.  rec: kAuditWords zeroed words — [0] mismatches, [1] NaN pairs (equal), [2] repairs, and for
+// the first mismatching row: [3] ~(row << 32 | column: + 64 for a logit), [4] ~(row << 32 | fused bits), [5] ~(row << 32 |
+// audit bits).  repair: the audit's value is written over every mismatching one.
+constexpr int kAuditWords = 8;
+hipError_t launch_audit_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
+                              float *logits, uint32_t row_lo, uint32_t row_hi, unsigned long long *rec, bool repair, hipStream_t stream);
+// the audit's test hook: out[at]'s lowest mantissa bit flipped by one lane
+hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
+
 // a whole stage (variants 0, 1, 2) on WIDE tiles — a workgroup per 64-vertex tile, the tile's gather and each dense layer's outputs
 // split over its four waves (k_stage_w1 / k_stage_w16): graphs with fewer tiles than the chip has SIMDs, no long rows
 hipError_t launch_stage_wide(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,

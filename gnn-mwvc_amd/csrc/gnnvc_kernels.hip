@@ -4537,6 +4537,183 @@ __global__ void k_zero_row(float *buf, uint32_t n, uint32_t width) {
     if (threadIdx.x < width) buf[(size_t)n * width + threadIdx.x] = 0.0f;
 }
 
+// ------------------------------------------------------------------ on-device audit (option "audit_period")
+// k_audit_stage recomputes ONE fused stage for rows [lo, hi) from that stage's own input, the way the layer-by-layer kernels
+// above state the math (k_graph_layer, k_linear, k_relu, k_sigmoid), and compares every value the fused path wrote: the stage
+// output and, for the sigmoid stage, the logits.  It shares nothing with the plans: no dense<>, no matrix cores, no exact_sum.h,
+// no tiles, tables, pruned or filtered views — GraphDev::rowptr / col / w / nw only (the launcher hands it a view with nothing
+// else set).  Per row:
+//   neighbour-sum column j: one fp32 chain in CSR order from 0.0f; then the own features, then degree, W / ws, NW / ws written
+//   last (k_graph_layer); each linear output: a __builtin_fmaf chain from 0.0f over all K inputs in k order, then + bias rounded
+//   on its own (k_linear); relu_ref, or sigmoid_ref on the last layer.
+// A 16-lane group per row, four rows per wave.  Lane j owns neighbour column j: the group fetches 16 column ids at a time (the
+// next 16 already on their way) and gathers 16 entries per lane before it adds them — for F = 16 one coalesced 64-byte row per
+// neighbour, for F = 1 one entry per lane that every lane adds in the same order (one chain).  The dense layers' outputs are
+// dealt to the lanes; each lane runs its outputs' full chains from the group's input vector and the transposed weights in LDS.
+// Two values are equal when their bits are, or when both are NaN (counted apart: a NaN input is no alarm).  Record, per stage
+// (kAuditWords 64-bit words, zeroed by the caller): [0] mismatches, [1] NaN pairs, [2] repairs, and for the first mismatching
+// row, its first mismatching value: [3] ~(row << 32 | column code), [4] ~(row << 32 | fused bits), [5] ~(row << 32 | audit bits)
+// (atomicMax of the complements: every row is checked by exactly one group, which submits one value, so the three minima
+// belong together).  Column code: the output column, + 64 for a logit.
+constexpr uint32_t audit_pitch(uint32_t k) { return ((k + 3u) / 4u * 4u) % 16u == 0u ? (k + 3u) / 4u * 4u + 4u : (k + 3u) / 4u * 4u; }
+
+// acc = fma-chain over k = 0 .. K-1 of x[k] * wt[k] (wt: one output's transposed weight row in LDS, 16-byte aligned)
+template <int K>
+__device__ __forceinline__ float audit_chain(const float (&x)[K], const float *wt) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k + 4 <= K; k += 4) {
+        const float4 w4 = *reinterpret_cast<const float4 *>(wt + k);
+        acc = __builtin_fmaf(x[k + 0], w4.x, acc);
+        acc = __builtin_fmaf(x[k + 1], w4.y, acc);
+        acc = __builtin_fmaf(x[k + 2], w4.z, acc);
+        acc = __builtin_fmaf(x[k + 3], w4.w, acc);
+    }
+#pragma unroll
+    for (int k = K / 4 * 4; k < K; ++k) acc = __builtin_fmaf(x[k], wt[k], acc);
+    return acc;
+}
+
+template <int K>
+__device__ __forceinline__ void audit_load(float (&x)[K], const float *src) {
+#pragma unroll
+    for (int k = 0; k + 4 <= K; k += 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(src + k);
+        x[k] = v.x; x[k + 1] = v.y; x[k + 2] = v.z; x[k + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = K / 4 * 4; k < K; ++k) x[k] = src[k];
+}
+
+template <int F, int N2, int N3, bool SIG>
+__global__ __launch_bounds__(256) void k_audit_stage(GraphDev g, float ws, const float *__restrict__ P, const float *__restrict__ in,
+                                                     float *out, float *logits, uint32_t lo, uint32_t hi,
+                                                     unsigned long long *__restrict__ rec, int repair) {
+    constexpr int N1 = 32, K1 = 2 * F + 3;
+    constexpr int P1 = audit_pitch(K1), P2 = audit_pitch(N1), P3 = audit_pitch(N2);
+    constexpr int GX = 36, GH1 = GX, GH2 = GX + 32, GS = GX + 64;   // per-group LDS: input vector, layer-1 and layer-2 outputs
+    static_assert(K1 <= GX && N2 <= 32 && N3 <= 16, "audit group layout");
+    __shared__ __attribute__((aligned(16))) float w1t[N1 * P1];
+    __shared__ __attribute__((aligned(16))) float w2t[N2 * P2];
+    __shared__ __attribute__((aligned(16))) float w3t[N3 * P3];
+    __shared__ float bs[N1 + N2 + N3];
+    __shared__ __attribute__((aligned(16))) float gs[16 * GS];
+    // parameters, transposed: wNt[o * PN + k] = WN[k * N + o]   (W1 b1 W2 b2 W3 b3 are contiguous from P)
+    const float *W1 = P, *B1 = W1 + K1 * N1, *W2 = B1 + N1, *B2 = W2 + N1 * N2, *W3 = B2 + N2, *B3 = W3 + N2 * N3;
+    for (int i = threadIdx.x; i < K1 * N1; i += blockDim.x) w1t[(i % N1) * P1 + i / N1] = W1[i];
+    for (int i = threadIdx.x; i < N1 * N2; i += blockDim.x) w2t[(i % N2) * P2 + i / N2] = W2[i];
+    for (int i = threadIdx.x; i < N2 * N3; i += blockDim.x) w3t[(i % N3) * P3 + i / N3] = W3[i];
+    for (int i = threadIdx.x; i < N1 + N2 + N3; i += blockDim.x) bs[i] = i < N1 ? B1[i] : (i < N1 + N2 ? B2[i - N1] : B3[i - N1 - N2]);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, j = lane & 15, grp = threadIdx.x >> 4, gbase = lane & 48;
+    float *xs = gs + grp * GS;
+    for (uint64_t base = lo + (uint64_t)blockIdx.x * 16u; base < hi; base += (uint64_t)gridDim.x * 16u) {
+        const uint32_t u = (uint32_t)std::min<uint64_t>(base + (uint64_t)grp, hi);   // (u == hi: no row, nothing read)
+        uint32_t cnt = 0, nan = 0, code = 0, fb = 0, pb = 0;
+        if (u < hi) {
+            // ---- graph layer
+            const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
+            float s = 0.0f;
+            uint32_t cn = (rs + j < re) ? g.col[rs + j] : 0u;   // (0: a valid row to fetch for lanes past the end)
+            for (uint32_t e = rs; e < re; e += 16u) {
+                const uint32_t cc = cn, m = min(16u, re - e);
+                cn = (e + 16u + j < re) ? g.col[e + 16u + j] : 0u;
+                if (F == 16) {
+                    float v[16];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) v[i] = in[(size_t)(uint32_t)__shfl((int)cc, gbase + i) * 16u + j];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i)
+                        if ((uint32_t)i < m) s = s + v[i];
+                } else {
+                    const float mine = in[cc];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const float t = __shfl(mine, gbase + i);
+                        if ((uint32_t)i < m) s = s + t;
+                    }
+                }
+            }
+            const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const int c = j + 16 * t;
+                if (c < K1) {
+                    float v = 0.0f;
+                    if (c < F) v = s;
+                    else if (c < 2 * F) v = in[(size_t)u * F + (c - F)];
+                    if (c == F + 1) v = deg;
+                    if (c == F + 2) v = wv;
+                    if (c == F + 3) v = nwv;
+                    xs[c] = v;
+                }
+            }
+            wave_lds_sync();
+            // ---- linear + ReLU, linear + ReLU, linear + ReLU | sigmoid
+            float x1[K1];
+            audit_load(x1, xs);
+#pragma unroll
+            for (int t = 0; t < N1 / 16; ++t) {
+                const int o = j + 16 * t;
+                xs[GH1 + o] = relu_ref(audit_chain(x1, w1t + o * P1) + bs[o]);
+            }
+            wave_lds_sync();
+            float x2[N1];
+            audit_load(x2, xs + GH1);
+#pragma unroll
+            for (int t = 0; t < N2 / 16; ++t) {
+                const int o = j + 16 * t;
+                xs[GH2 + o] = relu_ref(audit_chain(x2, w2t + o * P2) + bs[N1 + o]);
+            }
+            wave_lds_sync();
+            if (j < N3) {
+                float x3[N2];
+                audit_load(x3, xs + GH2);
+                const float t = audit_chain(x3, w3t + j * P3) + bs[N1 + N2 + j];
+                // ---- compare (and repair)
+                auto check = [&](float *p, float want, uint32_t cc) {
+                    const uint32_t a = __float_as_uint(*p), b = __float_as_uint(want);
+                    if (a == b) return;
+                    if ((a & 0x7FFFFFFFu) > 0x7F800000u && (b & 0x7FFFFFFFu) > 0x7F800000u) { ++nan; return; }
+                    if (cnt++ == 0) { code = cc; fb = a; pb = b; }
+                    if (repair) *p = want;
+                };
+                if (SIG) {
+                    check(out + u, sigmoid_ref(t), 0u);
+                    if (logits) check(logits + u, t, 64u);
+                } else {
+                    check(out + (size_t)u * N3 + j, relu_ref(t), (uint32_t)j);
+                }
+            }
+            wave_lds_sync();   // (the group's LDS is rewritten by its next row)
+        }
+        // one wave-wide reduction; the wave's first mismatch is its lowest lane's (rows ascend with the group, columns with the lane)
+        const unsigned long long m1 = __ballot(cnt != 0), m2 = __ballot(cnt > 1), n1 = __ballot(nan != 0), n2 = __ballot(nan > 1);
+        if (m1) {
+            const int L = __ffsll((long long)m1) - 1;
+            const unsigned long long row = (unsigned long long)(uint32_t)__shfl((int)u, L) << 32;
+            const uint32_t c0 = (uint32_t)__shfl((int)code, L), f0 = (uint32_t)__shfl((int)fb, L), p0 = (uint32_t)__shfl((int)pb, L);
+            if (lane == 0) {
+                const unsigned long long total = (unsigned long long)(__popcll(m1) + __popcll(m2));
+                atomicAdd(rec + 0, total);
+                if (repair) atomicAdd(rec + 2, total);
+                atomicMax(rec + 3, ~(row | c0));
+                atomicMax(rec + 4, ~(row | f0));
+                atomicMax(rec + 5, ~(row | p0));
+            }
+        }
+        if (n1 && lane == 0) atomicAdd(rec + 1, (unsigned long long)(__popcll(n1) + __popcll(n2)));
+    }
+}
+
+// the audit's test hook: flip the lowest mantissa bit of one output value (one lane, a plain store)
+__global__ void k_audit_flip(float *out, size_t at) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        uint32_t *p = reinterpret_cast<uint32_t *>(out) + at;
+        *p = *p ^ 1u;
+    }
+}
+
 inline unsigned blocks_for(size_t work, unsigned block) {
     return (unsigned)((work + block - 1) / block);
 }
@@ -4785,6 +4962,44 @@ __global__ void k_verdicts(VerdictWords vw, uint32_t *__restrict__ out) {
 }
 hipError_t write_verdicts(const VerdictWords &vw, uint32_t *out_dev, hipStream_t stream) {
     GNNVC_LAUNCH(k_verdicts, dim3(1), dim3(64), 0, stream, vw, out_dev);
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
+                              float *logits, uint32_t row_lo, uint32_t row_hi, unsigned long long *rec, bool repair, hipStream_t stream) {
+    if (row_hi <= row_lo) return hipSuccess;
+    // the graph as handed over and nothing else: no plan's view can reach the audit
+    GraphDev plain;
+    plain.n = g.n;
+    plain.nnz = g.nnz;
+    plain.rowptr = g.rowptr;
+    plain.col = g.col;
+    plain.w = g.w;
+    plain.nw = g.nw;
+    plain.row_base = g.row_base;
+    plain.row_end = g.row_end;
+    // a persistent grid: each block transposes the parameters into its LDS once, then walks 16 rows at a time
+    const dim3 grid(std::min<unsigned>(blocks_for((size_t)(row_hi - row_lo), 16), 2048u)), block(kBlock);
+    const float *P = params + sp.param_offset;
+    const int rp = repair ? 1 : 0;
+    switch (sp.variant) {
+    case 0:
+        GNNVC_LAUNCH((k_audit_stage<1, 32, 16, false>), grid, block, 0, stream, plain, ws, P, in, out, logits, row_lo, row_hi, rec, rp);
+        break;
+    case 1:
+        GNNVC_LAUNCH((k_audit_stage<16, 32, 16, false>), grid, block, 0, stream, plain, ws, P, in, out, logits, row_lo, row_hi, rec, rp);
+        break;
+    case 2:
+        GNNVC_LAUNCH((k_audit_stage<16, 16, 1, true>), grid, block, 0, stream, plain, ws, P, in, out, logits, row_lo, row_hi, rec, rp);
+        break;
+    default:
+        return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream) {
+    GNNVC_LAUNCH(k_audit_flip, dim3(1), dim3(64), 0, stream, out, at);
     return hipGetLastError();
 }
 

@@ -106,6 +106,9 @@ struct MultiState {
     int opt_push = 1;            // 0 = hipMemcpyPeerAsync per peer instead of the push kernel
     int opt_only_part = -1;      // >= 0: a forward runs THIS part's share only (timing rehearsal on one device; results are not complete)
     int opt_poison = 0;          // "poison_features": a forward starts by filling every part's feature buffers with NaN bit patterns (tests, fuzz)
+    int opt_audit_repair = 0;    // "audit_repair" (also set on every part): a part's mismatch repaired is no failure of the forward
+    bool parts_audit = false;    // the parts' "audit_period" is 1 (this forward is audited) — the handle counts the calls
+    int audit_last_part = -1;    // the first failing part of the last forward whose audit failed
     int opt_announce = -1;       // a part announces a 16-wide stage's complete input (compact table over its rows): -1 = up to 4 parts, 0 / 1
     Packing pk[2];
     std::vector<uint64_t> region_words[2];   // [r * kMaxPieces + k]: words of part r's piece k of stage s (dense + list)
@@ -542,6 +545,13 @@ int multi_create(MultiState **out, const char *model_text, size_t len, const int
             err = "creating a per-device engine failed";
             break;
         }
+        // a part records its audits without failing its stage calls: the job's barriers do not recover from a part that gives
+        // up, so mismatches are reported by multi_forward_device once the job has drained
+        rc = gnnvc_set_option(p.eng, "audit_quiet", 1);
+        if (rc != GNNVC_OK) {
+            err = "setting up a per-device engine failed";
+            break;
+        }
         hipError_t h = hipSetDevice(p.device);
         // the part runs on its engine's OWN stream: the engine's side queue was probed against that one (ADVICE r3 — a stream
         // made here could share the side queue's hardware queue and serialise the long rows with the tile kernel)
@@ -716,6 +726,10 @@ int multi_set_option(MultiState *m, const char *key, long value) {
         m->opt_poison = value != 0 ? 1 : 0;
         return GNNVC_OK;
     }
+    // (audit_period: the front handle counts the calls, multi_forward_device switches the parts; audit_quiet: the parts stay quiet;
+    // audit_log: the front handle prints for every part)
+    if (k == "audit_period" || k == "audit_quiet" || k == "audit_log") return GNNVC_OK;
+    if (k == "audit_repair") m->opt_audit_repair = value != 0 ? 1 : 0;   // (and on every part, below)
     for (Part &p : m->parts) {
         int rc = gnnvc_set_option(p.eng, key, value);
         if (rc) return rc;
@@ -793,7 +807,25 @@ int multi_upload(MultiState *m, uint32_t n, const uint64_t *rowptr64, const uint
     return GNNVC_OK;
 }
 
-int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float *d_logits, std::string &err) {
+bool multi_audit_info(MultiState *m, const char *key, long *value) {
+    const std::string k(key);
+    const bool sum = k == "audit_runs" || k == "audit_failures" || k == "audit_repairs" || k == "audit_nan_pairs";
+    if (sum) {
+        long total = 0;
+        for (const Part &p : m->parts) {
+            long v = 0;
+            if (gnnvc_get_info(p.eng, key, &v) != GNNVC_OK) return false;
+            total += v;
+        }
+        *value = total;
+        return true;
+    }
+    // audit_last_*: the first failing part's (part 0's, -1 / 0, while none has failed)
+    const Part &p = m->parts[(size_t)std::max(m->audit_last_part, 0)];
+    return gnnvc_get_info(p.eng, key, value) == GNNVC_OK;
+}
+
+int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float *d_logits, bool audit, std::string &err) {
     if (!m->have_graph) {
         err = "no graph attached";
         return GNNVC_ERR_STATE;
@@ -802,6 +834,18 @@ int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float
     if (m->opt_only_part >= 0 && m->parts.size() > 1 && !(m->pk[0].known && m->pk[1].known)) {
         err = "multi_only_part needs a complete forward on this graph first";
         return GNNVC_ERR_STATE;
+    }
+    std::vector<long> failures(m->parts.size(), 0);
+    if (audit || m->parts_audit) {   // (an unaudited forward after an unaudited one touches nothing)
+        for (size_t r = 0; r < m->parts.size(); ++r) {
+            Part &p = m->parts[r];
+            if (gnnvc_set_option(p.eng, "audit_period", audit ? 1 : 0) != GNNVC_OK ||
+                gnnvc_get_info(p.eng, "audit_failures", &failures[r]) != GNNVC_OK) {
+                err = "switching a part's audit failed";
+                return GNNVC_ERR_STATE;
+            }
+        }
+        m->parts_audit = audit;
     }
     const auto t0 = std::chrono::steady_clock::now();
     m->fw_x = d_x;
@@ -839,6 +883,18 @@ int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float
         if (!again) break;
     }
     if (rc != GNNVC_OK) m->pk[0] = m->pk[1] = Packing();   // (a first forward may have failed between choosing and allocating)
+    if (rc == GNNVC_OK && audit) {   // every part has drained: did any part's audit find a mismatch (in any attempt)?
+        for (size_t r = 0; r < m->parts.size(); ++r) {
+            long now = 0;
+            if (gnnvc_get_info(m->parts[r].eng, "audit_failures", &now) != GNNVC_OK || now == failures[r]) continue;
+            m->audit_last_part = (int)r;
+            if (!m->opt_audit_repair) {
+                err = "part " + std::to_string(r) + ": " + gnnvc_last_error(m->parts[r].eng);
+                rc = GNNVC_ERR_AUDIT;
+            }
+            break;
+        }
+    }
     (void)hipSetDevice(m->parts[0].device);
     m->last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;

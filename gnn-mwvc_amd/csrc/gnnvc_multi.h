@@ -26,7 +26,11 @@ int multi_set_option(MultiState *m, const char *key, long value);
 int multi_upload(MultiState *m, uint32_t n, const uint64_t *rowptr64, const uint32_t *rowptr32, const uint32_t *col,
                  const uint32_t *w, const uint32_t *nw, std::string &err);
 // d_x / d_scores / d_logits live on devices[0]; complete when it returns (every device's stream is drained)
-int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float *d_logits, std::string &err);
+// audit: the parts audit every stage call of this forward (the front handle counts the calls, option "audit_period"); a part's
+// mismatch is returned as GNNVC_ERR_AUDIT once the job has drained, err = "part <p>: " + that part's report
+int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float *d_logits, bool audit, std::string &err);
+// gnnvc_get_info keys "audit_*": the parts' counters summed, the first failing part's audit_last_*
+bool multi_audit_info(MultiState *m, const char *key, long *value);
 int multi_synchronize(MultiState *m);
 // rows / entries of part r, wall time of the last forward and of its exchanges as seen by the host
 int multi_part_info(const MultiState *m, int part, uint32_t *row_lo, uint32_t *row_hi, uint64_t *entries);

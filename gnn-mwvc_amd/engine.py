@@ -32,12 +32,23 @@ ABI_SYMBOLS = [
     "gnnvc_sigmoid_forward", "gnnvc_sgemm", "gnnvc_stream_sum", "gnnvc_kernel_trace",
 ]
 COL_PAD = 64
+ERR_AUDIT = -6   # GNNVC_ERR_AUDIT: the on-device audit (option "audit_period") found a fused stage's values wrong
+
+# gnnvc_get_info keys of the on-device audit (Engine.audit_report)
+AUDIT_KEYS = ("audit_runs", "audit_failures", "audit_repairs", "audit_nan_pairs", "audit_last_stage", "audit_last_row",
+              "audit_last_col", "audit_last_mismatches", "audit_last_fused_bits", "audit_last_plain_bits")
 
 
 class GnnvcError(RuntimeError):
     def __init__(self, code: int, detail: str = ""):
         self.code = code
+        self.detail = detail
         super().__init__(f"gnnvc error {code}: {detail}")
+
+    @property
+    def is_audit(self) -> bool:
+        """The call completed, but its audit found values that differ from the plain recomputation (code -6)."""
+        return self.code == ERR_AUDIT
 
 
 def library_path() -> pathlib.Path:
@@ -210,6 +221,10 @@ class Engine:
         v = C.c_long(0)
         self._check(self._L.gnnvc_get_info(self._h, key.encode(), C.byref(v)))
         return v.value
+
+    def audit_report(self) -> dict:
+        """The on-device audit's counters and its last failure (option "audit_period"), key -> value."""
+        return {k: self.get_info(k) for k in AUDIT_KEYS}
 
     def set_stream(self, hip_stream: int | None):
         self._check(self._L.gnnvc_set_stream(self._h, C.c_void_p(hip_stream or 0)))

@@ -549,14 +549,16 @@ void model::predict(const matrix &in, matrix &out, const reduction_graph<Tn, Tw>
         auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         float dev_ms = 0, st[3] = {0, 0, 0};
         gnnvc_last_forward_ms(e, &dev_ms, st, 3);
-        long longs = 0, sorted = 0;
+        long longs = 0, sorted = 0, audit_runs = 0, audit_failures = 0;
         gnnvc_get_info(e, "long_rows", &longs);
         gnnvc_get_info(e, "sorted_tiles_active", &sorted);
+        gnnvc_get_info(e, "audit_runs", &audit_runs);           // (option "audit_period", e.g. GNNVC_OPTIONS=audit_period=1)
+        gnnvc_get_info(e, "audit_failures", &audit_failures);
         std::fprintf(stderr,
                      "gnnvc predict n=%u nnz=%llu hand-off=%.3fms%s forward=%.3fms (device %.3fms: %.3f %.3f %.3f; "
-                     "long rows %ld, sorted tiles %ld)\n",
+                     "long rows %ld, sorted tiles %ld; audit_runs %ld audit_failures %ld)\n",
                      n, (unsigned long long)nnz, ms(t0, t2), derived ? " (derived on the device)" : "", ms(t2, t3), dev_ms, st[0],
-                     st[1], st[2], longs, sorted);
+                     st[1], st[2], longs, sorted, audit_runs, audit_failures);
     }
 }
 

@@ -40,7 +40,9 @@ enum {
     GNNVC_ERR_DEVICE = -2,      /* no HIP device, or a HIP call failed */
     GNNVC_ERR_NOMEM = -3,       /* host or device allocation failed */
     GNNVC_ERR_STATE = -4,       /* call out of order (e.g. forward before a graph) */
-    GNNVC_ERR_UNSUPPORTED = -5  /* model / size outside what the engine handles */
+    GNNVC_ERR_UNSUPPORTED = -5, /* model / size outside what the engine handles */
+    GNNVC_ERR_AUDIT = -6        /* the on-device audit (option "audit_period") found a fused stage's values wrong; the call
+                                   completed, its outputs are as the fused path wrote them, gnnvc_last_error says where */
 };
 
 typedef struct gnnvc_engine gnnvc_engine;
@@ -240,6 +242,35 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         classed by the entries they have left (default 1), the entry count from which the tile
  *                         kernel keeps rows of up to "sorted_long_row_threshold" entries (default 2^24; below: 512),
  *                         giant rows pruned too (default 1)
+ *   "audit_period" k >= 0  on-device audit: every k-th call of a forward entry point on this engine (gnnvc_forward,
+ *                         gnnvc_forward_device, gnnvc_stage_forward_device; counted from when the option was set, so calls k, 2k,
+ *                         3k, ...) has each fused stage it runs recomputed right behind it — before the next stage is queued — by
+ *                         a kernel that uses none of the plans (the CSR arrays only; sequential CSR-order sums, sequential fma
+ *                         chains, separately rounded bias adds, as the layer-by-layer kernels state them) and compared bit for
+ *                         bit with every value the fused path wrote (the stage output; the scores and logits of the last stage;
+ *                         two NaNs count as equal).  A stage call checks its own row range, a sliced engine included.  An
+ *                         audited call ends with one read-back of the records and SYNCHRONISES its stream; unaudited calls
+ *                         launch, record and wait exactly as with the option off.  On a mismatch the call still runs all its
+ *                         stages and returns GNNVC_ERR_AUDIT, gnnvc_last_error naming the stage, its row range, the number of
+ *                         mismatching values, the first row and column with both bit patterns in hex, and the plan that produced
+ *                         the stage; the engine stays usable.  Unfused models audit nothing.  Default 0 (off).
+ *   "audit_repair" 0|1    1 = the audit writes its own values over the mismatching ones: the call returns GNNVC_OK with correct
+ *                         outputs (a repaired stage hands correct rows to the next one) and counts the repair.  Default 0.
+ *   "audit_log" 0|1       1 = every audited call prints one stderr line, "gnnvc audit: audit_runs <n> audit_failures <n>
+ *                         audit_repairs <n>" (the engine's totals; a multi-device handle's summed over its parts) followed by the
+ *                         report of a failure — for drivers that cannot read gnnvc_get_info, e.g. through
+ *                         GNNVC_OPTIONS=audit_period=1,audit_log=1.  Default 0.
+ *   "audit_quiet" 0|1     1 = mismatches are recorded (counters, gnnvc_last_error) but not returned: the parts of a multi-device
+ *                         handle, which reports them itself once the whole job has drained.  Default 0.
+ *   "audit_flip_stage" -1|s, "audit_flip_row" r  (tests) in an audited call of stage s whose row range holds r, the lowest
+ *                         mantissa bit of output value (r, 0) is flipped between the stage and its audit.  Unaudited calls are
+ *                         never touched.  Default -1 (off).
+ *                         gnnvc_get_info: "audit_runs" (stage checks done), "audit_failures" (checks with a mismatch),
+ *                         "audit_repairs" (values repaired), "audit_nan_pairs" (NaN pairs taken as equal), and of the first
+ *                         failing check of the last failing call: "audit_last_stage", "audit_last_row", "audit_last_col",
+ *                         "audit_last_mismatches", "audit_last_fused_bits", "audit_last_plain_bits" (-1 / 0 before any).  A
+ *                         multi-device handle decides per forward whether its parts audit; it sums their counters and reports
+ *                         the last_* of the first failing part, its message prefixed "part <p>: ".
  * gnnvc_get_info keys (further): "pruned_stage1|2", "pruned_entries_stage1|2", "pruned_vertices_stage1|2",
  * "pruned_last_ok_stage1|2" (did the last call of that stage use its pruned adjacency),
  * "compact_gather_last_ok", "compact_gather_last_passes", "compact_gather_last_dirty",
@@ -345,7 +376,7 @@ int gnnvc_graph_row_hashes(gnnvc_engine *e, uint64_t *hashes);
 int gnnvc_forward(gnnvc_engine *e, const float *x, float *scores, float *logits);
 
 /* Device-resident forward: all pointers are device memory; asynchronous on
- * the engine's stream.  d_logits may be NULL. */
+ * the engine's stream (an audited call synchronises it: option "audit_period").  d_logits may be NULL. */
 int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits);
 
 /* One fused stage (graph layer + the dense layers up to the next graph
@@ -355,7 +386,7 @@ int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, flo
  * zeros (the gather reads it for masked lanes); d_out is the full
  * (n + 1) x out_width matrix of which only rows [row_lo, row_hi) are written.
  * d_logits (stage with a final sigmoid only, may be NULL) likewise.
- * Asynchronous on the engine's stream. */
+ * Asynchronous on the engine's stream (an audited call synchronises it: option "audit_period"). */
 int gnnvc_num_stages(const gnnvc_engine *e);
 int gnnvc_stage_widths(const gnnvc_engine *e, int stage, int *in_width, int *out_width);
 int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint32_t row_hi,
