@@ -142,6 +142,30 @@ int plan_model(gnnvc_engine *e) {
         i += 7;
     }
     if (ok && !st.empty() && st.back().sigmoid_last) e->stages = std::move(st);
+
+    // generic stages (k_stage_any): the same layer pattern, any widths within stage_any_fits; a sigmoid ends the last
+    // stage and no other (a model that ends in a ReLU stays layer by layer, as for the trained shapes), the last n3 is the
+    // output width
+    std::vector<StagePlan> gs;
+    bool gok = !e->layers.empty() && e->layers.size() % 7 == 0;
+    f = e->in_width;
+    for (i = 0; gok && i < e->layers.size(); i += 7) {
+        const Layer *L = &e->layers[i];
+        gok = L[0].kind == kGraph && L[1].kind == kLinear && L[2].kind == kRelu && L[3].kind == kLinear && L[4].kind == kRelu &&
+              L[5].kind == kLinear && (L[6].kind == kRelu || L[6].kind == kSigmoid);
+        if (!gok) break;
+        StagePlan sp;
+        sp.f = f;
+        sp.n1 = (int)L[1].m; sp.n2 = (int)L[3].m; sp.n3 = (int)L[5].m;
+        sp.sigmoid_last = L[6].kind == kSigmoid;
+        sp.param_offset = L[1].w_off;
+        const bool last = (i + 7 == e->layers.size());
+        gok = gnnvc::stage_any_fits(sp.f, sp.n1, sp.n2, sp.n3) && (int)L[1].k == 2 * f + 3 && (int)L[3].k == sp.n1 &&
+              (int)L[5].k == sp.n2 && sp.sigmoid_last == last;
+        gs.push_back(sp);
+        f = sp.n3;
+    }
+    if (gok && !gs.empty()) e->gstages = std::move(gs);
     return GNNVC_OK;
 }
 
@@ -624,6 +648,25 @@ int forward_unfused(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
     return GNNVC_OK;
 }
 
+// Forward of a generic-stage model (option "generic_stages"): one k_stage_any launch per stage, rows ping-ponging through the
+// scratch buffers.  No plan, no pad row (the kernel reads rows of neighbours only), nothing cached between calls.
+int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_logits) {
+    const uint32_t n = e->g.n;
+    const std::vector<StagePlan> &st = e->gstages;
+    int wmax = 1;
+    for (size_t s = 0; s + 1 < st.size(); ++s) wmax = std::max(wmax, st[s].n3);
+    if (st.size() > 1)
+        for (auto &b : e->scratch) HIP_TRY(e, b.reserve(((size_t)n + 1) * (size_t)wmax));
+    const float *cur = d_x;
+    for (size_t s = 0; s < st.size(); ++s) {
+        const bool last = s + 1 == st.size();
+        float *dst = last ? d_out : e->scratch[s & 1].p;
+        HIP_TRY(e, gnnvc::launch_stage_any(st[s], e->g, e->ws, e->params.p, cur, dst, last ? d_logits : nullptr, 0, n, e->stream));
+        cur = dst;
+    }
+    return GNNVC_OK;
+}
+
 }  // namespace
 
 
@@ -823,6 +866,10 @@ int gnnvc_set_option(gnnvc_engine *e, const char *key, long value) {
         e->audit_calls = 0;   // (calls are counted from here)
         return GNNVC_OK;
     }
+    if (k == "generic_stages") {   // (k_stage_any: takes effect at once, touches nothing a forward has cached; a multi-device handle's parts keep their kernels)
+        e->opt_generic = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
+        return GNNVC_OK;
+    }
     if (k == "audit_log") {   // (the front handle of several devices prints for all its parts)
         e->opt_audit_log = value != 0 ? 1 : 0;
         return GNNVC_OK;
@@ -912,6 +959,9 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (e->multi && k.rfind("audit_", 0) == 0) {   // the parts' audits (gnnvc_multi.cpp)
         if (!gnnvc::multi_audit_info(e->multi, key, value)) return GNNVC_ERR_INVALID;
     }
+    else if (k == "generic_stages") *value = e->opt_generic;
+    else if (k == "generic_stages_model") *value = e->generic_on() ? 1 : 0;   // would a forward run k_stage_any now
+    else if (k == "generic_stages_active") *value = e->generic_ran ? 1 : 0;   // did the last one
     else if (k == "audit_runs") *value = (long)e->audit_runs;
     else if (k == "audit_failures") *value = (long)e->audit_failures;
     else if (k == "audit_repairs") *value = (long)e->audit_repairs;
@@ -1036,15 +1086,15 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
 }
 
 int gnnvc_num_layers(const gnnvc_engine *e) { return e ? (int)e->layers.size() : GNNVC_ERR_INVALID; }
-int gnnvc_is_fused(const gnnvc_engine *e) { return e ? (e->stages.empty() ? 0 : 1) : GNNVC_ERR_INVALID; }
+int gnnvc_is_fused(const gnnvc_engine *e) { return e ? (e->stage_list().empty() ? 0 : 1) : GNNVC_ERR_INVALID; }
 int gnnvc_in_width(const gnnvc_engine *e) { return e ? e->in_width : GNNVC_ERR_INVALID; }
 int gnnvc_out_width(const gnnvc_engine *e) { return e ? e->out_width : GNNVC_ERR_INVALID; }
-int gnnvc_num_stages(const gnnvc_engine *e) { return e ? (int)e->stages.size() : GNNVC_ERR_INVALID; }
+int gnnvc_num_stages(const gnnvc_engine *e) { return e ? (int)e->stage_list().size() : GNNVC_ERR_INVALID; }
 
 int gnnvc_stage_widths(const gnnvc_engine *e, int stage, int *in_width, int *out_width) {
-    if (!e || stage < 0 || stage >= (int)e->stages.size()) return GNNVC_ERR_INVALID;
-    if (in_width) *in_width = e->stages[stage].f;
-    if (out_width) *out_width = e->stages[stage].n3;
+    if (!e || stage < 0 || stage >= (int)e->stage_list().size()) return GNNVC_ERR_INVALID;
+    if (in_width) *in_width = e->stage_list()[stage].f;
+    if (out_width) *out_width = e->stage_list()[stage].n3;
     return GNNVC_OK;
 }
 
@@ -1489,7 +1539,7 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     const bool audit = audit_tick(e);
     NOT_ON_MULTI(e, "gnnvc_stage_forward_device");
     if (!e->have_graph) return fail(e, GNNVC_ERR_STATE, "no graph attached");
-    if (stage < 0 || stage >= (int)e->stages.size()) return fail(e, GNNVC_ERR_INVALID, "stage %d out of range", stage);
+    if (stage < 0 || stage >= (int)e->stage_list().size()) return fail(e, GNNVC_ERR_INVALID, "stage %d out of range", stage);
     if (row_lo > row_hi || row_hi > e->g.n) return fail(e, GNNVC_ERR_INVALID, "row range [%u,%u) outside graph of %u", row_lo, row_hi, e->g.n);
     if (row_lo == row_hi) return GNNVC_OK;
     if (e->empty_slice || row_lo < e->g.lo() || row_hi > e->g.hi())
@@ -1498,6 +1548,11 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     if (!d_in || !d_out) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
     int rc = use_device(e);
     if (rc) return rc;
+    if (e->generic_on()) {   // (k_stage_any: one launch, no plan; a generic stage audits nothing)
+        const StagePlan &sp = e->gstages[stage];
+        HIP_TRY(e, gnnvc::launch_stage_any(sp, e->g, e->ws, e->params.p, d_in, d_out, sp.sigmoid_last ? d_logits : nullptr, row_lo, row_hi, e->stream));
+        return GNNVC_OK;
+    }
     if (!audit) return run_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits);
     e->audit_now = true;
     std::string plan;
@@ -1537,8 +1592,8 @@ int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, flo
         if (audit && e->opt_audit_log) audit_log_line(e, rc);
         return rc;
     }
-    // (an unfused model runs the layer-by-layer kernels: nothing to audit)
-    e->audit_now = audit && !e->stages.empty();
+    // (an unfused model runs the layer-by-layer kernels, a generic-stage model k_stage_any: nothing to audit)
+    e->audit_now = audit && !e->stages.empty() && !e->generic_on();
     const int rc = audit_finish(e, forward_single(e, d_x, d_scores, d_logits));
     if (audit && e->opt_audit_log) audit_log_line(e, rc);
     return rc;
@@ -1555,11 +1610,12 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     if (!d_x || !d_scores) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
     int rc = use_device(e);
     if (rc) return rc;
-    if (e->stages.empty()) {
+    e->generic_ran = e->generic_on();
+    if (e->generic_ran || e->stages.empty()) {
         rc = ensure_events(e, 2);
         if (rc) return rc;
         if (e->opt_timing >= 1) HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
-        rc = forward_unfused(e, d_x, d_scores, d_logits);
+        rc = e->generic_ran ? forward_generic(e, d_x, d_scores, d_logits) : forward_unfused(e, d_x, d_scores, d_logits);
         if (rc) return rc;
         if (e->opt_timing >= 1) HIP_TRY(e, hipEventRecord(e->ev[1], e->stream));
         e->ev_count = e->opt_timing >= 1 ? 2 : 0;

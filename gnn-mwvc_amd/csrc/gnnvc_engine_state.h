@@ -95,7 +95,14 @@ struct gnnvc_engine {
     gnnvc::MultiState *multi = nullptr;
     std::string name;
     std::vector<Layer> layers;
-    std::vector<StagePlan> stages;  // non-empty iff fused
+    std::vector<StagePlan> stages;  // non-empty iff every stage is of a trained shape (gnnvc::stage_variant): the specialised kernels and plans
+    // Generic stages (option "generic_stages", k_stage_any): the stage list of every model of the fused layer pattern whose
+    // widths fit gnnvc::stage_any_fits — the trained shapes included, which only option value 2 sends there.
+    std::vector<StagePlan> gstages;
+    int opt_generic = 1;            // 0 = never, 1 = models that have no trained-shape stage list, 2 = every model that fits (tests)
+    bool generic_ran = false;       // gnnvc_get_info "generic_stages_active": the last forward ran k_stage_any
+    bool generic_on() const { return !gstages.empty() && (opt_generic == 2 || (opt_generic == 1 && stages.empty())); }
+    const std::vector<StagePlan> &stage_list() const { return generic_on() ? gstages : stages; }   // what the ABI reports and runs
     int in_width = 1, out_width = 1;
     int max_width = 1;
     bool ends_in_sigmoid = false;
@@ -119,7 +126,7 @@ struct gnnvc_engine {
     bool staging = false;
     // feature buffers
     DevBuf<float> x, h[2], scores, logits;
-    DevBuf<float> scratch[2];  // layer-level entry points / unfused path
+    DevBuf<float> scratch[2];  // layer-level entry points / unfused path / generic stages (ping-pong rows of up to 32 columns)
 
     // column-blocked plan of the F = 1 stage (built per graph, see gnnvc_kernels.hip)
     int opt_blocked = 1;            // option "blocked_stage0"

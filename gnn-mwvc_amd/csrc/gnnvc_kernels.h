@@ -151,6 +151,14 @@ hipError_t launch_audit_stage(const StagePlan &sp, const GraphDev &g, float ws, 
 // the audit's test hook: out[at]'s lowest mantissa bit flipped by one lane
 hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 
+// A fused stage of ANY widths within stage_any_fits (k_stage_any, gnnvc_stage_any.hip): 1 <= f <= 32, n1, n2 <= 64, n3 <= 32 —
+// models laid out like the trained one, (Graph, Linear, ReLU, Linear, ReLU, Linear, ReLU | Sigmoid)+, that are not of its
+// widths.  One launch per call; the graph's rowptr / col / w / nw only (no plan); rows of every degree.  in: (n + 1) x f rows
+// (the pad row is never read), out: rows [row_lo, row_hi) of an (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
+bool stage_any_fits(int f, int n1, int n2, int n3);
+hipError_t launch_stage_any(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
+                            float *logits, uint32_t row_lo, uint32_t row_hi, hipStream_t stream);
+
 // a whole stage (variants 0, 1, 2) on WIDE tiles — a workgroup per 64-vertex tile, the tile's gather and each dense layer's outputs
 // split over its four waves (k_stage_w1 / k_stage_w16): graphs with fewer tiles than the chip has SIMDs, no long rows
 hipError_t launch_stage_wide(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,

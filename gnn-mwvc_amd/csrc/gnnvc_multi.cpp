@@ -589,8 +589,12 @@ int multi_create(MultiState **out, const char *model_text, size_t len, const int
     }
     if (rc == GNNVC_OK) {
         m->stages = gnnvc_num_stages(m->parts[0].eng);
-        if (m->stages != 3 || !gnnvc_is_fused(m->parts[0].eng)) {
-            err = "a multi-device handle runs the fused three-stage model only";
+        // (a three-stage model of other widths reports fused too — option "generic_stages" — but the packers, the exchange and the
+        // plans here are made for the trained shape's 16-wide rows)
+        long generic = 0;
+        (void)gnnvc_get_info(m->parts[0].eng, "generic_stages_model", &generic);
+        if (m->stages != 3 || !gnnvc_is_fused(m->parts[0].eng) || generic != 0) {
+            err = "a multi-device handle runs the fused three-stage model of the trained widths only";
             rc = GNNVC_ERR_UNSUPPORTED;
         }
     }

@@ -1,0 +1,305 @@
+// gnnvc_stage_any.hip — k_stage_any: one fused stage (graph layer, three dense layers, ReLU | sigmoid) whose widths are
+// kernel ARGUMENTS, for models that are laid out like the trained one but are not of its widths (a retrain with 8-, 24- or
+// 64-wide hidden layers, another feature width, several input features or outputs).  The trained widths keep their own
+// kernels in gnnvc_kernels.hip; nothing here is shared with them or with k_audit_stage.
+//
+// What is computed is the layer-by-layer kernels' arithmetic (k_graph_layer, k_linear, k_relu, k_sigmoid):
+//   neighbour-sum column c   one fp32 add chain in stored CSR order from +0.0f;
+//   the row                  [sums (f) | own (f) | 0 0 0], then degree, W / ws, NW / ws written LAST into columns f + 1 .. f + 3
+//                            (for f > 1 they land on own-feature columns, as in k_graph_layer);
+//   each linear output       one __builtin_fmaf chain over k = 0 .. K - 1 from +0.0f, then a separately rounded bias add;
+//   relu_ref, or sigmoid_ref on the last layer of the last stage (the logits are its input).
+// Compile with -ffp-contract=off, like the rest of the library.
+//
+// Bounds (stage_any_fits): 1 <= f <= 32, 1 <= n1, n2 <= 64, 1 <= n3 <= 32.
+//
+// Shape of the kernel: 256-thread workgroups walk the row range 16 rows at a time (grid-stride; no workgroup barrier inside
+// the walk, so a wave that sits on a very long row holds up nobody else).  Each workgroup first transposes the stage's
+// three weight matrices into LDS (wNt[o * pitch + k], pitch an odd number of 16-byte slots: the sixteen lanes of a group
+// read sixteen different 16-byte slots of the bank row).  A 16-lane group owns a row:
+//   gather   lane j owns neighbour columns j and j + 16.  The group fetches the column ids of a round (32 entries; 16 when
+//            f > 16), the next round's already on their way, issues the round's 32 row loads per lane, then adds them in
+//            order.  f = 1: every lane fetches one neighbour's value per 16 entries, 64 entries a round, and all lanes add
+//            them in the same order.  Rows of any degree take this loop.
+//   dense    the outputs of a layer are dealt to the lanes (o = j + 16 t); a lane runs its outputs' chains together, four
+//            k at a time: one 16-byte read of the group's input vector (same address for the group) and one per output of
+//            its transposed weight row.  The number of outputs per lane (1 .. 4) is a template argument chosen by a
+//            wave-uniform switch, so the accumulators stay in registers.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "expf_glibc.h"
+#include "gnnvc_kernels.h"
+
+namespace gnnvc {
+
+namespace {
+
+// (the same two functions as gnnvc_kernels.hip's: (x < 0) ? 0 : x, and 1 / (1 + expf(-x)) with glibc's expf restated)
+__device__ __forceinline__ float relu_ref(float x) { return (x < 0.0f) ? 0.0f : x; }
+__device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf_glibc(-x)); }
+
+__device__ __forceinline__ void wave_lds_sync() {
+    // LDS operations of one wave execute in program order; this keeps the compiler from moving them across the hand-off
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+constexpr int kAnyBlock = 256, kAnyRows = kAnyBlock / 16;
+
+// what the kernel reads of GraphDev: the graph as handed over and nothing else — no plan's view reaches it
+struct AnyGraph {
+    const uint32_t *rowptr, *col, *w, *nw;
+};
+
+}  // namespace
+
+// LDS layout, in floats (host and device agree through this one function)
+struct StageAnyLayout {
+    int p;                       // pitch of the transposed weights
+    int w1, w2, w3, bias, grp;   // offsets
+    int gs, hb;                  // per group: gs floats — [0, hb) input vector, later the second layer's outputs; [hb, gs) the first layer's
+    int total;
+};
+__host__ __device__ inline int any_round4(int v) { return (v + 3) / 4 * 4; }
+__host__ __device__ inline int any_pitch(int k) {
+    return 4 * (((k + 3) / 4) | 1);   // an odd number of 16-byte slots: rows o .. o + 15 start in sixteen different slots
+}
+__host__ __device__ inline StageAnyLayout stage_any_layout(int f, int n1, int n2, int n3) {
+    StageAnyLayout L;
+    const int k1 = 2 * f + 3;
+    const int kmax = k1 > n1 ? (k1 > n2 ? k1 : n2) : (n1 > n2 ? n1 : n2);
+    L.p = any_pitch(kmax);   // one pitch for the three matrices (fewer wave-uniform values to keep; the LDS it wastes is small)
+    L.w1 = 0;
+    L.w2 = L.w1 + n1 * L.p;
+    L.w3 = L.w2 + n2 * L.p;
+    L.bias = L.w3 + n3 * L.p;
+    L.grp = L.bias + any_round4(n1 + n2 + n3);
+    L.hb = any_round4(k1 > n2 ? k1 : n2);
+    L.gs = L.hb + any_round4(n1);
+    L.total = L.grp + kAnyRows * L.gs;
+    return L;
+}
+
+namespace {
+
+// T outputs per lane (o = j + 16 t, clamped to the layer's last output for lanes that have none there: they compute a copy
+// nobody stores): acc[t] = fma-chain over k = 0 .. K - 1 of x[k] * wt[o * pitch + k], from +0.0f; + bias[o] rounded on its own
+template <int T>
+__device__ __forceinline__ void any_chains(const float *x, int K, const float *wt, int pitch, const float *bias, int N, int j,
+                                           float (&res)[T]) {
+    const float *wrow[T];
+    float acc[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        wrow[t] = wt + min(j + 16 * t, N - 1) * pitch;
+        acc[t] = 0.0f;
+    }
+    int k = 0;
+#pragma unroll 1   // (unrolled, the T = 4 bodies cost 60 VGPRs and a wave per SIMD)
+    for (; k + 4 <= K; k += 4) {
+        const float4 x4 = *reinterpret_cast<const float4 *>(x + k);
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const float4 w4 = *reinterpret_cast<const float4 *>(wrow[t] + k);
+            acc[t] = __builtin_fmaf(x4.x, w4.x, acc[t]);
+            acc[t] = __builtin_fmaf(x4.y, w4.y, acc[t]);
+            acc[t] = __builtin_fmaf(x4.z, w4.z, acc[t]);
+            acc[t] = __builtin_fmaf(x4.w, w4.w, acc[t]);
+        }
+    }
+    for (; k < K; ++k) {
+        const float xv = x[k];
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[t] = __builtin_fmaf(xv, wrow[t][k], acc[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) res[t] = acc[t] + bias[min(j + 16 * t, N - 1)];
+}
+
+// a hidden layer: dst[o] = relu_ref(chain + bias), o < N
+template <int T>
+__device__ __forceinline__ void any_hidden(const float *x, int K, const float *wt, int pitch, const float *bias, int N, int j,
+                                           float *dst) {
+    float r[T];
+    any_chains<T>(x, K, wt, pitch, bias, N, j, r);
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        if (j + 16 * t < N) dst[j + 16 * t] = relu_ref(r[t]);
+}
+
+__device__ __forceinline__ void any_hidden_n(const float *x, int K, const float *wt, int pitch, const float *bias, int N, int j,
+                                             float *dst) {
+    switch ((N + 15) >> 4) {   // (wave-uniform)
+    case 1: any_hidden<1>(x, K, wt, pitch, bias, N, j, dst); break;
+    case 2: any_hidden<2>(x, K, wt, pitch, bias, N, j, dst); break;
+    case 3: any_hidden<3>(x, K, wt, pitch, bias, N, j, dst); break;
+    default: any_hidden<4>(x, K, wt, pitch, bias, N, j, dst); break;
+    }
+}
+
+// the stage's last layer, straight to memory: row u of out (and of logits, sigmoid stage, when asked for)
+template <int T>
+__device__ __forceinline__ void any_last(const float *x, int K, const float *wt, int pitch, const float *bias, int N, int j,
+                                         int sig, float *out_row, float *logit_row) {
+    float r[T];
+    any_chains<T>(x, K, wt, pitch, bias, N, j, r);
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int o = j + 16 * t;
+        if (o < N) {
+            if (sig) {
+                out_row[o] = sigmoid_ref(r[t]);
+                if (logit_row) logit_row[o] = r[t];
+            } else {
+                out_row[o] = relu_ref(r[t]);
+            }
+        }
+    }
+}
+
+// the neighbour sums of row [rs, re): s0 = column j, s1 = column j + 16 (TWO: f > 16).  A round fetches 32 entries' rows (16
+// when a lane owns two columns): 32 loads in flight per lane either way, the next round's column ids already on their way.
+// Loads of lanes without a column, and of slots behind the row's end, go to a valid address (row 0 / the lane's last column)
+// and are never added.
+template <bool TWO>
+__device__ __forceinline__ void any_gather(const uint32_t *__restrict__ col, const float *__restrict__ in, uint32_t rs, uint32_t re,
+                                           uint32_t f, int j, int gbase, float &s0, float &s1) {
+    constexpr int CH = TWO ? 1 : 2;
+    const uint32_t c0 = min((uint32_t)j, f - 1u), c1 = min((uint32_t)j + 16u, f - 1u);
+    uint32_t cn[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) cn[c] = (rs + 16u * c + j < re) ? col[rs + 16u * c + j] : 0u;
+    for (uint32_t e = rs; e < re; e += 16u * CH) {
+        const uint32_t m = min(16u * CH, re - e);
+        uint32_t cc[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            cc[c] = cn[c];
+            cn[c] = (e + 16u * (CH + c) + j < re) ? col[e + 16u * (CH + c) + j] : 0u;
+        }
+        float v0[16 * CH], v1[16];
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const size_t row = (size_t)(uint32_t)__shfl((int)cc[c], gbase + i) * f;
+                v0[16 * c + i] = in[row + c0];
+                if (TWO) v1[i] = in[row + c1];
+            }
+#pragma unroll
+        for (int i = 0; i < 16 * CH; ++i)
+            if ((uint32_t)i < m) {
+                s0 = s0 + v0[i];
+                if (TWO) s1 = s1 + v1[i & 15];
+            }
+    }
+}
+
+// f = 1: every lane fetches one neighbour's value per chunk of 16 (four chunks a round), and all lanes of the group add the
+// values in the same — stored — order
+__device__ __forceinline__ float any_gather1(const uint32_t *__restrict__ col, const float *__restrict__ in, uint32_t rs, uint32_t re,
+                                             int j, int gbase) {
+    constexpr int CH = 4;
+    float s = 0.0f;
+    uint32_t cn[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) cn[c] = (rs + 16u * c + j < re) ? col[rs + 16u * c + j] : 0u;
+    for (uint32_t e = rs; e < re; e += 16u * CH) {
+        const uint32_t m = min(16u * CH, re - e);
+        float mine[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            mine[c] = in[cn[c]];
+            cn[c] = (e + 16u * (CH + c) + j < re) ? col[e + 16u * (CH + c) + j] : 0u;
+        }
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float t = __shfl(mine[c], gbase + i);
+                if ((uint32_t)(16 * c + i) < m) s = s + t;
+            }
+    }
+    return s;
+}
+
+__global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
+                                                        float *__restrict__ out, float *__restrict__ logits, uint32_t lo, uint32_t hi,
+                                                        int f, int n1, int n2, int n3, int sig) {
+    extern __shared__ float4 any_lds4[];
+    float *lds = reinterpret_cast<float *>(any_lds4);
+    const StageAnyLayout L = stage_any_layout(f, n1, n2, n3);
+    const int k1 = 2 * f + 3;
+    float *w1t = lds + L.w1, *w2t = lds + L.w2, *w3t = lds + L.w3, *bs = lds + L.bias;
+    // parameters, transposed: wNt[o * p + k] = WN[k * N + o]   (W1 b1 W2 b2 W3 b3 are contiguous from P)
+    const float *W1 = P, *B1 = W1 + k1 * n1, *W2 = B1 + n1, *B2 = W2 + n1 * n2, *W3 = B2 + n2, *B3 = W3 + n2 * n3;
+    for (int i = threadIdx.x; i < k1 * n1; i += kAnyBlock) w1t[(i % n1) * L.p + i / n1] = W1[i];
+    for (int i = threadIdx.x; i < n1 * n2; i += kAnyBlock) w2t[(i % n2) * L.p + i / n2] = W2[i];
+    for (int i = threadIdx.x; i < n2 * n3; i += kAnyBlock) w3t[(i % n3) * L.p + i / n3] = W3[i];
+    for (int i = threadIdx.x; i < n1 + n2 + n3; i += kAnyBlock) bs[i] = i < n1 ? B1[i] : (i < n1 + n2 ? B2[i - n1] : B3[i - n1 - n2]);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, j = lane & 15, grp = threadIdx.x >> 4, gbase = lane & 48;
+    float *xs = lds + L.grp + grp * L.gs, *h1 = xs + L.hb;
+    for (uint64_t base = (uint64_t)lo + (uint64_t)blockIdx.x * kAnyRows; base < hi; base += (uint64_t)gridDim.x * kAnyRows) {
+        const uint64_t u64 = base + (uint64_t)grp;
+        if (u64 >= hi) continue;   // (no workgroup barrier below: a group without a row just waits for the next round)
+        const uint32_t u = (uint32_t)u64;
+        // ---- graph layer
+        const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
+        float s0 = 0.0f, s1 = 0.0f;
+        if (f == 1) {
+            s0 = any_gather1(g.col, in, rs, re, j, gbase);
+        } else if (f <= 16) {
+            any_gather<false>(g.col, in, rs, re, (uint32_t)f, j, gbase, s0, s1);
+        } else {
+            any_gather<true>(g.col, in, rs, re, (uint32_t)f, j, gbase, s0, s1);
+        }
+        const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
+        for (int c = j; c < k1; c += 16) {
+            float v = 0.0f;
+            if (c < f) v = c < 16 ? s0 : s1;
+            else if (c < 2 * f) v = in[(size_t)u * (uint32_t)f + (uint32_t)(c - f)];
+            if (c == f + 1) v = deg;
+            if (c == f + 2) v = wv;
+            if (c == f + 3) v = nwv;
+            xs[c] = v;
+        }
+        wave_lds_sync();
+        // ---- linear + ReLU, linear + ReLU (xs -> h1 -> xs), linear + ReLU | sigmoid (xs -> memory)
+        any_hidden_n(xs, k1, w1t, L.p, bs, n1, j, h1);
+        wave_lds_sync();
+        any_hidden_n(h1, n1, w2t, L.p, bs + n1, n2, j, xs);
+        wave_lds_sync();
+        float *out_row = out + (size_t)u * (uint32_t)n3;
+        float *logit_row = logits ? logits + (size_t)u * (uint32_t)n3 : nullptr;   // (null unless this is the sigmoid stage)
+        if (n3 <= 16) any_last<1>(xs, n2, w3t, L.p, bs + n1 + n2, n3, j, sig, out_row, logit_row);
+        else any_last<2>(xs, n2, w3t, L.p, bs + n1 + n2, n3, j, sig, out_row, logit_row);
+        wave_lds_sync();   // (the group's LDS is rewritten by its next row)
+    }
+}
+
+}  // namespace
+
+bool stage_any_fits(int f, int n1, int n2, int n3) {
+    return f >= 1 && f <= 32 && n1 >= 1 && n1 <= 64 && n2 >= 1 && n2 <= 64 && n3 >= 1 && n3 <= 32;
+}
+
+hipError_t launch_stage_any(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
+                            float *logits, uint32_t row_lo, uint32_t row_hi, hipStream_t stream) {
+    if (row_hi <= row_lo) return hipSuccess;
+    if (!stage_any_fits(sp.f, sp.n1, sp.n2, sp.n3) || row_hi > g.hi() || row_lo < g.lo()) return hipErrorInvalidValue;
+    const AnyGraph plain{g.rowptr, g.col, g.w, g.nw};
+    const StageAnyLayout L = stage_any_layout(sp.f, sp.n1, sp.n2, sp.n3);
+    const size_t lds = (size_t)L.total * sizeof(float);   // <= 53 KB at the largest widths
+    // a persistent grid: as many workgroups as the LDS lets a CU hold (at most 8), on 256 CUs
+    const unsigned per_cu = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (160u * 1024u) / (lds + 1024u)));
+    const unsigned need = (unsigned)(((size_t)(row_hi - row_lo) + kAnyRows - 1) / kAnyRows);
+    const dim3 grid(std::min(need, 256u * per_cu)), block(kAnyBlock);
+    hipLaunchKernelGGL(k_stage_any, grid, block, lds, stream, plain, ws, params + sp.param_offset, in, out, sp.sigmoid_last ? logits : nullptr, row_lo, row_hi,
+                       sp.f, sp.n1, sp.n2, sp.n3, sp.sigmoid_last ? 1 : 0);
+    return hipGetLastError();
+}
+
+}  // namespace gnnvc
