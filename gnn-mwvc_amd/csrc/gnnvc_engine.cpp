@@ -298,9 +298,16 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
     return GNNVC_OK;
 }
 
+// stage sp over rows [lo, hi) of the engine's graph, on its stream
+gnnvc::StageCall stage_call(const gnnvc_engine *e, const gnnvc::StagePlan &sp, const float *in, float *out, float *logits, uint32_t lo,
+                            uint32_t hi) {
+    return {.sp = &sp, .g = &e->g, .ws = e->ws, .params = e->params.p, .in = in, .out = out, .logits = logits, .row_lo = lo,
+            .row_hi = hi, .stream = e->stream};
+}
+
 // fork: the long (and giant) rows of this stage beside the tile kernel
-int launch_side_rows(gnnvc_engine *e, const GraphDev &gv, int stage, uint32_t lo, uint32_t hi, const float *in, float *out,
-                     float *logits, uint32_t thr, bool plain_f1) {
+int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr, bool plain_f1) {
+    const GraphDev &gv = *call.g;
     // One side queue beside the main one (ensure_side_streams).  The giant rows' walk is a latency chain on a few waves and
     // always goes there; the long rows join it — unless that walk is what a stage waits for (find_giant: the power-law graph),
     // then they run ahead of the tile kernel on the main queue instead: power-law 1 M 0.89 ms (long rows beside the giant
@@ -312,7 +319,9 @@ int launch_side_rows(gnnvc_engine *e, const GraphDev &gv, int stage, uint32_t lo
     hipStream_t s_giant = !side ? e->stream : (long_on_main ? e->giant_stream : e->long_stream);
     e->side_join = !side ? 0 : (long_on_main ? 2 : 1);
     // rows from this degree on go the giant way in this stage
-    const uint32_t giant_from = e->stages[stage].f == 16 ? e->giant_f16() : e->giant_thresh;
+    const uint32_t giant_from = call.sp->f == 16 ? e->giant_f16() : e->giant_thresh;
+    gnnvc::StageCall giant = call;   // (on the main queue until the fork; the pruned view only where the option asks for it)
+    if (!e->opt_prune_giant) giant.g = &e->g;
     gnnvc::GiantRows gr;
     bool gather_first = false;
     if (e->n_giant) {
@@ -337,9 +346,7 @@ int launch_side_rows(gnnvc_engine *e, const GraphDev &gv, int stage, uint32_t lo
         // for a kernel that takes 0.6 alone; the stage 6.1 ms against the tile kernel's 3.3)
         gather_first = side && (e->opt_giant_gather_first < 0 ? (!long_on_main && (e->giant_entries <= (16ull << 20) || plain_f1))
                                                                : e->opt_giant_gather_first != 0);
-        if (gather_first)
-            HIP_TRY(e, gnnvc::launch_giant_stage(e->stages[stage], e->opt_prune_giant ? gv : e->g, e->ws, e->params.p, in, out, logits, lo, hi,
-                                                 gr, e->stream, giant_from, /*part=*/1));
+        if (gather_first) HIP_TRY(e, gnnvc::launch_giant_stage(giant, gr, giant_from, gnnvc::GiantPart::kGather));
     }
     if (side) {
         HIP_TRY(e, hipEventRecord(e->ev_fork, e->stream));
@@ -347,22 +354,29 @@ int launch_side_rows(gnnvc_engine *e, const GraphDev &gv, int stage, uint32_t lo
     }
     if (e->n_giant) {   // the heaviest rows: beside the tile kernel
         if (long_on_main) HIP_TRY(e, hipStreamWaitEvent(e->giant_stream, e->ev_fork, 0));
-        HIP_TRY(e, gnnvc::launch_giant_stage(e->stages[stage], e->opt_prune_giant ? gv : e->g, e->ws, e->params.p, in, out, logits, lo, hi, gr,
-                                             s_giant, giant_from, gather_first ? 2 : 0));
+        giant.stream = s_giant;
+        HIP_TRY(e, gnnvc::launch_giant_stage(giant, gr, giant_from, gather_first ? gnnvc::GiantPart::kAfterGather : gnnvc::GiantPart::kAll));
         if (long_on_main) HIP_TRY(e, hipEventRecord(e->ev_giant, e->giant_stream));
     }
     // (with rows classed by the entries they have left, k_long_* takes rows from gv.eff_thresh entries on whatever their degree)
     const uint32_t long_from = gv.prune_eff ? std::min(thr, gv.eff_thresh) : thr;
-    if ((e->n_giant < e->n_long || giant_from > e->giant_thresh) && long_from < giant_from)   // (equal: a plan or the giant kernels have every row in between)
-        HIP_TRY(e, gnnvc::launch_long_stage(e->stages[stage], gv, e->ws, e->params.p, in, out, logits, lo, hi,
-                                            e->long_list.p, e->n_long, thr, giant_from, s_long));
+    if ((e->n_giant < e->n_long || giant_from > e->giant_thresh) && long_from < giant_from) {   // (equal: a plan or the giant kernels have every row in between)
+        gnnvc::StageCall lng = call;
+        lng.stream = s_long;
+        HIP_TRY(e, gnnvc::launch_long_stage(lng, {.list = e->long_list.p, .n = e->n_long, .min_deg = thr, .max_deg = giant_from}));
+    }
     if (side_long) HIP_TRY(e, hipEventRecord(e->ev_long, e->long_stream));
     return GNNVC_OK;
 }
 
-int launch_main(gnnvc_engine *e, const StageChoice &c, const GraphDev &gv, const gnnvc::SortedOrder &so_p, int stage, uint32_t lo,
-                uint32_t hi, const float *in, float *out, float *logits) {
-    const gnnvc::StagePlan &sp = e->stages[stage];
+// call: the stage on the view of the graph the gathering kernels take (gather_view); the plans' launches see the graph itself
+int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &call, const gnnvc::SortedOrder &so_p, int stage) {
+    const gnnvc::StagePlan &sp = *call.sp;
+    const GraphDev &gv = *call.g;
+    const uint32_t lo = call.row_lo, hi = call.row_hi;
+    const float *in = call.in;
+    gnnvc::StageCall plain = call;
+    plain.g = &e->g;
     gnnvc::EmitArgs emit;
     // (the counters are zeroed only AFTER this stage's own k_c4_choose has read what the previous stage kernel left in them)
     auto arm_emit = [&]() -> int {
@@ -391,8 +405,10 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const GraphDev &gv, const
         pe.spec = e->c4_desc.p + 2 * gnnvc_engine::kDescWords + 4;   // a word that is always 0: count, do not write table rows
         pe.table = e->c4_table.p;
         pe.counts = e->c4_emit_counts.p;
-        HIP_TRY(e, gnnvc::launch_stage(sp, e->g, e->ws, e->params.p, in, out, nullptr, lo, lo + rows, 0xFFFFFFFFu, /*mfma=*/false, nullptr,
-                                       /*interleave=*/true, e->stream, nullptr, nullptr, nullptr, false, pe));
+        gnnvc::StageCall first = plain;   // (every row of them on VALU tiles, no logits)
+        first.row_hi = lo + rows;
+        first.logits = nullptr;
+        HIP_TRY(e, gnnvc::launch_stage(first, {.interleave = true, .emit = pe}));
         HIP_TRY(e, gnnvc::compact_choose(e->c4_emit_counts.p, 64, rows, cons, 1u, e->stream));
         return GNNVC_OK;
     };
@@ -405,14 +421,14 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const GraphDev &gv, const
     if (c.sums == StageChoice::kTableTiles) {
         uint32_t *d_in = e->t4_desc_of(stage, e->t4_parity), *d_out = e->t4_desc_of(stage, e->t4_parity ^ 1u);
         const bool solo = e->t4_fit_seen[stage] && e->opt_t4_solo;
-        HIP_TRY(e, gnnvc::launch_stage_t4(sp, e->g, e->ws, e->params.p, in, out, logits, lo, hi, e->interleave, e->stream,
-                                          e->t4_table[stage - 1].p, e->t4_counts_of(stage, e->t4_parity),
-                                          e->t4_counts_of(stage, e->t4_parity ^ 1u), d_in, d_out, emit, solo));
+        HIP_TRY(e, gnnvc::launch_stage_t4(plain, {.table_in = e->t4_table[stage - 1].p,
+                                                  .counts_in = e->t4_counts_of(stage, e->t4_parity),
+                                                  .counts_zero = e->t4_counts_of(stage, e->t4_parity ^ 1u),
+                                                  .desc_in = d_in, .desc_out = d_out, .emit = emit, .interleave = e->interleave, .solo = solo}));
         if (solo) return GNNVC_OK;
         // ... and the gathering kernel, which leaves at once when the table tiles did the rows (d_out[8]: decided on the device)
-        return hip_rc(e, gnnvc::launch_stage(sp, gv, e->ws, e->params.p, in, out, logits, lo, hi, c.long_thresh, c.mfma, nullptr,
-                                             e->interleave, e->stream, nullptr, nullptr, nullptr, false, gnnvc::EmitArgs(), true, nullptr,
-                                             nullptr, d_out + 8));
+        return hip_rc(e, gnnvc::launch_stage(call, {.long_thresh = c.long_thresh, .mfma = c.mfma, .interleave = e->interleave,
+                                                    .skip_flag = d_out + 8}));
     }
     if (c.sums == StageChoice::kLdsTable || c.sums == StageChoice::kBlocked) {
         int rc = pilot();
@@ -420,23 +436,22 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const GraphDev &gv, const
         rc = arm_emit();
         if (rc) return rc;
     }
-    if (c.sums == StageChoice::kLdsTable)
-        return hip_rc(e, gnnvc::launch_stage0_lds_table(sp, e->g, e->ws, e->params.p, in, out, lo, hi, e->lt_rows, e->lt_stepptr.p,
-                                                        e->lt_steps.p, e->lt_entries.p, e->lt_bytes.p, e->blk_acc.p, e->lt_bad.p,
-                                                        c.long_thresh, e->opt_mfma == 1, e->interleave, e->stream, emit,
-                                                        e->lt_last_entry, e->lt_mapped ? e->lt_rowmap.p : nullptr,
-                                                        e->lt_mapped ? e->lt_chunks : 0u, e->lt_base, e->lt_end, e->lt_bits));
+    if (c.sums == StageChoice::kLdsTable)   // (the sums share the blocked plan's buffer)
+        return hip_rc(e, gnnvc::launch_stage0_lds_table(plain, lds_table_plan(e), e->lt_bytes.p, e->blk_acc.p, e->lt_bad.p,
+                                                        {.long_thresh = c.long_thresh, .mfma = e->opt_mfma == 1,
+                                                         .interleave = e->interleave, .emit = emit}));
     if (c.sums == StageChoice::kBlocked)
-        return hip_rc(e, gnnvc::launch_stage0_blocked(sp, e->g, e->ws, e->params.p, in, out, lo, hi, e->blk_count, e->blk_ptr.p,
-                                                      e->blk_col.p, e->blk_acc.p, e->long_thresh, e->opt_mfma == 1, e->interleave,
-                                                      e->stream, emit));
-    const float *acc4 = nullptr;
+        return hip_rc(e, gnnvc::launch_stage0_blocked(plain,
+                                                      {.nblocks = e->blk_count, .bp = e->blk_ptr.p, .colb = e->blk_col.p, .acc = e->blk_acc.p},
+                                                      {.long_thresh = e->long_thresh, .mfma = e->opt_mfma == 1,
+                                                       .interleave = e->interleave, .emit = emit}));
+    gnnvc::CompactSums sums;   // (all null: the compact-table plan is not in this call)
     uint32_t *desc = nullptr;
     if (c.sums == StageChoice::kCompactPrepared || c.sums == StageChoice::kCompactWhole) {
         desc = e->c4_desc.p + gnnvc_engine::kDescWords * (stage - 1);
         e->c4_last_desc = gnnvc_engine::kDescWords * (stage - 1);
         if (c.sums == StageChoice::kCompactWhole) e->fit_used[stage] = true;
-        acc4 = e->c4_acc.p;
+        sums = {.acc4 = e->c4_acc.p, .c4desc = desc, .agg16 = e->c4_agg16.p, .table_in = e->opt_dense_skip ? e->c4_table.p : nullptr};
         const bool whole = c.sums == StageChoice::kCompactWhole;
         if (whole && !c.fused_counts) HIP_TRY(e, gnnvc::column_counts(in, e->g.n, e->c4_counts.p, e->stream));
         const bool fused = whole && c.fused_counts;
@@ -457,15 +472,14 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const GraphDev &gv, const
     // Wide tiles (k_stage_w*): a graph with fewer tiles than the chip has SIMDs — the reference CLI's later predict calls — and
     // nothing but the plain gather to run (no plan, no long rows, no pruned adjacency, nothing to emit): a workgroup per tile
     if (c.sums == StageChoice::kGather && e->opt_wide && e->g.n <= (sp.f == 16 ? e->opt_wide_max_n16 : e->opt_wide_max_n) && !e->g.sliced() && e->n_long == 0 && !sop &&
-        !acc4 && !emit.counts && gv.prune_bad == nullptr && gv.zero_bits == nullptr && sp.variant >= 0 && sp.variant <= 2) {
+        !sums.acc4 && !emit.counts && gv.prune_bad == nullptr && gv.zero_bits == nullptr && sp.variant >= 0 && sp.variant <= 2) {
         e->wide_used = true;
         e->stage_wide = true;
-        return hip_rc(e, gnnvc::launch_stage_wide(sp, e->g, e->ws, e->params.p, in, out, logits, lo, hi, e->stream));
+        return hip_rc(e, gnnvc::launch_stage_wide(plain));
     }
-    HIP_TRY(e, gnnvc::launch_stage(sp, gv, e->ws, e->params.p, in, out, logits, lo, hi, c.long_thresh, c.mfma, sop,
-                                   e->interleave, e->stream, acc4, desc, e->c4_agg16.p, e->opt_mfma == 1, emit,
-                                   /*dense_part=*/!c.rounds, so_p.vertex ? &so_p : nullptr,
-                                   (acc4 && e->opt_dense_skip) ? e->c4_table.p : nullptr));
+    HIP_TRY(e, gnnvc::launch_stage(call, {.long_thresh = c.long_thresh, .mfma = c.mfma, .so = sop, .interleave = e->interleave,
+                                          .sums = sums, .mfma_agg = e->opt_mfma == 1, .emit = emit, .dense_part = !c.rounds,
+                                          .so_pruned = so_p.vertex ? &so_p : nullptr}));
     if (!c.rounds) return GNNVC_OK;
     HIP_TRY(e, hipMemsetAsync(desc + 5, 0, sizeof(uint32_t), e->stream));        // dirty-row counter
     HIP_TRY(e, hipMemsetAsync(e->c4_marks.p, 0, sizeof(uint32_t), e->stream));   // marks[0]
@@ -491,8 +505,11 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const GraphDev &gv, const
         }
         HIP_TRY(e, gnnvc::compact_fix(e->g, in, desc, e->c4_dirty.p, e->c4_dirty_cap, e->c4_agg16.p, e->c4_marks.p + k, ds,
                                       /*blocks=*/64));
-        HIP_TRY(e, gnnvc::launch_dense_sigmoid(sp, e->g, e->ws, e->params.p, in, out, logits, ra, rb, e->c4_acc.p, desc,
-                                               e->c4_agg16.p, ds, 0xFFFFFFFFu, e->opt_dense_skip ? e->c4_table.p : nullptr));
+        gnnvc::StageCall round = plain;
+        round.row_lo = ra;
+        round.row_hi = rb;
+        round.stream = ds;
+        HIP_TRY(e, gnnvc::launch_dense_sigmoid(round, sums, /*long_thresh=*/0xFFFFFFFFu));
     }
     if (nrounds > 1) {
         HIP_TRY(e, hipEventRecord(e->ev_join, e->aux_stream));
@@ -530,12 +547,13 @@ int run_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float 
     gnnvc::SortedOrder so_p;
     rc = gather_view(e, stage, lo, hi, in, c.sums == StageChoice::kGather, c.sorted.n != 0, gv, so_p, c.mfma, c.long_thresh);
     if (rc) return rc;
+    gnnvc::StageCall call = stage_call(e, e->stages[stage], in, out, logits, lo, hi);
+    call.g = &gv;
     if (longs) {
-        rc = launch_side_rows(e, gv, stage, lo, hi, in, out, logits, c.long_thresh,
-                              /*plain_f1=*/e->stages[stage].f == 1 && c.sums == StageChoice::kGather);
+        rc = launch_side_rows(e, call, c.long_thresh, /*plain_f1=*/call.sp->f == 1 && c.sums == StageChoice::kGather);
         if (rc) return rc;
     }
-    rc = launch_main(e, c, gv, so_p, stage, lo, hi, in, out, logits);
+    rc = launch_main(e, c, call, so_p, stage);
     if (rc) return rc;
     if (longs && e->side_join) {   // join: the side queue's last kernel of this stage
         if (e->side_join == 1) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_long, 0));
@@ -565,8 +583,8 @@ int audit_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
     const gnnvc::StagePlan &sp = e->stages[stage];
     if (e->opt_audit_flip_stage == stage && e->opt_audit_flip_row >= lo && e->opt_audit_flip_row < hi)
         HIP_TRY(e, gnnvc::launch_audit_flip(out, (size_t)e->opt_audit_flip_row * (size_t)sp.n3, e->stream));
-    HIP_TRY(e, gnnvc::launch_audit_stage(sp, e->g, e->ws, e->params.p, in, out, sp.sigmoid_last ? logits : nullptr, lo, hi,
-                                         e->audit_rec.p + slot * gnnvc::kAuditWords, e->opt_audit_repair != 0, e->stream));
+    HIP_TRY(e, gnnvc::launch_audit_stage(stage_call(e, sp, in, out, sp.sigmoid_last ? logits : nullptr, lo, hi),
+                                         e->audit_rec.p + slot * gnnvc::kAuditWords, /*repair=*/e->opt_audit_repair != 0));
     e->audit_pending.push_back(gnnvc_engine::AuditCheck{stage, lo, hi, std::move(plan)});
     return GNNVC_OK;
 }
@@ -661,7 +679,7 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
     for (size_t s = 0; s < st.size(); ++s) {
         const bool last = s + 1 == st.size();
         float *dst = last ? d_out : e->scratch[s & 1].p;
-        HIP_TRY(e, gnnvc::launch_stage_any(st[s], e->g, e->ws, e->params.p, cur, dst, last ? d_logits : nullptr, 0, n, e->stream));
+        HIP_TRY(e, gnnvc::launch_stage_any(stage_call(e, st[s], cur, dst, last ? d_logits : nullptr, 0, n)));
         cur = dst;
     }
     return GNNVC_OK;
@@ -1550,7 +1568,7 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     if (rc) return rc;
     if (e->generic_on()) {   // (k_stage_any: one launch, no plan; a generic stage audits nothing)
         const StagePlan &sp = e->gstages[stage];
-        HIP_TRY(e, gnnvc::launch_stage_any(sp, e->g, e->ws, e->params.p, d_in, d_out, sp.sigmoid_last ? d_logits : nullptr, row_lo, row_hi, e->stream));
+        HIP_TRY(e, gnnvc::launch_stage_any(stage_call(e, sp, d_in, d_out, sp.sigmoid_last ? d_logits : nullptr, row_lo, row_hi)));
         return GNNVC_OK;
     }
     if (!audit) return run_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits);

@@ -495,6 +495,7 @@ int c4_begin(gnnvc_engine *e, uint32_t base, uint32_t end);
 int c4_advance(gnnvc_engine *e, uint32_t upto, hipStream_t stream);
 int c4_finish(gnnvc_engine *e);
 gnnvc::CompactPlan compact_plan(const gnnvc_engine *e);
+gnnvc::LdsTablePlan lds_table_plan(const gnnvc_engine *e);
 int ensure_side_streams(gnnvc_engine *e);
 int reprobe_side_streams(gnnvc_engine *e);
 int ensure_round_events(gnnvc_engine *e, size_t count);

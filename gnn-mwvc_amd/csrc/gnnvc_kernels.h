@@ -95,9 +95,21 @@ void set_kernel_trace(KernelTraceSink *sink);   // nullptr = off
 // Returns the instantiation index for a stage shape, or -1.
 int stage_variant(int f, int n1, int n2, int n3, int sigmoid_last);
 
-// Fused stage over rows [row_lo, row_hi).  in: F=1 -> n floats; F=16 -> (n+1) x 16
-// with a zero last row.  out: (n+1) x n3 rows (n3 = 16) or, for the sigmoid
-// stage, out = scores[n], logits optional.
+// What every stage launcher is told: stage *sp over rows [row_lo, row_hi) of *g, on `stream`.  in: F=1 -> n floats;
+// F=16 -> (n+1) x 16 with a zero last row.  out: (n+1) x n3 rows (n3 = 16) or, for the sigmoid stage, out = scores[n],
+// logits optional.  A stage that issues several launches copies the struct and changes the named field (another view
+// of the graph, a side stream, a part of the rows).
+struct StageCall {
+    const StagePlan *sp = nullptr;
+    const GraphDev *g = nullptr;
+    float ws = 0.0f;
+    const float *params = nullptr;   // the engine's parameter buffer (the launchers add sp->param_offset)
+    const float *in = nullptr;
+    float *out = nullptr, *logits = nullptr;
+    uint32_t row_lo = 0, row_hi = 0;
+    hipStream_t stream = nullptr;
+};
+
 // Producer side of the compact-table plan: a stage kernel whose dense layers run on the VALU can count the
 // non-zeros of the rows it writes (64 slots x 17 counters, zeroed by the caller) and write their compact form for
 // the columns chosen at the previous forward (spec = that forward's desc), see c4_emit.  All null = off.
@@ -108,18 +120,33 @@ struct EmitArgs {
 };
 constexpr int kEmitCounters = 64 * 17;
 
-hipError_t launch_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params,
-                        const float *in, float *out, float *logits, uint32_t row_lo,
-                        uint32_t row_hi, uint32_t long_thresh, bool mfma, const SortedOrder *so,
-                        bool interleave, hipStream_t stream, const float *acc4 = nullptr,
-                        const uint32_t *c4desc = nullptr, const float *agg16 = nullptr, bool mfma_agg = false,
-                        const EmitArgs &emit = EmitArgs(),
-                        bool dense_part = true /* false: only the gathering kernel (which leaves at once when the compact-table
-                                                  plan applies); the caller launches the sums and the dense kernel itself */,
-                        const SortedOrder *so_pruned = nullptr /* g.prune_eff: the tile order by entries left (meta = pruned ranges) */,
-                        const float *table_in = nullptr /* acc4: the compact table of THIS stage's input (one pass), so that the dense
-                                                           kernel takes a row's own live values from it; null = from the full rows */,
-                        const uint32_t *skip_flag = nullptr /* (no acc4) a device word: != 0 = another kernel has done this launch's rows */);
+// Consumer side of the compact-table plan: what a stage's dense layers take in place of a gather.  acc4 null = the plan is not
+// in this call.
+struct CompactSums {
+    const float *acc4 = nullptr;        // the four sums per row and pass
+    const uint32_t *c4desc = nullptr;   // the device's choice of columns and its verdict on this input
+    const float *agg16 = nullptr;       // the full sums of the rows the table does not serve
+    const float *table_in = nullptr;    // the compact table of THIS stage's input (one pass), so that the dense kernel takes a
+                                        // row's own live values from it; null = from the full rows
+};
+
+// Fused stage on 64-vertex tiles, a wave per tile (k_stage_f1 / k_stage_f16): what the tile kernels are told beyond the call.
+struct TileArgs {
+    uint32_t long_thresh = 0xFFFFFFFFu;       // rows at least this long are another kernel's (the default: none is)
+    bool mfma = false;                        // dense layers on the matrix cores
+    const SortedOrder *so = nullptr;          // degree-sorted tile order of the range; null = natural tiles
+    bool interleave = false;                  // natural tiles dealt round-robin over the workgroups
+    // The gathering kernel takes ONE device word that can tell it to leave at once: sums.c4desc when sums.acc4 is set (the
+    // compact-table plan fits this input), else skip_flag (!= 0 = another kernel has done this launch's rows).
+    CompactSums sums;
+    const uint32_t *skip_flag = nullptr;
+    bool mfma_agg = false;                    // sums: the aggregate-only dense layers on the matrix cores, not the VALU
+    EmitArgs emit;
+    bool dense_part = true;                   // false: only the gathering kernel (which leaves at once when the compact-table plan
+                                              // applies); the caller launches the sums and the dense kernel itself
+    const SortedOrder *so_pruned = nullptr;   // g.prune_eff: the tile order by entries left (meta = pruned ranges)
+};
+hipError_t launch_stage(const StageCall &c, const TileArgs &a);
 // What a hand-off wants to know about a graph before it accepts and classes it, in ONE pass of the stream and one wait (round 4;
 // it used to be four round trips — the checks, nine row pointers, the tiles' lockstep cost, the long rows — 0.2 of a mid-size
 // graph's 0.3 ms attach): k_validate_graph, then (all three read row pointers only, so an invalid graph cannot send them astray)
@@ -140,14 +167,13 @@ struct VerdictWords {
 };
 hipError_t write_verdicts(const VerdictWords &vw, uint32_t *out_dev, hipStream_t stream);
 
-// On-device audit (option "audit_period", k_audit_stage): stage sp recomputed for rows [row_lo, row_hi) from `in` by code that
-// uses none of the plans (the graph's rowptr / col / w / nw only), every value of out (and logits, when non-null, for the sigmoid
-// stage) compared bit for bit.  rec: kAuditWords zeroed words — [0] mismatches, [1] NaN pairs (equal), [2] repairs, and for
-// the first mismatching row: [3] ~(row << 32 | column: + 64 for a logit), [4] ~(row << 32 | fused bits), [5] ~(row << 32 |
-// audit bits).  repair: the audit's value is written over every mismatching one.
+// On-device audit (option "audit_period", k_audit_stage): the call's stage recomputed for its rows from `in` by code that
+// uses none of the plans (the graph's rowptr / col / w / nw only: whatever view c.g holds is dropped), every value of out (and
+// logits, when non-null, for the sigmoid stage) compared bit for bit.  rec: kAuditWords zeroed words — [0] mismatches, [1] NaN
+// pairs (equal), [2] repairs, and for the first mismatching row: [3] ~(row << 32 | column: + 64 for a logit), [4] ~(row << 32 |
+// fused bits), [5] ~(row << 32 | audit bits).  repair: the audit's value is written over every mismatching one.
 constexpr int kAuditWords = 8;
-hipError_t launch_audit_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                              float *logits, uint32_t row_lo, uint32_t row_hi, unsigned long long *rec, bool repair, hipStream_t stream);
+hipError_t launch_audit_stage(const StageCall &c, unsigned long long *rec, bool repair);
 // the audit's test hook: out[at]'s lowest mantissa bit flipped by one lane
 hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 
@@ -156,27 +182,29 @@ hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 // widths.  One launch per call; the graph's rowptr / col / w / nw only (no plan); rows of every degree.  in: (n + 1) x f rows
 // (the pad row is never read), out: rows [row_lo, row_hi) of an (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
 bool stage_any_fits(int f, int n1, int n2, int n3);
-hipError_t launch_stage_any(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                            float *logits, uint32_t row_lo, uint32_t row_hi, hipStream_t stream);
+hipError_t launch_stage_any(const StageCall &c);
 
 // a whole stage (variants 0, 1, 2) on WIDE tiles — a workgroup per 64-vertex tile, the tile's gather and each dense layer's outputs
 // split over its four waves (k_stage_w1 / k_stage_w16): graphs with fewer tiles than the chip has SIMDs, no long rows
-hipError_t launch_stage_wide(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                             float *logits, uint32_t row_lo, uint32_t row_hi, hipStream_t stream);
+hipError_t launch_stage_wide(const StageCall &c);
 // a 16-wide stage (variant 1 or 2) from the L2-resident compact table of its input (k_stage_t4: graphs of 50 - 400 K vertices, whole
 // forwards): table_in = (n + 1) rows of 16 bytes written by the producer of the input (EmitArgs) for the columns in desc_in,
 // counts_in = that producer's kEmitCounters; desc_out (another 16 words) receives this forward's choice — the next forward's
 // spec — and desc_out[8] = 1 iff the kernel did the rows (the gathering kernel launched behind it takes desc_out + 8 as skip_flag)
-hipError_t launch_stage_t4(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out, float *logits,
-                           uint32_t row_lo, uint32_t row_hi, bool interleave, hipStream_t stream, const float *table_in,
-                           const unsigned long long *counts_in, unsigned long long *counts_zero /* the other parity's set, cleared here */,
-                           const uint32_t *desc_in, uint32_t *desc_out, const EmitArgs &emit,
-                           bool solo = false /* no gathering kernel follows: a table that does not fit is handled inside, the slow way */);
-// the dense layers + sigmoid of the last stage when its aggregates are ready (compact-table plan)
-hipError_t launch_dense_sigmoid(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                                float *logits, uint32_t row_lo, uint32_t row_hi, const float *acc4, const uint32_t *c4desc,
-                                const float *agg16, hipStream_t stream, uint32_t long_thresh = 0xFFFFFFFFu /* rows at least this long are not this kernel's */,
-                                const float *table_in = nullptr /* as launch_stage's */);
+struct TableTileArgs {
+    const float *table_in = nullptr;
+    const unsigned long long *counts_in = nullptr;
+    unsigned long long *counts_zero = nullptr;   // the other parity's set, cleared here
+    const uint32_t *desc_in = nullptr;
+    uint32_t *desc_out = nullptr;
+    EmitArgs emit;
+    bool interleave = false;                     // as TileArgs'
+    bool solo = false;   // no gathering kernel follows: a table that does not fit is handled inside, the slow way
+};
+hipError_t launch_stage_t4(const StageCall &c, const TableTileArgs &a);
+// the dense layers + sigmoid of the last stage when its aggregates are ready (compact-table plan); rows at least long_thresh
+// long are not this kernel's
+hipError_t launch_dense_sigmoid(const StageCall &c, const CompactSums &s, uint32_t long_thresh);
 
 // Building blocks of the degree-sorted order (the prefix over the few thousand degree classes
 // is done on the host).
@@ -199,9 +227,11 @@ hipError_t degree_scatter(const GraphDev &g, uint32_t row_lo, uint32_t row_hi, u
 // same threshold; pass 0xFFFFFFFF to make them handle every row.
 hipError_t find_long_rows(const GraphDev &g, uint32_t thresh, uint32_t *list, uint32_t *count,
                           hipStream_t stream);
-hipError_t launch_long_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params,
-                             const float *in, float *out, float *logits, uint32_t row_lo, uint32_t row_hi,
-                             const uint32_t *list, uint32_t n_long, uint32_t min_deg, uint32_t max_deg, hipStream_t stream);
+struct LongRows {
+    const uint32_t *list = nullptr;   // find_long_rows' list and count
+    uint32_t n = 0, min_deg = 0, max_deg = 0xFFFFFFFFu;   // listed rows of a degree outside [min_deg, max_deg) are another kernel's
+};
+hipError_t launch_long_stage(const StageCall &c, const LongRows &lr);
 
 // Giant rows (degree >= the giant threshold, a subset of the long rows): the same CSR-order fp32 sums evaluated in
 // parallel (exact_sum.h).  meta: uint4[n + 1] {row, first CSR entry, degree, first gather block}, the last entry's
@@ -222,9 +252,10 @@ uint32_t giant_window();
 uint32_t giant_block();
 hipError_t find_giant_rows(const GraphDev &g, const uint32_t *list, uint32_t n_long, uint32_t thresh, void *meta, uint32_t *count,
                            hipStream_t stream);
-hipError_t launch_giant_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                              float *logits, uint32_t row_lo, uint32_t row_hi, const GiantRows &gr, hipStream_t stream,
-                              uint32_t min_deg = 0 /* listed rows below this degree are another kernel's in this stage */, int part = 0);
+// min_deg: listed rows below this degree are another kernel's in this stage.  The engine puts the gather on one queue and
+// everything behind it on another, hence the parts.
+enum class GiantPart { kAll, kGather, kAfterGather };
+hipError_t launch_giant_stage(const StageCall &c, const GiantRows &gr, uint32_t min_deg, GiantPart part);
 hipError_t stream_sums(const float *streams_dev, uint32_t streams, uint32_t len, void *meta, unsigned long long *off, float *agg,
                        int mode /* 0 on several waves, 2 on one wave: the same exact sum */, hipStream_t stream, float *segsum = nullptr,
                        void *segmap = nullptr);
@@ -237,11 +268,19 @@ size_t blocked_scan_scratch_elems(size_t n_elems);
 hipError_t build_blocked_index(const GraphDev &g, uint32_t wb, uint32_t nblocks, uint32_t long_thresh,
                                uint32_t *bp, uint32_t *colb, uint32_t *scratch, uint32_t *bad_flag,
                                hipStream_t stream);
-hipError_t launch_stage0_blocked(const StagePlan &sp, const GraphDev &g, float ws, const float *params,
-                                 const float *x, float *out, uint32_t row_lo, uint32_t row_hi,
-                                 uint32_t nblocks, const uint32_t *bp, const uint32_t *colb, float *acc,
-                                 uint32_t long_thresh, bool mfma, bool interleave, hipStream_t stream,
-                                 const EmitArgs &emit = EmitArgs());
+struct BlockedPlan {   // the per-graph part (build_blocked_index) and the sums' scratch
+    uint32_t nblocks = 0;
+    const uint32_t *bp = nullptr, *colb = nullptr;
+    float *acc = nullptr;
+};
+// what the tile kernel behind an F = 1 plan's sums is told per call (as TileArgs' fields of these names)
+struct Stage0Args {
+    uint32_t long_thresh = 0xFFFFFFFFu;
+    bool mfma = false;
+    bool interleave = false;
+    EmitArgs emit;
+};
+hipError_t launch_stage0_blocked(const StageCall &c, const BlockedPlan &bp, const Stage0Args &a);
 
 // Layer-by-layer kernels (any model; also the layer-level ABI entry points).
 hipError_t launch_graph_layer(const GraphDev &g, float ws, uint32_t f, const float *in,
@@ -324,16 +363,21 @@ hipError_t deal_rows(const GraphDev &g, const uint32_t *sorted_rows, uint32_t m,
                      uint32_t *rowmap, uint32_t *weight, hipStream_t stream);
 // cand[k] = first row whose CSR offset reaches k * target: column ranges of equal entry mass on a symmetric adjacency
 hipError_t mass_bounds(const GraphDev &g, unsigned long long target, uint32_t count, uint32_t *cand, hipStream_t stream);
-hipError_t launch_stage0_lds_table(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *x,
-                                   float *out, uint32_t row_lo, uint32_t row_hi, uint32_t rows_per_chunk,
-                                   const uint32_t *step_ptr, const void *steps, const uint32_t *entries,
-                                   uint8_t *wbyte /* lds_table_bytes_for(bits, n) bytes: rewritten from x by every launch */,
-                                   float *acc, uint32_t *bad, uint32_t long_thresh, bool mfma, bool interleave,
-                                   hipStream_t stream, const EmitArgs &emit, uint32_t last_entry,
-                                   const uint32_t *rowmap = nullptr /* skewed graphs: the plan's rows, slice by slice */,
-                                   uint32_t mapped_chunks = 0,
-                                   uint32_t plan_base = 0, uint32_t plan_end = 0xFFFFFFFFu /* the plan's row range (a rank's rows) */,
-                                   uint32_t bits = 8 /* width of the table's entries (the plan's blocks were laid out for it) */);
+struct LdsTablePlan {   // the per-graph part of the plan, as the launch needs it
+    uint32_t rows_per_chunk = 0;
+    uint32_t plan_base = 0, plan_end = 0xFFFFFFFFu;   // the plan's row range (a rank's rows)
+    uint32_t bits = 8;                   // width of the table's entries (the plan's blocks were laid out for it)
+    uint32_t last_entry = 0;             // last index of entries[] a 16-byte read may start at
+    uint32_t mapped_chunks = 0;          // chunks in rowmap
+    const uint32_t *step_ptr = nullptr;
+    const void *steps = nullptr;
+    const uint32_t *entries = nullptr;
+    const uint32_t *rowmap = nullptr;    // skewed graphs: the plan's rows, slice by slice; null: consecutive rows
+};
+// wbyte: lds_table_bytes_for(bits, n) bytes, rewritten from the call's input by every launch; acc: float[n] sums; *bad != 0
+// afterwards: this input does not match the table, and the tile kernel has gathered instead
+hipError_t launch_stage0_lds_table(const StageCall &c, const LdsTablePlan &lp, uint8_t *wbyte, float *acc, uint32_t *bad,
+                                   const Stage0Args &a);
 
 // compact-table plan of the 16-wide stages (see the k_c4_* kernels); the step layout is built with the
 // lds_table_* functions per SLICE (rows_per_chunk / compact_slices() rows), compact_step() entries per step,
@@ -350,13 +394,12 @@ struct CompactPlan {   // the per-graph part of the plan, as the launches need i
     uint32_t rows_per_chunk = 0, block_cols = 0, nblocks = 0, plan_base = 0, plan_end = 0;
     uint32_t last_entry = 0;             // last index of entries[] a 16-byte read may start at
     uint32_t nslices = 0;                // mapped plans: slices in rowmap
-    uint32_t max_passes = 1;             // tables of four columns the device may choose for one input (<= compact_max_passes())
+    uint32_t max_passes = 1;             // tables of four columns the device may choose for one input
     const uint32_t *step_ptr = nullptr;
     const void *steps = nullptr;
     const uint32_t *entries = nullptr;
     const uint32_t *rowmap = nullptr;    // null: slices of consecutive rows
 };
-uint32_t compact_max_passes();
 // table: max_passes x (n + 1) rows of 16 bytes, acc4: max_passes x n
 hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const float *in, const unsigned long long *counts,
                                  int count_slots, uint32_t *desc, float *table, float *acc4, uint32_t row_lo, uint32_t row_hi,
@@ -413,10 +456,9 @@ hipError_t validate_graph(const GraphDev &g, uint32_t *flags, hipStream_t stream
 hipError_t validate_rowptr(const GraphDev &g, uint32_t *flags, hipStream_t stream);   // row pointers only (bit1 as validate_graph)
 hipError_t narrow_rowptr(const void *in_u64, uint32_t *out, size_t count, hipStream_t stream);
 
-// this zero-fills
-// the pad row of a feature matrix: rows [n, n+1) of an (n+1) x width buffer.
 // *yes = kernels on b run beside kernels on a (the two streams sit on different hardware queues); ~0.3 ms
 hipError_t streams_run_side_by_side(hipStream_t a, hipStream_t b, bool *yes);
+// zero-fills the pad row of a feature matrix: rows [n, n+1) of an (n+1) x width buffer
 hipError_t launch_zero_pad_row(float *buf, uint32_t n, uint32_t width, hipStream_t stream);
 
 }  // namespace gnnvc

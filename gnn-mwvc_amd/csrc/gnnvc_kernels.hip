@@ -4731,24 +4731,23 @@ int stage_variant(int f, int n1, int n2, int n3, int sigmoid_last) {
     return -1;
 }
 
-// a 16-wide stage from the L2-resident compact table (k_stage_t4); it leaves at once unless the table in place fits this input
 // a stage on wide tiles (k_stage_w1 / k_stage_w16: a workgroup per 64-vertex tile; small graphs without long rows)
-hipError_t launch_stage_wide(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                             float *logits, uint32_t row_lo, uint32_t row_hi, hipStream_t stream) {
-    if (row_hi <= row_lo) return hipSuccess;
-    const dim3 grid((row_hi - row_lo + kWave - 1) / kWave), block(kBlock);
-    const float *P = params + sp.param_offset;
+hipError_t launch_stage_wide(const StageCall &c) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const dim3 grid((c.row_hi - c.row_lo + kWave - 1) / kWave), block(kBlock);
+    const float *P = c.params + sp.param_offset;
     switch (sp.variant) {
     case 0:
-        GNNVC_LAUNCH((k_stage_w1<32, 32, 16>), grid, block, 0, stream, g, ws, in, out, P, row_lo, row_hi);
+        GNNVC_LAUNCH((k_stage_w1<32, 32, 16>), grid, block, 0, c.stream, *c.g, c.ws, c.in, c.out, P, c.row_lo, c.row_hi);
         break;
     case 1:
-        GNNVC_LAUNCH((k_stage_w16<32, 32, 16, false>), grid, block, 0, stream, g, ws, reinterpret_cast<const float4 *>(in), out,
-                     (float *)nullptr, P, row_lo, row_hi);
+        GNNVC_LAUNCH((k_stage_w16<32, 32, 16, false>), grid, block, 0, c.stream, *c.g, c.ws, reinterpret_cast<const float4 *>(c.in), c.out,
+                     (float *)nullptr, P, c.row_lo, c.row_hi);
         break;
     case 2:
-        GNNVC_LAUNCH((k_stage_w16<32, 16, 1, true>), grid, block, 0, stream, g, ws, reinterpret_cast<const float4 *>(in), out, logits, P,
-                     row_lo, row_hi);
+        GNNVC_LAUNCH((k_stage_w16<32, 16, 1, true>), grid, block, 0, c.stream, *c.g, c.ws, reinterpret_cast<const float4 *>(c.in), c.out,
+                     c.logits, P, c.row_lo, c.row_hi);
         break;
     default:
         return hipErrorInvalidValue;
@@ -4759,75 +4758,71 @@ hipError_t launch_stage_wide(const StagePlan &sp, const GraphDev &g, float ws, c
 #ifndef GNNVC_T4_S
 #define GNNVC_T4_S 4   // neighbours' table rows in flight per vertex
 #endif
-hipError_t launch_stage_t4(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out, float *logits,
-                           uint32_t row_lo, uint32_t row_hi, bool interleave, hipStream_t stream, const float *table_in,
-                           const unsigned long long *counts_in, unsigned long long *counts_zero, const uint32_t *desc_in, uint32_t *desc_out,
-                           const EmitArgs &emit, bool solo) {
-    if (row_hi <= row_lo) return hipSuccess;
-    if (sp.f != 16 || (sp.variant != 1 && sp.variant != 2) || !table_in || !counts_in || !counts_zero || counts_zero == counts_in || !desc_in ||
-        !desc_out || desc_in == desc_out)
+// a 16-wide stage from the L2-resident compact table (k_stage_t4); it leaves at once unless the table in place fits this input
+hipError_t launch_stage_t4(const StageCall &c, const TableTileArgs &a) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    if (sp.f != 16 || (sp.variant != 1 && sp.variant != 2) || !a.table_in || !a.counts_in || !a.counts_zero || a.counts_zero == a.counts_in ||
+        !a.desc_in || !a.desc_out || a.desc_in == a.desc_out)
         return hipErrorInvalidValue;
-    const uint32_t ntiles = (row_hi - row_lo + kWave - 1) / kWave;
+    const uint32_t ntiles = (c.row_hi - c.row_lo + kWave - 1) / kWave;
     const uint32_t per_xcd = (ntiles + 7) / 8;
     const uint32_t blocks_per_xcd = (per_xcd + kWavesPerBlock - 1) / kWavesPerBlock;
     const dim3 grid(blocks_per_xcd * 8 + 1), block(kBlock);   // (+ 1: the workgroup that chooses)
-    const float *P = params + sp.param_offset;
-    const float4 *in4 = reinterpret_cast<const float4 *>(in), *tab = reinterpret_cast<const float4 *>(table_in);
+    const float *P = c.params + sp.param_offset;
+    const float4 *in4 = reinterpret_cast<const float4 *>(c.in), *tab = reinterpret_cast<const float4 *>(a.table_in);
     if (sp.variant == 1)
-        GNNVC_LAUNCH((k_stage_t4<32, 32, 16, false, GNNVC_T4_S>), grid, block, 0, stream, g, ws, in4, out, (float *)nullptr, P, row_lo, row_hi,
-                     interleave ? 1 : 0, tab, counts_in, counts_zero, desc_in, desc_out, emit.spec, reinterpret_cast<c4row *>(emit.table),
-                     emit.counts, solo ? 1 : 0);
+        GNNVC_LAUNCH((k_stage_t4<32, 32, 16, false, GNNVC_T4_S>), grid, block, 0, c.stream, *c.g, c.ws, in4, c.out, (float *)nullptr, P,
+                     c.row_lo, c.row_hi, a.interleave ? 1 : 0, tab, a.counts_in, a.counts_zero, a.desc_in, a.desc_out, a.emit.spec,
+                     reinterpret_cast<c4row *>(a.emit.table), a.emit.counts, a.solo ? 1 : 0);
     else
-        GNNVC_LAUNCH((k_stage_t4<32, 16, 1, true, GNNVC_T4_S>), grid, block, 0, stream, g, ws, in4, out, logits, P, row_lo, row_hi,
-                     interleave ? 1 : 0, tab, counts_in, counts_zero, desc_in, desc_out, (const uint32_t *)nullptr, (c4row *)nullptr,
-                     (unsigned long long *)nullptr, solo ? 1 : 0);
+        GNNVC_LAUNCH((k_stage_t4<32, 16, 1, true, GNNVC_T4_S>), grid, block, 0, c.stream, *c.g, c.ws, in4, c.out, c.logits, P,
+                     c.row_lo, c.row_hi, a.interleave ? 1 : 0, tab, a.counts_in, a.counts_zero, a.desc_in, a.desc_out,
+                     (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr, a.solo ? 1 : 0);
     return hipGetLastError();
 }
 
 // the dense layers + sigmoid of the last stage when its aggregates are ready (compact-table plan): rows [row_lo, row_hi)
-hipError_t launch_dense_sigmoid(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                                float *logits, uint32_t row_lo, uint32_t row_hi, const float *acc4, const uint32_t *c4desc,
-                                const float *agg16, hipStream_t stream, uint32_t long_thresh, const float *table_in) {
-    if (row_hi <= row_lo) return hipSuccess;
-    if (sp.f != 16 || sp.variant != 2 || !acc4 || !c4desc) return hipErrorInvalidValue;
-    const dim3 grid((row_hi - row_lo + kBlock - 1) / kBlock), block(kBlock);
-    GNNVC_LAUNCH((k_dense_f16<32, 16, 1, true>), grid, block, 0, stream, g, ws, reinterpret_cast<const float4 *>(in), out, logits,
-                       params + sp.param_offset, row_lo, row_hi, reinterpret_cast<const float4 *>(acc4), c4desc,
-                       reinterpret_cast<const float4 *>(agg16), reinterpret_cast<const float4 *>(table_in), long_thresh,
+hipError_t launch_dense_sigmoid(const StageCall &c, const CompactSums &s, uint32_t long_thresh) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    if (c.sp->f != 16 || c.sp->variant != 2 || !s.acc4 || !s.c4desc) return hipErrorInvalidValue;
+    const dim3 grid((c.row_hi - c.row_lo + kBlock - 1) / kBlock), block(kBlock);
+    GNNVC_LAUNCH((k_dense_f16<32, 16, 1, true>), grid, block, 0, c.stream, *c.g, c.ws, reinterpret_cast<const float4 *>(c.in), c.out,
+                       c.logits, c.params + c.sp->param_offset, c.row_lo, c.row_hi, reinterpret_cast<const float4 *>(s.acc4), s.c4desc,
+                       reinterpret_cast<const float4 *>(s.agg16), reinterpret_cast<const float4 *>(s.table_in), long_thresh,
                        (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params,
-                        const float *in, float *out, float *logits, uint32_t row_lo,
-                        uint32_t row_hi, uint32_t long_thresh, bool mfma, const SortedOrder *so,
-                        bool interleave, hipStream_t stream, const float *acc4, const uint32_t *c4desc, const float *agg16,
-                        bool mfma_agg, const EmitArgs &emit, bool dense_part, const SortedOrder *so_pruned, const float *table_in,
-                        const uint32_t *skip_flag) {
-    if (row_hi <= row_lo) return hipSuccess;
+hipError_t launch_stage(const StageCall &c, const TileArgs &a) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
+    const SortedOrder *so = a.so, *so_pruned = a.so_pruned;
+    const CompactSums &s = a.sums;
     const bool sorted = so && so->n > 0;
     const bool with_p = sorted && g.prune_eff && so_pruned && so_pruned->vertex;
     if (g.prune_eff && sorted && !with_p) return hipErrorInvalidValue;   // (classing by entries left needs the matching tile order)
     if (so && so->n == 0 && !with_p) return hipSuccess;   // every row of the range is a long row
     const uint32_t n_p = with_p ? so_pruned->n : 0u;
-    const uint32_t ntiles = sorted ? (std::max(so->n, n_p) + kWave - 1) / kWave : (row_hi - row_lo + kWave - 1) / kWave;
+    const uint32_t ntiles = sorted ? (std::max(so->n, n_p) + kWave - 1) / kWave : (c.row_hi - c.row_lo + kWave - 1) / kWave;
     const uint32_t per_xcd = (ntiles + 7) / 8;
     const uint32_t blocks_per_xcd = (per_xcd + kWavesPerBlock - 1) / kWavesPerBlock;
     const dim3 grid(blocks_per_xcd * 8), block(kBlock);
-    const float *P = params + sp.param_offset;
-    const float4 *in4 = reinterpret_cast<const float4 *>(in);
+    const float *P = c.params + sp.param_offset;
+    const float4 *in4 = reinterpret_cast<const float4 *>(c.in);
     const float *nofloat = nullptr;
-    const int il = interleave ? 1 : 0;
-    switch (sp.variant * 2 + (mfma ? 1 : 0)) {
+    const int il = a.interleave ? 1 : 0;
+    switch (sp.variant * 2 + (a.mfma ? 1 : 0)) {
     case 0:
-        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, stream, g, ws, in, out, P,
-                           row_lo, row_hi, g.rowptr, g.col, nofloat, long_thresh, il, (const uint32_t *)nullptr,
-                           emit.spec, reinterpret_cast<c4row *>(emit.table), emit.counts, sorted ? so->vertex : nullptr,
+        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, P,
+                           c.row_lo, c.row_hi, g.rowptr, g.col, nofloat, a.long_thresh, il, (const uint32_t *)nullptr,
+                           a.emit.spec, reinterpret_cast<c4row *>(a.emit.table), a.emit.counts, sorted ? so->vertex : nullptr,
                            sorted ? reinterpret_cast<const uint4 *>(so->meta) : nullptr, sorted ? so->n : 0u);
         break;
     case 1:
-        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, stream, g, ws, in, out, P,
-                           row_lo, row_hi, g.rowptr, g.col, nofloat, long_thresh, il, (const uint32_t *)nullptr,
+        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, P,
+                           c.row_lo, c.row_hi, g.rowptr, g.col, nofloat, a.long_thresh, il, (const uint32_t *)nullptr,
                            (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr,
                            sorted ? so->vertex : nullptr, sorted ? reinterpret_cast<const uint4 *>(so->meta) : nullptr,
                            sorted ? so->n : 0u);
@@ -4843,12 +4838,12 @@ hipError_t launch_stage(const StagePlan &sp, const GraphDev &g, float ws, const 
 #define GNNVC_GATHER_S_SORTED 3
 #endif
 #define GNNVC_F16_ARGS(SIG_, MF_, LG_)                                                                              \
-                       grid, block, 0, stream, g, ws, in4, out,                                                           \
-                       LG_, P, row_lo, row_hi, long_thresh, sorted ? so->vertex : nullptr,                                \
-                       sorted ? so->meta : nullptr, sorted ? so->n : 0u, il,                                              \
-                       (const float4 *)nullptr, acc4 ? c4desc : skip_flag, (const float4 *)nullptr,                       \
-                       (MF_ || SIG_) ? nullptr : emit.spec, reinterpret_cast<c4row *>((MF_ || SIG_) ? nullptr : emit.table), \
-                       (MF_ || SIG_) ? nullptr : emit.counts,                                                             \
+                       grid, block, 0, c.stream, g, c.ws, in4, c.out,                                               \
+                       LG_, P, c.row_lo, c.row_hi, a.long_thresh, sorted ? so->vertex : nullptr,                    \
+                       sorted ? so->meta : nullptr, sorted ? so->n : 0u, il,                                        \
+                       (const float4 *)nullptr, s.acc4 ? s.c4desc : a.skip_flag, (const float4 *)nullptr,           \
+                       (MF_ || SIG_) ? nullptr : a.emit.spec, reinterpret_cast<c4row *>((MF_ || SIG_) ? nullptr : a.emit.table), \
+                       (MF_ || SIG_) ? nullptr : a.emit.counts,                                                     \
                        with_p ? so_pruned->vertex : nullptr, with_p ? so_pruned->meta : nullptr, n_p
 #define GNNVC_LAUNCH_X(...) GNNVC_LAUNCH(__VA_ARGS__)   // (the argument list above is expanded on the way through)
 #define GNNVC_LAUNCH_F16(N2_, N3_, SIG_, MF_, SRT_, S_, LG_) \
@@ -4867,15 +4862,15 @@ hipError_t launch_stage(const StagePlan &sp, const GraphDev &g, float ws, const 
         else GNNVC_LAUNCH_F16(32, 16, false, true, false, GNNVC_GATHER_S, nullptr);
         break;
     case 4:
-        if (sorted) GNNVC_LAUNCH_F16(16, 1, true, false, true, GNNVC_GATHER_S_SORTED, logits);
-        else GNNVC_LAUNCH_F16(16, 1, true, false, false, GNNVC_GATHER_S, logits);
+        if (sorted) GNNVC_LAUNCH_F16(16, 1, true, false, true, GNNVC_GATHER_S_SORTED, c.logits);
+        else GNNVC_LAUNCH_F16(16, 1, true, false, false, GNNVC_GATHER_S, c.logits);
         break;
     case 5:
         if (g.zero_bits) {
-            if (sorted) GNNVC_LAUNCH_F16F(16, 1, true, true, true, GNNVC_GATHER_S_SORTED, logits, true);
-            else GNNVC_LAUNCH_F16F(16, 1, true, true, false, GNNVC_GATHER_S, logits, true);
-        } else if (sorted) GNNVC_LAUNCH_F16(16, 1, true, true, true, GNNVC_GATHER_S_SORTED, logits);
-        else GNNVC_LAUNCH_F16(16, 1, true, true, false, GNNVC_GATHER_S, logits);
+            if (sorted) GNNVC_LAUNCH_F16F(16, 1, true, true, true, GNNVC_GATHER_S_SORTED, c.logits, true);
+            else GNNVC_LAUNCH_F16F(16, 1, true, true, false, GNNVC_GATHER_S, c.logits, true);
+        } else if (sorted) GNNVC_LAUNCH_F16(16, 1, true, true, true, GNNVC_GATHER_S_SORTED, c.logits);
+        else GNNVC_LAUNCH_F16(16, 1, true, true, false, GNNVC_GATHER_S, c.logits);
         break;
 #undef GNNVC_LAUNCH_F16
 #undef GNNVC_LAUNCH_F16F
@@ -4884,33 +4879,33 @@ hipError_t launch_stage(const StagePlan &sp, const GraphDev &g, float ws, const 
     default:
         return hipErrorInvalidValue;
     }
-    if (acc4 && sp.f == 16 && dense_part) {
+    if (s.acc4 && sp.f == 16 && a.dense_part) {
         // compact-table plan: the aggregate-only variant does the launch when the device found the input fit for
         // it (the gathering variant above has then left at once, and the other way round).  Without gathers to
         // overlap with, the dense layers run faster on the VALU (one lane per vertex, weights from SGPRs) than on
         // the fp32 matrix cores: 6.65 vs 7.16 ms per forward on the metric graph.  It always walks natural tiles
         // (nothing to balance without a gather, and consecutive rows read their sums coalesced).
-        const uint32_t nt = (row_hi - row_lo + kWave - 1) / kWave;
+        const uint32_t nt = (c.row_hi - c.row_lo + kWave - 1) / kWave;
         const dim3 grid((((nt + 7) / 8 + kWavesPerBlock - 1) / kWavesPerBlock) * 8);
 #define GNNVC_LAUNCH_AGG(N2_, N3_, SIG_, MF_, LG_)                                                        \
-        GNNVC_LAUNCH((k_stage_f16<32, N2_, N3_, SIG_, 2, MF_, false, true>), grid, block, 0, stream, g, ws, in4, \
-                           out, LG_, P, row_lo, row_hi, long_thresh, (const uint32_t *)nullptr, (const uint4 *)nullptr, \
-                           0u, il, reinterpret_cast<const float4 *>(acc4), c4desc, reinterpret_cast<const float4 *>(agg16), \
-                           (MF_ || SIG_) ? nullptr : emit.spec, reinterpret_cast<c4row *>((MF_ || SIG_) ? nullptr : emit.table), \
-                           (MF_ || SIG_) ? nullptr : emit.counts)
+        GNNVC_LAUNCH((k_stage_f16<32, N2_, N3_, SIG_, 2, MF_, false, true>), grid, block, 0, c.stream, g, c.ws, in4, \
+                           c.out, LG_, P, c.row_lo, c.row_hi, a.long_thresh, (const uint32_t *)nullptr, (const uint4 *)nullptr, \
+                           0u, il, reinterpret_cast<const float4 *>(s.acc4), s.c4desc, reinterpret_cast<const float4 *>(s.agg16), \
+                           (MF_ || SIG_) ? nullptr : a.emit.spec, reinterpret_cast<c4row *>((MF_ || SIG_) ? nullptr : a.emit.table), \
+                           (MF_ || SIG_) ? nullptr : a.emit.counts)
         if (sp.variant == 1) {
-            if (mfma_agg) {
+            if (a.mfma_agg) {
                 GNNVC_LAUNCH_AGG(32, 16, false, true, nullptr);
             } else {   // (round 4: one lane per row, the terms that are zero left out — k_dense_f16)
-                const dim3 dgrid((row_hi - row_lo + kBlock - 1) / kBlock);
-                GNNVC_LAUNCH((k_dense_f16<32, 32, 16, false>), dgrid, block, 0, stream, g, ws, in4, out, (float *)nullptr, P, row_lo, row_hi,
-                                   reinterpret_cast<const float4 *>(acc4), c4desc, reinterpret_cast<const float4 *>(agg16),
-                                   reinterpret_cast<const float4 *>(table_in), long_thresh, emit.spec,
-                                   reinterpret_cast<c4row *>(emit.table), emit.counts);
+                const dim3 dgrid((c.row_hi - c.row_lo + kBlock - 1) / kBlock);
+                GNNVC_LAUNCH((k_dense_f16<32, 32, 16, false>), dgrid, block, 0, c.stream, g, c.ws, in4, c.out, (float *)nullptr, P, c.row_lo, c.row_hi,
+                                   reinterpret_cast<const float4 *>(s.acc4), s.c4desc, reinterpret_cast<const float4 *>(s.agg16),
+                                   reinterpret_cast<const float4 *>(s.table_in), a.long_thresh, a.emit.spec,
+                                   reinterpret_cast<c4row *>(a.emit.table), a.emit.counts);
             }
         } else {
-            if (mfma_agg) GNNVC_LAUNCH_AGG(16, 1, true, true, logits);
-            else return launch_dense_sigmoid(sp, g, ws, params, in, out, logits, row_lo, row_hi, acc4, c4desc, agg16, stream, long_thresh, table_in);
+            if (a.mfma_agg) GNNVC_LAUNCH_AGG(16, 1, true, true, c.logits);
+            else return launch_dense_sigmoid(c, s, a.long_thresh);
         }
 #undef GNNVC_LAUNCH_AGG
     }
@@ -4965,9 +4960,10 @@ hipError_t write_verdicts(const VerdictWords &vw, uint32_t *out_dev, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_audit_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                              float *logits, uint32_t row_lo, uint32_t row_hi, unsigned long long *rec, bool repair, hipStream_t stream) {
-    if (row_hi <= row_lo) return hipSuccess;
+hipError_t launch_audit_stage(const StageCall &c, unsigned long long *rec, bool repair) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
     // the graph as handed over and nothing else: no plan's view can reach the audit
     GraphDev plain;
     plain.n = g.n;
@@ -4979,18 +4975,18 @@ hipError_t launch_audit_stage(const StagePlan &sp, const GraphDev &g, float ws, 
     plain.row_base = g.row_base;
     plain.row_end = g.row_end;
     // a persistent grid: each block transposes the parameters into its LDS once, then walks 16 rows at a time
-    const dim3 grid(std::min<unsigned>(blocks_for((size_t)(row_hi - row_lo), 16), 2048u)), block(kBlock);
-    const float *P = params + sp.param_offset;
+    const dim3 grid(std::min<unsigned>(blocks_for((size_t)(c.row_hi - c.row_lo), 16), 2048u)), block(kBlock);
+    const float *P = c.params + sp.param_offset;
     const int rp = repair ? 1 : 0;
     switch (sp.variant) {
     case 0:
-        GNNVC_LAUNCH((k_audit_stage<1, 32, 16, false>), grid, block, 0, stream, plain, ws, P, in, out, logits, row_lo, row_hi, rec, rp);
+        GNNVC_LAUNCH((k_audit_stage<1, 32, 16, false>), grid, block, 0, c.stream, plain, c.ws, P, c.in, c.out, c.logits, c.row_lo, c.row_hi, rec, rp);
         break;
     case 1:
-        GNNVC_LAUNCH((k_audit_stage<16, 32, 16, false>), grid, block, 0, stream, plain, ws, P, in, out, logits, row_lo, row_hi, rec, rp);
+        GNNVC_LAUNCH((k_audit_stage<16, 32, 16, false>), grid, block, 0, c.stream, plain, c.ws, P, c.in, c.out, c.logits, c.row_lo, c.row_hi, rec, rp);
         break;
     case 2:
-        GNNVC_LAUNCH((k_audit_stage<16, 16, 1, true>), grid, block, 0, stream, plain, ws, P, in, out, logits, row_lo, row_hi, rec, rp);
+        GNNVC_LAUNCH((k_audit_stage<16, 16, 1, true>), grid, block, 0, c.stream, plain, c.ws, P, c.in, c.out, c.logits, c.row_lo, c.row_hi, rec, rp);
         break;
     default:
         return hipErrorInvalidValue;
@@ -5104,31 +5100,30 @@ hipError_t build_blocked_index(const GraphDev &g, uint32_t wb, uint32_t nblocks,
     return hipGetLastError();
 }
 
-hipError_t launch_stage0_blocked(const StagePlan &sp, const GraphDev &g, float ws, const float *params,
-                                 const float *x, float *out, uint32_t row_lo, uint32_t row_hi,
-                                 uint32_t nblocks, const uint32_t *bp, const uint32_t *colb, float *acc,
-                                 uint32_t long_thresh, bool mfma, bool interleave, hipStream_t stream, const EmitArgs &emit) {
-    if (row_hi <= row_lo) return hipSuccess;
+hipError_t launch_stage0_blocked(const StageCall &c, const BlockedPlan &bp, const Stage0Args &a) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
     if (sp.variant != 0) return hipErrorInvalidValue;
-    const unsigned nb = (row_hi - row_lo + 255) / 256;
-    for (uint32_t k = 0; k + 1 < nblocks; ++k)
-        GNNVC_LAUNCH(k_blk_accumulate, dim3(nb), dim3(256), 0, stream, bp + (size_t)k * g.n, colb, x,
-                           acc, row_lo, row_hi, k == 0 ? 1 : 0);
-    const uint32_t ntiles = (row_hi - row_lo + kWave - 1) / kWave;
+    const unsigned nb = (c.row_hi - c.row_lo + 255) / 256;
+    for (uint32_t k = 0; k + 1 < bp.nblocks; ++k)
+        GNNVC_LAUNCH(k_blk_accumulate, dim3(nb), dim3(256), 0, c.stream, bp.bp + (size_t)k * g.n, bp.colb, c.in,
+                           bp.acc, c.row_lo, c.row_hi, k == 0 ? 1 : 0);
+    const uint32_t ntiles = (c.row_hi - c.row_lo + kWave - 1) / kWave;
     const uint32_t per_xcd = (ntiles + 7) / 8;
     const uint32_t blocks_per_xcd = (per_xcd + kWavesPerBlock - 1) / kWavesPerBlock;
-    const uint32_t *ep = bp + (size_t)(nblocks - 1) * g.n;
-    const float *acc_in = nblocks > 1 ? acc : nullptr;
+    const uint32_t *ep = bp.bp + (size_t)(bp.nblocks - 1) * g.n;
+    const float *acc_in = bp.nblocks > 1 ? bp.acc : nullptr;
     const dim3 grid(blocks_per_xcd * 8), block(kBlock);
-    if (mfma)
-        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, stream, g, ws, x, out,
-                           params + sp.param_offset, row_lo, row_hi, ep, colb, acc_in, long_thresh, interleave ? 1 : 0,
+    if (a.mfma)
+        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, c.stream, g, c.ws, c.in, c.out,
+                           c.params + sp.param_offset, c.row_lo, c.row_hi, ep, bp.colb, acc_in, a.long_thresh, a.interleave ? 1 : 0,
                            (const uint32_t *)nullptr, (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr,
                            (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
     else
-        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, stream, g, ws, x, out,
-                           params + sp.param_offset, row_lo, row_hi, ep, colb, acc_in, long_thresh, interleave ? 1 : 0,
-                           (const uint32_t *)nullptr, emit.spec, reinterpret_cast<c4row *>(emit.table), emit.counts,
+        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, c.stream, g, c.ws, c.in, c.out,
+                           c.params + sp.param_offset, c.row_lo, c.row_hi, ep, bp.colb, acc_in, a.long_thresh, a.interleave ? 1 : 0,
+                           (const uint32_t *)nullptr, a.emit.spec, reinterpret_cast<c4row *>(a.emit.table), a.emit.counts,
                            (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
     return hipGetLastError();
 }
@@ -5314,56 +5309,55 @@ hipError_t mass_bounds(const GraphDev &g, unsigned long long target, uint32_t co
     return hipGetLastError();
 }
 
-hipError_t launch_stage0_lds_table(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *x,
-                                   float *out, uint32_t row_lo, uint32_t row_hi, uint32_t rows_per_chunk,
-                                   const uint32_t *step_ptr, const void *steps, const uint32_t *entries, uint8_t *wbyte,
-                                   float *acc, uint32_t *bad, uint32_t long_thresh, bool mfma, bool interleave,
-                                   hipStream_t stream, const EmitArgs &emit, uint32_t last_entry, const uint32_t *rowmap,
-                                   uint32_t mapped_chunks, uint32_t plan_base, uint32_t plan_end, uint32_t bits) {
-    if (row_hi <= row_lo) return hipSuccess;
-    if (bits != 8 && bits != 10 && bits != 16) return hipErrorInvalidValue;
-    if (rowmap && bits != 8) return hipErrorInvalidValue;   // (the skewed layout's block starts are multiples of 256 columns, not of a 10-bit piece)
-    if (plan_end > g.n) plan_end = g.n;
-    if (row_lo < plan_base || row_hi > plan_end) return hipErrorInvalidValue;
-    if (rowmap && (row_lo != 0 || row_hi != g.n || mapped_chunks == 0)) return hipErrorInvalidValue;   // (a mapped plan sums all of its rows)
-    if (sp.variant != 0 || rows_per_chunk == 0 || rows_per_chunk > 16u * lt_slice_rows_max(bits) || rows_per_chunk % 16u || g.nnz == 0)
+hipError_t launch_stage0_lds_table(const StageCall &c, const LdsTablePlan &lp, uint8_t *wbyte, float *acc, uint32_t *bad,
+                                   const Stage0Args &a) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
+    if (lp.bits != 8 && lp.bits != 10 && lp.bits != 16) return hipErrorInvalidValue;
+    if (lp.rowmap && lp.bits != 8) return hipErrorInvalidValue;   // (the skewed layout's block starts are multiples of 256 columns, not of a 10-bit piece)
+    const uint32_t plan_end = std::min(lp.plan_end, g.n);
+    if (c.row_lo < lp.plan_base || c.row_hi > plan_end) return hipErrorInvalidValue;
+    if (lp.rowmap && (c.row_lo != 0 || c.row_hi != g.n || lp.mapped_chunks == 0)) return hipErrorInvalidValue;   // (a mapped plan sums all of its rows)
+    if (sp.variant != 0 || lp.rows_per_chunk == 0 || lp.rows_per_chunk > 16u * lt_slice_rows_max(lp.bits) || lp.rows_per_chunk % 16u || g.nnz == 0)
         return hipErrorInvalidValue;
     // does this forward's input match the table?  decided on the device: no host round trip
-    hipError_t rc = hipMemsetAsync(bad, 0, sizeof(uint32_t), stream);
+    hipError_t rc = hipMemsetAsync(bad, 0, sizeof(uint32_t), c.stream);
     if (rc != hipSuccess) return rc;
     const dim3 tgrid(std::min<unsigned>((g.n / 4 + 255) / 256 + 1, 4096u));
-    const uint32_t c0 = rowmap ? 0u : (row_lo - plan_base) / rows_per_chunk, c1 = rowmap ? mapped_chunks - 1 : (row_hi - 1 - plan_base) / rows_per_chunk;
-    const uint32_t slice_rows = rows_per_chunk / 16u;
+    const uint32_t c0 = lp.rowmap ? 0u : (c.row_lo - lp.plan_base) / lp.rows_per_chunk;
+    const uint32_t c1 = lp.rowmap ? lp.mapped_chunks - 1 : (c.row_hi - 1 - lp.plan_base) / lp.rows_per_chunk;
+    const uint32_t slice_rows = lp.rows_per_chunk / 16u;
     constexpr size_t lds_max = (size_t)16 * kLtwSliceRows * 4 + 1024 + kLtwBlock;
     static_assert(lds_max <= 160 * 1024, "LDS budget of k_lt_agg");
-    const size_t lds = (size_t)16 * slice_rows * 4 + lt_lut_floats(bits) * 4 + kLtwBlock;
+    const size_t lds = (size_t)16 * slice_rows * 4 + lt_lut_floats(lp.bits) * 4 + kLtwBlock;
 #define GNNVC_LT_AGG(B_)                                                                                                          \
     {                                                                                                                             \
-        GNNVC_LAUNCH(k_lt_bytes_x<B_>, tgrid, dim3(256), 0, stream, x, ws, g.n, wbyte, bad);                                      \
+        GNNVC_LAUNCH(k_lt_bytes_x<B_>, tgrid, dim3(256), 0, c.stream, c.in, c.ws, g.n, wbyte, bad);                               \
         static std::atomic<uint64_t> lds_ok{0};                                                                                   \
         rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_lt_agg<B_>), (int)lds_max, lds_ok);                               \
         if (rc != hipSuccess) return rc;                                                                                          \
-        GNNVC_LAUNCH(k_lt_agg<B_>, dim3(c1 - c0 + 1), dim3(1024), lds, stream, step_ptr, reinterpret_cast<const uint32_t *>(steps), \
-                     entries, wbyte, ws, acc, g.n, slice_rows, c0, last_entry, bad, rowmap, rowmap ? 0u : plan_base,               \
-                     rowmap ? g.n : plan_end);                                                                                    \
+        GNNVC_LAUNCH(k_lt_agg<B_>, dim3(c1 - c0 + 1), dim3(1024), lds, c.stream, lp.step_ptr,                                     \
+                     reinterpret_cast<const uint32_t *>(lp.steps), lp.entries, wbyte, c.ws, acc, g.n, slice_rows, c0, lp.last_entry, bad, \
+                     lp.rowmap, lp.rowmap ? 0u : lp.plan_base, lp.rowmap ? g.n : plan_end);                                       \
     }
-    if (bits == 8) GNNVC_LT_AGG(8)
-    else if (bits == 10) GNNVC_LT_AGG(10)
+    if (lp.bits == 8) GNNVC_LT_AGG(8)
+    else if (lp.bits == 10) GNNVC_LT_AGG(10)
     else GNNVC_LT_AGG(16)
 #undef GNNVC_LT_AGG
-    const uint32_t ntiles = (row_hi - row_lo + kWave - 1) / kWave;
+    const uint32_t ntiles = (c.row_hi - c.row_lo + kWave - 1) / kWave;
     const uint32_t per_xcd = (ntiles + 7) / 8;
     const uint32_t blocks_per_xcd = (per_xcd + kWavesPerBlock - 1) / kWavesPerBlock;
     const dim3 grid(blocks_per_xcd * 8), block(kBlock);
-    if (mfma)
-        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, stream, g, ws, x, out, params + sp.param_offset,
-                           row_lo, row_hi, g.rowptr, g.col, acc, long_thresh, interleave ? 1 : 0, (const uint32_t *)bad,
+    if (a.mfma)
+        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.params + sp.param_offset,
+                           c.row_lo, c.row_hi, g.rowptr, g.col, acc, a.long_thresh, a.interleave ? 1 : 0, (const uint32_t *)bad,
                            (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr,
                            (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
     else
-        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, stream, g, ws, x, out, params + sp.param_offset,
-                           row_lo, row_hi, g.rowptr, g.col, acc, long_thresh, interleave ? 1 : 0, (const uint32_t *)bad,
-                           emit.spec, reinterpret_cast<c4row *>(emit.table), emit.counts,
+        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.params + sp.param_offset,
+                           c.row_lo, c.row_hi, g.rowptr, g.col, acc, a.long_thresh, a.interleave ? 1 : 0, (const uint32_t *)bad,
+                           a.emit.spec, reinterpret_cast<c4row *>(a.emit.table), a.emit.counts,
                            (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
     return hipGetLastError();
 }
@@ -5374,7 +5368,6 @@ uint32_t compact_block() { return kC4Block; }
 uint32_t compact_shift() { return kC4Shift; }
 uint32_t compact_slices() { return kC4Slices; }
 uint32_t compact_step() { return kC4Step; }
-uint32_t compact_max_passes() { return kC4MaxPasses; }
 
 // counts -> desc -> table(s) -> four sums per pass and row of [row_lo, row_hi) (chunks that straddle the ends are done
 // whole; a mapped plan always does all of its rows).  `counts` holds the per-column non-zero counts of `in`
@@ -5538,43 +5531,43 @@ hipError_t find_giant_rows(const GraphDev &g, const uint32_t *list, uint32_t n_l
 uint32_t giant_window() { return kGiantWin; }
 uint32_t giant_block() { return kGiantBlk; }
 
-hipError_t launch_giant_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                              float *logits, uint32_t row_lo, uint32_t row_hi, const GiantRows &gr, hipStream_t stream, uint32_t min_deg,
-                              int part) {
-    // part: 0 = everything on `stream`, 1 = the gather only, 2 = everything behind the gather (the engine puts the gather — a
+hipError_t launch_giant_stage(const StageCall &c, const GiantRows &gr, uint32_t min_deg, GiantPart part) {
+    // part: kAll = everything on c.stream, kGather = the gather only, kAfterGather = everything behind it (the engine puts the gather — a
     // throughput kernel, 0.03 ms alone — on the main queue AHEAD of the tile kernel and the walk on the side queue: queued
     // beside the tile kernel it waited 0.2 - 0.3 ms for free slots at the head of the chain a stage waits for)
-    if (gr.n == 0 || row_hi <= row_lo) return hipSuccess;
+    if (gr.n == 0 || c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
     const uint4 *meta = reinterpret_cast<const uint4 *>(gr.meta);
     const uint32_t F = sp.f == 16 ? 16u : 1u;
     const uint32_t *pr = sp.f == 16 ? g.prp : nullptr, *pb = sp.f == 16 ? g.prune_bad : nullptr;   // (pruned adjacency: 16-wide stages only)
     if (sp.f != 16 && sp.f != 1) return hipErrorInvalidValue;
-    if (part != 2) {
+    if (part != GiantPart::kAfterGather) {
         if (sp.f == 16)
-            GNNVC_LAUNCH(k_giant_gather16, dim3(gr.blocks), dim3(256), 0, stream, g, reinterpret_cast<const float4 *>(in), gr.slab,
-                               meta, gr.off, gr.n, row_lo, row_hi, min_deg);
+            GNNVC_LAUNCH(k_giant_gather16, dim3(gr.blocks), dim3(256), 0, c.stream, g, reinterpret_cast<const float4 *>(c.in), gr.slab,
+                               meta, gr.off, gr.n, c.row_lo, c.row_hi, min_deg);
         else
-            GNNVC_LAUNCH(k_giant_gather1, dim3(gr.blocks), dim3(256), 0, stream, g, in, gr.slab, meta, gr.off, gr.n, row_lo, row_hi);
-        if (part == 1) return hipGetLastError();
+            GNNVC_LAUNCH(k_giant_gather1, dim3(gr.blocks), dim3(256), 0, c.stream, g, c.in, gr.slab, meta, gr.off, gr.n, c.row_lo, c.row_hi);
+        if (part == GiantPart::kGather) return hipGetLastError();
     }
     {
         const bool seg = gr.segsum && gr.segmap && gr.maxseg > 1;   // one stream on several waves (see k_giant_segmap)
         if (seg) {
             const dim3 sgrid(gr.n * F * giant_seg_blocks(gr.maxseg)), sblock(64 * kGiantSegWaves);
-            GNNVC_LAUNCH(k_giant_segsum, sgrid, sblock, 0, stream, gr.slab, meta, gr.off, F, gr.maxseg, gr.segsum,
-                         row_lo, row_hi, pr, pb, min_deg);
-            GNNVC_LAUNCH(k_giant_segmap, sgrid, sblock, 0, stream, gr.slab, meta, gr.off, F, gr.maxseg, gr.segsum,
-                         reinterpret_cast<uint4 *>(gr.segmap), row_lo, row_hi, pr, pb, min_deg);
+            GNNVC_LAUNCH(k_giant_segsum, sgrid, sblock, 0, c.stream, gr.slab, meta, gr.off, F, gr.maxseg, gr.segsum,
+                         c.row_lo, c.row_hi, pr, pb, min_deg);
+            GNNVC_LAUNCH(k_giant_segmap, sgrid, sblock, 0, c.stream, gr.slab, meta, gr.off, F, gr.maxseg, gr.segsum,
+                         reinterpret_cast<uint4 *>(gr.segmap), c.row_lo, c.row_hi, pr, pb, min_deg);
         }
-        GNNVC_LAUNCH(k_giant_sum, dim3(gr.n * F), dim3(64), 0, stream, gr.slab, meta, gr.off, F, gr.agg, row_lo, row_hi, pr, pb,
+        GNNVC_LAUNCH(k_giant_sum, dim3(gr.n * F), dim3(64), 0, c.stream, gr.slab, meta, gr.off, F, gr.agg, c.row_lo, c.row_hi, pr, pb,
                      seg ? reinterpret_cast<const uint4 *>(gr.segmap) : nullptr, gr.maxseg, min_deg);
     }
-    const float *P = params + sp.param_offset;
+    const float *P = c.params + sp.param_offset;
     const dim3 grid(gr.n), block(64);
     switch (sp.variant) {
-    case 0: GNNVC_LAUNCH(k_giant_dense<0>, grid, block, 0, stream, g, ws, in, out, logits, P, meta, gr.n, gr.agg, row_lo, row_hi, min_deg); break;
-    case 1: GNNVC_LAUNCH(k_giant_dense<1>, grid, block, 0, stream, g, ws, in, out, logits, P, meta, gr.n, gr.agg, row_lo, row_hi, min_deg); break;
-    case 2: GNNVC_LAUNCH(k_giant_dense<2>, grid, block, 0, stream, g, ws, in, out, logits, P, meta, gr.n, gr.agg, row_lo, row_hi, min_deg); break;
+    case 0: GNNVC_LAUNCH(k_giant_dense<0>, grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.logits, P, meta, gr.n, gr.agg, c.row_lo, c.row_hi, min_deg); break;
+    case 1: GNNVC_LAUNCH(k_giant_dense<1>, grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.logits, P, meta, gr.n, gr.agg, c.row_lo, c.row_hi, min_deg); break;
+    case 2: GNNVC_LAUNCH(k_giant_dense<2>, grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.logits, P, meta, gr.n, gr.agg, c.row_lo, c.row_hi, min_deg); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -5609,34 +5602,34 @@ hipError_t stream_sums(const float *streams_dev, uint32_t streams, uint32_t len,
     return hipGetLastError();
 }
 
-hipError_t launch_long_stage(const StagePlan &sp, const GraphDev &g, float ws, const float *params,
-                             const float *in, float *out, float *logits, uint32_t row_lo, uint32_t row_hi,
-                             const uint32_t *list, uint32_t n_long, uint32_t min_deg, uint32_t max_deg, hipStream_t stream) {
-    if (n_long == 0 || row_hi <= row_lo) return hipSuccess;
-    const float *P = params + sp.param_offset;
-    const dim3 grid(n_long), block(256);
+hipError_t launch_long_stage(const StageCall &c, const LongRows &lr) {
+    if (lr.n == 0 || c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
+    const float *P = c.params + sp.param_offset;
+    const dim3 grid(lr.n), block(256);
     switch (sp.variant) {
     case 0:
-        GNNVC_LAUNCH((k_long_f1<32, 32, 16>), grid, block, 0, stream, g, ws, in, out, P, row_lo, row_hi, list,
-                           min_deg, max_deg);
+        GNNVC_LAUNCH((k_long_f1<32, 32, 16>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, P, c.row_lo, c.row_hi, lr.list,
+                           lr.min_deg, lr.max_deg);
         break;
     case 1:
         if (g.zero_bits && g.keep_col) {
-            GNNVC_LAUNCH(k_long_lists, grid, block, 0, stream, g, row_lo, row_hi, list, min_deg, max_deg);
-            GNNVC_LAUNCH((k_long_f16<32, 32, 16, false, true>), grid, block, 0, stream, g, ws,
-                               reinterpret_cast<const float4 *>(in), out, nullptr, P, row_lo, row_hi, list, min_deg, max_deg);
+            GNNVC_LAUNCH(k_long_lists, grid, block, 0, c.stream, g, c.row_lo, c.row_hi, lr.list, lr.min_deg, lr.max_deg);
+            GNNVC_LAUNCH((k_long_f16<32, 32, 16, false, true>), grid, block, 0, c.stream, g, c.ws,
+                               reinterpret_cast<const float4 *>(c.in), c.out, nullptr, P, c.row_lo, c.row_hi, lr.list, lr.min_deg, lr.max_deg);
         } else
-            GNNVC_LAUNCH((k_long_f16<32, 32, 16, false>), grid, block, 0, stream, g, ws,
-                               reinterpret_cast<const float4 *>(in), out, nullptr, P, row_lo, row_hi, list, min_deg, max_deg);
+            GNNVC_LAUNCH((k_long_f16<32, 32, 16, false>), grid, block, 0, c.stream, g, c.ws,
+                               reinterpret_cast<const float4 *>(c.in), c.out, nullptr, P, c.row_lo, c.row_hi, lr.list, lr.min_deg, lr.max_deg);
         break;
     case 2:
         if (g.zero_bits && g.keep_col) {
-            GNNVC_LAUNCH(k_long_lists, grid, block, 0, stream, g, row_lo, row_hi, list, min_deg, max_deg);
-            GNNVC_LAUNCH((k_long_f16<32, 16, 1, true, true>), grid, block, 0, stream, g, ws,
-                               reinterpret_cast<const float4 *>(in), out, logits, P, row_lo, row_hi, list, min_deg, max_deg);
+            GNNVC_LAUNCH(k_long_lists, grid, block, 0, c.stream, g, c.row_lo, c.row_hi, lr.list, lr.min_deg, lr.max_deg);
+            GNNVC_LAUNCH((k_long_f16<32, 16, 1, true, true>), grid, block, 0, c.stream, g, c.ws,
+                               reinterpret_cast<const float4 *>(c.in), c.out, c.logits, P, c.row_lo, c.row_hi, lr.list, lr.min_deg, lr.max_deg);
         } else
-            GNNVC_LAUNCH((k_long_f16<32, 16, 1, true>), grid, block, 0, stream, g, ws,
-                               reinterpret_cast<const float4 *>(in), out, logits, P, row_lo, row_hi, list, min_deg, max_deg);
+            GNNVC_LAUNCH((k_long_f16<32, 16, 1, true>), grid, block, 0, c.stream, g, c.ws,
+                               reinterpret_cast<const float4 *>(c.in), c.out, c.logits, P, c.row_lo, c.row_hi, lr.list, lr.min_deg, lr.max_deg);
         break;
     default:
         return hipErrorInvalidValue;

@@ -831,6 +831,21 @@ gnnvc::CompactPlan compact_plan(const gnnvc_engine *e) {
     return cp;
 }
 
+gnnvc::LdsTablePlan lds_table_plan(const gnnvc_engine *e) {
+    gnnvc::LdsTablePlan lp;
+    lp.rows_per_chunk = e->lt_rows;
+    lp.step_ptr = e->lt_stepptr.p;
+    lp.steps = e->lt_steps.p;
+    lp.entries = e->lt_entries.p;
+    lp.last_entry = e->lt_last_entry;
+    lp.rowmap = e->lt_mapped ? e->lt_rowmap.p : nullptr;
+    lp.mapped_chunks = e->lt_mapped ? e->lt_chunks : 0u;
+    lp.plan_base = e->lt_base;
+    lp.plan_end = e->lt_end;
+    lp.bits = e->lt_bits;
+    return lp;
+}
+
 int build_blocked(gnnvc_engine *e) {
     return timed_build(e, [&] { return build_blocked_impl(e); }, e->opt_blocked && e->g.n >= e->opt_blocked_min_n && e->g.nnz != 0);
 }

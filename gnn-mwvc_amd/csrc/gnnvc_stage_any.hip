@@ -286,19 +286,20 @@ bool stage_any_fits(int f, int n1, int n2, int n3) {
     return f >= 1 && f <= 32 && n1 >= 1 && n1 <= 64 && n2 >= 1 && n2 <= 64 && n3 >= 1 && n3 <= 32;
 }
 
-hipError_t launch_stage_any(const StagePlan &sp, const GraphDev &g, float ws, const float *params, const float *in, float *out,
-                            float *logits, uint32_t row_lo, uint32_t row_hi, hipStream_t stream) {
-    if (row_hi <= row_lo) return hipSuccess;
-    if (!stage_any_fits(sp.f, sp.n1, sp.n2, sp.n3) || row_hi > g.hi() || row_lo < g.lo()) return hipErrorInvalidValue;
+hipError_t launch_stage_any(const StageCall &c) {
+    if (c.row_hi <= c.row_lo) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
+    if (!stage_any_fits(sp.f, sp.n1, sp.n2, sp.n3) || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
     const AnyGraph plain{g.rowptr, g.col, g.w, g.nw};
     const StageAnyLayout L = stage_any_layout(sp.f, sp.n1, sp.n2, sp.n3);
     const size_t lds = (size_t)L.total * sizeof(float);   // <= 53 KB at the largest widths
     // a persistent grid: as many workgroups as the LDS lets a CU hold (at most 8), on 256 CUs
     const unsigned per_cu = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (160u * 1024u) / (lds + 1024u)));
-    const unsigned need = (unsigned)(((size_t)(row_hi - row_lo) + kAnyRows - 1) / kAnyRows);
+    const unsigned need = (unsigned)(((size_t)(c.row_hi - c.row_lo) + kAnyRows - 1) / kAnyRows);
     const dim3 grid(std::min(need, 256u * per_cu)), block(kAnyBlock);
-    hipLaunchKernelGGL(k_stage_any, grid, block, lds, stream, plain, ws, params + sp.param_offset, in, out, sp.sigmoid_last ? logits : nullptr, row_lo, row_hi,
-                       sp.f, sp.n1, sp.n2, sp.n3, sp.sigmoid_last ? 1 : 0);
+    hipLaunchKernelGGL(k_stage_any, grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, c.out,
+                       sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, sp.f, sp.n1, sp.n2, sp.n3, sp.sigmoid_last ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -962,6 +962,42 @@ def test_compact_gather_plan_is_bit_identical(model_text, oracle_model, case):
         e.close()
 
 
+def test_compact_gather_dense_layers_from_full_rows(model_text, oracle_model):
+    """Option dense_skip_zeros = 0: the aggregate-only dense kernels of the compact-table plan are handed no table of their
+    own input and take every row's own values from the full rows (stage 1: k_dense_f16 behind the gathering kernel; stage 2:
+    the dense + sigmoid kernel of the rounds).  Same bits as the oracle, with strays that make table and full rows differ."""
+    import torch
+    import gnn_mwvc_amd as G
+    g = gg.erdos_renyi(20000, 200000, 70)
+    h = _sparse_features(g.n, np.random.default_rng(6), [0, 3, 7, 11], [1.0, 0.1, 0.5, 1.0], 25)
+    e = G.Engine(model_text, device=0)
+    try:
+        e.set_option("blocked_min_n", 0)
+        e.set_option("dense_skip_zeros", 0)
+        e.set_weight_scale(g.ws)
+        oracle_model.set_weight_scale(g.ws)
+        e.upload_graph(g)
+        e.forward(g.x())
+        _, logits = e.forward(g.x())                       # second forward: the plans are built
+        assert e.get_info("compact_gather_active") == 1
+        assert np.array_equal(bits(logits[:, 0]), bits(oracle_model.logits(g)))
+        dev = torch.device("cuda:0")
+        hin = torch.zeros((g.n + 1, 16), dtype=torch.float32, device=dev)
+        hin[: g.n] = torch.from_numpy(h).to(dev)
+        for stage in (1, 2):
+            out = torch.full((g.n + 1, 16 if stage == 1 else 1), 7.0, dtype=torch.float32, device=dev)
+            lg = torch.full((g.n + 1,), 7.0, dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()
+            e.stage_forward_device(stage, 0, g.n, hin.data_ptr(), out.data_ptr(), lg.data_ptr() if stage == 2 else 0)
+            e.synchronize()
+            assert e.get_info("compact_gather_last_ok") == 1 and e.get_info("compact_gather_last_dirty") > 0
+            want = _oracle_stage(oracle_model, g, stage, h)
+            got = out[: g.n].cpu().numpy() if stage == 1 else lg[: g.n].cpu().numpy().reshape(-1, 1)
+            assert np.array_equal(bits(got), bits(want)), stage
+    finally:
+        e.close()
+
+
 def test_compact_gather_long_runs(model_text, oracle_model):
     """k_c4_agg forced onto a skewed graph (three hubs of degree 4096, no long-row kernels): runs of thousands of
     entries of one row cross lanes, waves' steps and — with small chunks — sit alone in a one-row slice."""
