@@ -216,24 +216,24 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
     // An announcement (gnnvc_stage_input_ready) covers the calls for ITS stage that follow it.  A call for any other
     // stage means the caller has moved on — the next forward has begun, or the announced buffer is about to be
     // rewritten — and a call that writes into the announced buffer ends it too: the table must never outlive its input.
-    if (e->c4_prepared_stage != -1 && (stage != e->c4_prepared_stage || out == e->c4_prepared_in)) e->c4_prepared_stage = -1;
+    if (e->pg.c4_prepared_stage != -1 && (stage != e->pg.c4_prepared_stage || out == e->c4_prepared_in)) e->pg.c4_prepared_stage = -1;
     // Producer side of the compact-table plan: inside a whole forward (engine-owned feature buffers nobody else
     // writes) the stage kernel that produces the next 16-wide stage's input also counts its non-zeros and writes
     // its compact rows, so that stage can skip its two passes over the input.  Only the VALU variants emit.
     const int fused_in = in_forward ? e->c4_fused_for : -1;   // is THIS stage's input covered by the previous kernel?
     e->c4_fused_for = -1;
-    const bool may_emit = in_forward && e->c4_ready && !e->c4_range_mode && e->c4_base == 0 && e->c4_end == e->g.n && !longs &&
+    const bool may_emit = in_forward && e->pg.c4_ready && !e->pg.c4_range_mode && e->c4_base == 0 && e->c4_end == e->g.n && !longs &&
                           (size_t)stage + 1 < e->stages.size() && e->stages[stage + 1].f == 16 && lo == 0 && hi == e->g.n &&
-                          e->opt_mfma != 1 && !e->c4_stage_off[stage + 1];
+                          e->opt.mfma != 1 && !e->pg.c4_stage_off[stage + 1];
     c.long_thresh = (sp.f == 16) ? e->thresh_f16 : e->long_thresh;
-    c.mfma = e->opt_mfma == 1 || (e->opt_mfma == 2 && sp.f == 16);
+    c.mfma = e->opt.mfma == 1 || (e->opt.mfma == 2 && sp.f == 16);
     const bool t4 = in_forward && e->t4_now && lo == 0 && hi == e->g.n;   // table tiles: whole forwards on a graph that qualifies
     c.emit_t4 = t4 && (size_t)stage + 1 < e->stages.size();
     if (stage == 0) {
         // The LDS-table plan works in chunks of ~19.5 K rows, one workgroup each: a call that covers fewer than
         // three quarters of a GPU's worth of chunks (the pieces of a pipelined multi-GPU run) would leave most CUs
         // idle for the time one chunk takes — such calls use the column-blocked plan instead.
-        if (e->graph_uses >= 1 && !e->lt_tried) {
+        if (e->pg.graph_uses >= 1 && !e->pg.lt_tried) {
             int rc = build_lds_table(e);
             if (rc) return rc;
         }
@@ -241,17 +241,17 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
         // (consecutive-row layout: any call that covers at least three quarters of the chunks a full GPU takes — or of the plan's
         // own, where the plan is a rank's slice of fewer)
         const uint32_t lt_need = std::min(192u, e->lt_chunks - e->lt_chunks / 4u);
-        const bool lt_fits = e->lt_ready && !e->lt_off && hi > lo &&
+        const bool lt_fits = e->pg.lt_ready && !e->pg.lt_off && hi > lo &&
                              (e->lt_mapped ? (lo == 0 && hi == e->g.n)
                                            : (lo >= e->lt_base && hi <= e->lt_end &&
                                               ((hi - 1 - e->lt_base) / e->lt_rows - (lo - e->lt_base) / e->lt_rows + 1) >= lt_need));
-        if (e->graph_uses >= 1 && !lt_fits && !e->blocked_tried) {
+        if (e->pg.graph_uses >= 1 && !lt_fits && !e->pg.blocked_tried) {
             int rc = build_blocked(e);
             if (rc) return rc;
         }
-        ++e->graph_uses;
-        c.sums = lt_fits ? StageChoice::kLdsTable : (e->blocked_ready ? StageChoice::kBlocked : StageChoice::kGather);
-        if (lt_fits && in_forward) e->lt_used = true;
+        ++e->pg.graph_uses;
+        c.sums = lt_fits ? StageChoice::kLdsTable : (e->pg.blocked_ready ? StageChoice::kBlocked : StageChoice::kGather);
+        if (lt_fits && in_forward) e->pg.lt_used = true;
         if (lt_fits && e->lt_mapped) c.long_thresh = e->lt_plan_thresh;   // the plan holds every row below the giant ones
         c.emit = may_emit;
         if (c.sums != StageChoice::kGather) return GNNVC_OK;   // (those two bring their own tile order)
@@ -260,20 +260,20 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
     } else if (sp.f == 16) {
         // (the second forward on a graph builds the plan; a graph whose plain 16-wide stages cost well above the build — the
         // option's bound — builds it in its first, which is all a score-once caller ever runs)
-        const bool first_too = e->opt_compact_first_entries && e->g.nnz >= e->opt_compact_first_entries && lo == 0 && hi == e->g.n && in_forward;
-        if (!e->c4_range_mode && (e->graph_uses >= 2 || first_too) && !e->c4_tried) {
+        const bool first_too = e->opt.compact_first_entries && e->g.nnz >= e->opt.compact_first_entries && lo == 0 && hi == e->g.n && in_forward;
+        if (!e->pg.c4_range_mode && (e->pg.graph_uses >= 2 || first_too) && !e->pg.c4_tried) {
             int rc = build_compact(e);
             if (rc) return rc;
         }
-        const bool whole_plan = e->c4_ready && e->c4_base == 0 && e->c4_end == e->g.n && !e->c4_stage_off[stage];
-        const bool prepared = e->c4_ready && e->c4_prepared_stage == stage && e->c4_prepared_in == in &&
+        const bool whole_plan = e->pg.c4_ready && e->c4_base == 0 && e->c4_end == e->g.n && !e->pg.c4_stage_off[stage];
+        const bool prepared = e->pg.c4_ready && e->pg.c4_prepared_stage == stage && e->c4_prepared_in == in &&
                               lo >= e->c4_base && hi <= e->c4_end && hi > lo;
         if (prepared && !longs) {
             // gnnvc_stage_input_ready wrote the table for this input: any call that fills at least half the
             // GPU with chunks takes the sums from it (smaller ones would leave most CUs idle for a chunk's time)
             const uint32_t nchunks = (hi - 1 - e->c4_base) / e->c4_rows - (lo - e->c4_base) / e->c4_rows + 1;
             if (nchunks >= 128u) c.sums = StageChoice::kCompactPrepared;
-        } else if (!e->c4_range_mode && whole_plan && !longs && (uint64_t)(hi - lo) * 2 >= e->g.n) {
+        } else if (!e->pg.c4_range_mode && whole_plan && !longs && (uint64_t)(hi - lo) * 2 >= e->g.n) {
             // worth its fixed cost (count + compact the whole input) only when this call covers most of the rows
             c.sums = StageChoice::kCompactWhole;
             c.fused_counts = fused_in == stage;
@@ -282,7 +282,7 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
             // are launched one round (256 chunks) at a time and the dense kernel of round k goes to the aux stream,
             // under the sums of round k + 1.  Metric graph: 1.71 -> 1.58 ms.  (Not for the feature stages: their dense
             // kernels store 64-byte rows and slow the co-running sums by more than is gained.)
-            c.rounds = e->opt_overlap && sp.variant == 2 && e->opt_mfma != 1;
+            c.rounds = e->opt.overlap && sp.variant == 2 && e->opt.mfma != 1;
             c.emit = may_emit;   // this stage's own (aggregate-only, VALU) kernel produces for the next one
         }
     }
@@ -312,8 +312,8 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
     // always goes there; the long rows join it — unless that walk is what a stage waits for (find_giant: the power-law graph),
     // then they run ahead of the tile kernel on the main queue instead: power-law 1 M 0.89 ms (long rows beside the giant
     // walk: 1.15), R-MAT-22 2.62 ms (long rows on the main queue: 2.79).
-    const bool side = e->opt_side_streams != 0;
-    const bool long_on_main = side && (e->opt_long_on_main < 0 ? (e->n_giant != 0 && e->giant_walk_bound) : e->opt_long_on_main != 0);
+    const bool side = e->opt.side_streams != 0;
+    const bool long_on_main = side && (e->opt.long_on_main < 0 ? (e->n_giant != 0 && e->giant_walk_bound) : e->opt.long_on_main != 0);
     const bool side_long = side && !long_on_main;
     hipStream_t s_long = side_long ? e->long_stream : e->stream;
     hipStream_t s_giant = !side ? e->stream : (long_on_main ? e->giant_stream : e->long_stream);
@@ -321,7 +321,7 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
     // rows from this degree on go the giant way in this stage
     const uint32_t giant_from = call.sp->f == 16 ? e->giant_f16() : e->giant_thresh;
     gnnvc::StageCall giant = call;   // (on the main queue until the fork; the pruned view only where the option asks for it)
-    if (!e->opt_prune_giant) giant.g = &e->g;
+    if (!e->opt.prune_giant) giant.g = &e->g;
     gnnvc::GiantRows gr;
     bool gather_first = false;
     if (e->n_giant) {
@@ -344,8 +344,8 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
         // ... or, however large, in an F = 1 stage that has no plan (a graph's first forward): every long row's chain is on the
         // side queue there and the gather at its head waited for slots for as long as the tile kernel ran (R-MAT-24: 3.1 ms
         // for a kernel that takes 0.6 alone; the stage 6.1 ms against the tile kernel's 3.3)
-        gather_first = side && (e->opt_giant_gather_first < 0 ? (!long_on_main && (e->giant_entries <= (16ull << 20) || plain_f1))
-                                                               : e->opt_giant_gather_first != 0);
+        gather_first = side && (e->opt.giant_gather_first < 0 ? (!long_on_main && (e->giant_entries <= (16ull << 20) || plain_f1))
+                                                               : e->opt.giant_gather_first != 0);
         if (gather_first) HIP_TRY(e, gnnvc::launch_giant_stage(giant, gr, giant_from, gnnvc::GiantPart::kGather));
     }
     if (side) {
@@ -395,9 +395,9 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     // run, which then writes the table on its way.  The consumer's k_c4_choose still decides from the counts of ALL rows
     // and has the table rewritten if the pilot chose otherwise: the pilot changes time, never a result.
     auto pilot = [&]() -> int {
-        if (!c.emit || e->c4_seeded[stage + 1] || !e->opt_pilot_rows) return GNNVC_OK;
-        e->c4_seeded[stage + 1] = true;
-        const uint32_t rows = std::min(e->opt_pilot_rows, hi - lo);
+        if (!c.emit || e->pg.c4_seeded[stage + 1] || !e->opt.pilot_rows) return GNNVC_OK;
+        e->pg.c4_seeded[stage + 1] = true;
+        const uint32_t rows = std::min(e->opt.pilot_rows, hi - lo);
         if ((uint64_t)rows * 8 > (uint64_t)(hi - lo)) return GNNVC_OK;   // (a graph this small is its own pilot: not worth a launch)
         uint32_t *cons = e->c4_desc.p + gnnvc_engine::kDescWords * stage;   // consumer stage `stage + 1`
         HIP_TRY(e, hipMemsetAsync(e->c4_emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
@@ -420,7 +420,7 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     }
     if (c.sums == StageChoice::kTableTiles) {
         uint32_t *d_in = e->t4_desc_of(stage, e->t4_parity), *d_out = e->t4_desc_of(stage, e->t4_parity ^ 1u);
-        const bool solo = e->t4_fit_seen[stage] && e->opt_t4_solo;
+        const bool solo = e->t4_fit_seen[stage] && e->opt.t4_solo;
         HIP_TRY(e, gnnvc::launch_stage_t4(plain, {.table_in = e->t4_table[stage - 1].p,
                                                   .counts_in = e->t4_counts_of(stage, e->t4_parity),
                                                   .counts_zero = e->t4_counts_of(stage, e->t4_parity ^ 1u),
@@ -438,20 +438,20 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     }
     if (c.sums == StageChoice::kLdsTable)   // (the sums share the blocked plan's buffer)
         return hip_rc(e, gnnvc::launch_stage0_lds_table(plain, lds_table_plan(e), e->lt_bytes.p, e->blk_acc.p, e->lt_bad.p,
-                                                        {.long_thresh = c.long_thresh, .mfma = e->opt_mfma == 1,
+                                                        {.long_thresh = c.long_thresh, .mfma = e->opt.mfma == 1,
                                                          .interleave = e->interleave, .emit = emit}));
     if (c.sums == StageChoice::kBlocked)
         return hip_rc(e, gnnvc::launch_stage0_blocked(plain,
                                                       {.nblocks = e->blk_count, .bp = e->blk_ptr.p, .colb = e->blk_col.p, .acc = e->blk_acc.p},
-                                                      {.long_thresh = e->long_thresh, .mfma = e->opt_mfma == 1,
+                                                      {.long_thresh = e->long_thresh, .mfma = e->opt.mfma == 1,
                                                        .interleave = e->interleave, .emit = emit}));
     gnnvc::CompactSums sums;   // (all null: the compact-table plan is not in this call)
     uint32_t *desc = nullptr;
     if (c.sums == StageChoice::kCompactPrepared || c.sums == StageChoice::kCompactWhole) {
         desc = e->c4_desc.p + gnnvc_engine::kDescWords * (stage - 1);
         e->c4_last_desc = gnnvc_engine::kDescWords * (stage - 1);
-        if (c.sums == StageChoice::kCompactWhole) e->fit_used[stage] = true;
-        sums = {.acc4 = e->c4_acc.p, .c4desc = desc, .agg16 = e->c4_agg16.p, .table_in = e->opt_dense_skip ? e->c4_table.p : nullptr};
+        if (c.sums == StageChoice::kCompactWhole) e->pg.fit_used[stage] = true;
+        sums = {.acc4 = e->c4_acc.p, .c4desc = desc, .agg16 = e->c4_agg16.p, .table_in = e->opt.dense_skip ? e->c4_table.p : nullptr};
         const bool whole = c.sums == StageChoice::kCompactWhole;
         if (whole && !c.fused_counts) HIP_TRY(e, gnnvc::column_counts(in, e->g.n, e->c4_counts.p, e->stream));
         const bool fused = whole && c.fused_counts;
@@ -471,14 +471,14 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     const gnnvc::SortedOrder *sop = c.sorted.n ? &c.sorted : nullptr;
     // Wide tiles (k_stage_w*): a graph with fewer tiles than the chip has SIMDs — the reference CLI's later predict calls — and
     // nothing but the plain gather to run (no plan, no long rows, no pruned adjacency, nothing to emit): a workgroup per tile
-    if (c.sums == StageChoice::kGather && e->opt_wide && e->g.n <= (sp.f == 16 ? e->opt_wide_max_n16 : e->opt_wide_max_n) && !e->g.sliced() && e->n_long == 0 && !sop &&
+    if (c.sums == StageChoice::kGather && e->opt.wide && e->g.n <= (sp.f == 16 ? e->opt.wide_max_n16 : e->opt.wide_max_n) && !e->g.sliced() && e->n_long == 0 && !sop &&
         !sums.acc4 && !emit.counts && gv.prune_bad == nullptr && gv.zero_bits == nullptr && sp.variant >= 0 && sp.variant <= 2) {
-        e->wide_used = true;
+        e->pg.wide_used = true;
         e->stage_wide = true;
         return hip_rc(e, gnnvc::launch_stage_wide(plain));
     }
     HIP_TRY(e, gnnvc::launch_stage(call, {.long_thresh = c.long_thresh, .mfma = c.mfma, .so = sop, .interleave = e->interleave,
-                                          .sums = sums, .mfma_agg = e->opt_mfma == 1, .emit = emit, .dense_part = !c.rounds,
+                                          .sums = sums, .mfma_agg = e->opt.mfma == 1, .emit = emit, .dense_part = !c.rounds,
                                           .so_pruned = so_p.vertex ? &so_p : nullptr}));
     if (!c.rounds) return GNNVC_OK;
     HIP_TRY(e, hipMemsetAsync(desc + 5, 0, sizeof(uint32_t), e->stream));        // dirty-row counter
@@ -568,8 +568,8 @@ int run_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float 
 // ---------------------------------------------------------------- the audit (options "audit_*", k_audit_stage)
 // Is this call of a forward entry point audited?  (calls k, 2k, 3k, ... since the period was set)
 bool audit_tick(gnnvc_engine *e) {
-    if (!e->opt_audit_period) return false;
-    return ++e->audit_calls % e->opt_audit_period == 0;
+    if (!e->opt.audit_period) return false;
+    return ++e->audit_calls % e->opt.audit_period == 0;
 }
 
 // right behind run_stage of `stage` over [lo, hi), on e->stream: the test hook, then the audit into the call's next record
@@ -581,10 +581,10 @@ int audit_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
     }
     if (slot >= e->stages.size()) return fail(e, GNNVC_ERR_STATE, "more audited stages than the model has");
     const gnnvc::StagePlan &sp = e->stages[stage];
-    if (e->opt_audit_flip_stage == stage && e->opt_audit_flip_row >= lo && e->opt_audit_flip_row < hi)
-        HIP_TRY(e, gnnvc::launch_audit_flip(out, (size_t)e->opt_audit_flip_row * (size_t)sp.n3, e->stream));
+    if (e->opt.audit_flip_stage == stage && e->opt.audit_flip_row >= lo && e->opt.audit_flip_row < hi)
+        HIP_TRY(e, gnnvc::launch_audit_flip(out, (size_t)e->opt.audit_flip_row * (size_t)sp.n3, e->stream));
     HIP_TRY(e, gnnvc::launch_audit_stage(stage_call(e, sp, in, out, sp.sigmoid_last ? logits : nullptr, lo, hi),
-                                         e->audit_rec.p + slot * gnnvc::kAuditWords, /*repair=*/e->opt_audit_repair != 0));
+                                         e->audit_rec.p + slot * gnnvc::kAuditWords, /*repair=*/e->opt.audit_repair != 0));
     e->audit_pending.push_back(gnnvc_engine::AuditCheck{stage, lo, hi, std::move(plan)});
     return GNNVC_OK;
 }
@@ -625,7 +625,7 @@ int audit_finish(gnnvc_engine *e, int rc) {
     }
     if (report.empty()) return GNNVC_OK;
     e->err = report;   // (also where a quiet engine's owner reads it)
-    if (e->opt_audit_repair || e->opt_audit_quiet) return GNNVC_OK;
+    if (e->opt.audit_repair || e->opt.audit_quiet) return GNNVC_OK;
     return GNNVC_ERR_AUDIT;
 }
 
@@ -726,7 +726,7 @@ int gnnvc_create(gnnvc_engine **out, const char *model_text, size_t len, int dev
         }
         if (rc == GNNVC_OK) rc = use_device(e);
         if (rc == GNNVC_OK) {
-            if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess)
+            if (e->own_stream.create(hipStreamNonBlocking) != hipSuccess)
                 rc = fail(e, GNNVC_ERR_DEVICE, "hipStreamCreate failed");
             e->stream = e->own_stream;
         }
@@ -739,7 +739,7 @@ int gnnvc_create(gnnvc_engine **out, const char *model_text, size_t len, int dev
         if (rc == GNNVC_OK && (e->fit_pin.reserve(8) != hipSuccess ||
                                hipHostGetDevicePointer(reinterpret_cast<void **>(&e->fit_dev), e->fit_pin.p, 0) != hipSuccess))
             rc = fail(e, GNNVC_ERR_NOMEM, "page-locked verdict words");
-        if (rc == GNNVC_OK && hipEventCreateWithFlags(&e->ev_fit, hipEventDisableTiming) != hipSuccess)
+        if (rc == GNNVC_OK && e->ev_fit.create(hipEventDisableTiming) != hipSuccess)
             rc = fail(e, GNNVC_ERR_DEVICE, "hipEventCreate failed");
     } catch (const std::bad_alloc &) {
         rc = GNNVC_ERR_NOMEM;
@@ -786,54 +786,12 @@ void gnnvc_destroy(gnnvc_engine *e) {
         gnnvc::multi_destroy(e->multi);
         e->multi = nullptr;
     }
+    // nothing of this engine's is in flight any more when its members (gnnvc_device_mem.h) free what they hold
     if (e->own_stream) {
         (void)hipSetDevice(e->device);
         (void)hipStreamSynchronize(e->own_stream);
+        if (e->aux_stream) (void)hipStreamSynchronize(e->aux_stream);
     }
-    e->params.release();
-    e->rowptr.release(); e->col.release(); e->w.release(); e->nw.release();
-    e->x.release(); e->h[0].release(); e->h[1].release();
-    e->scores.release(); e->logits.release();
-    e->scratch[0].release(); e->scratch[1].release();
-    e->blk_ptr.release(); e->blk_col.release(); e->blk_scratch.release(); e->blk_flag.release();
-    e->blk_acc.release();
-    e->lt_bytes.release(); e->lt_entries.release(); e->lt_segcnt.release(); e->lt_stepptr.release();
-    e->lt_stepcnt.release(); e->lt_bad.release(); e->lt_steps.release(); e->lt_rowmap.release(); e->lt_first.release(); e->lt_bstart.release();
-    e->c4_entries.release(); e->c4_segcnt.release(); e->c4_stepptr.release(); e->c4_stepcnt.release();
-    for (auto &t : e->t4_table) t.release();
-    for (auto &t : e->t4_counts) t.release();
-    e->t4_desc.release();
-    e->c4_desc.release(); e->c4_map_vertex.release(); e->c4_map_meta.release(); e->map_coarse.release(); e->c4_steps.release(); e->c4_table.release(); e->c4_marks.release(); e->c4_acc.release(); e->c4_counts.release();
-    e->c4_agg16.release(); e->c4_dirty.release(); e->c4_emit_counts.release();
-    for (auto &pp : e->prune) { pp.prp.release(); pp.pcol.release(); pp.heavy.release(); pp.svertex.release(); pp.smeta.release(); }
-    e->prune_flags.release(); e->prune_scratch.release(); e->prune_off.release(); e->prune_mask.release();
-    for (auto &b : e->filter_bits) b.release();
-    e->filter_info.release();
-    e->long_list.release(); e->long_count.release(); e->cls_dev.release(); e->cls_pin.release();
-    e->gi_meta.release(); e->gi_off.release(); e->gi_slab.release(); e->gi_agg.release(); e->gi_segsum.release(); e->gi_segmap.release();
-    e->rowptr2.release(); e->col2.release(); e->der_old_row.release(); e->der_new_of.release(); e->der_tail.release();
-    e->der_tailptr.release(); e->der_tailcols.release(); e->hash_buf.release();
-    e->pin_rowptr.release(); e->pin_col.release(); e->pin_w.release(); e->pin_nw.release(); e->fit_pin.release();
-    if (e->ev_fit) (void)hipEventDestroy(e->ev_fit);
-    if (e->ev_piece) (void)hipEventDestroy(e->ev_piece);
-    e->pin_small.release();
-    e->pin_info.release();
-    e->audit_rec.release();
-    e->audit_pin.release();
-    e->dev_info.release();
-    for (auto &r : e->srt) { r.vertex.release(); r.meta.release(); }
-    e->srt_hist.release(); e->srt_sum.release();
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    if (e->aux_stream) { (void)hipStreamSynchronize(e->aux_stream); (void)hipStreamDestroy(e->aux_stream); }
-    if (e->ev_long) (void)hipEventDestroy(e->ev_long);
-
-
-    if (e->ev_giant) (void)hipEventDestroy(e->ev_giant);
-    for (auto v : e->ev) (void)hipEventDestroy(v);
-    for (auto v : e->round_ev) (void)hipEventDestroy(v);
-    for (auto &r : e->ktrace.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
 }
 
@@ -863,104 +821,20 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream) {
 
 int gnnvc_set_option(gnnvc_engine *e, const char *key, long value) {
     if (!e || !key) return GNNVC_ERR_INVALID;
-    const std::string k(key);
-    if (k.rfind("multi_", 0) == 0) {   // the exchange of a multi-device handle (gnnvc_multi.cpp): "multi_pieces", "multi_pack", "multi_push", "multi_only_part"
+    if (strncmp(key, "multi_", 6) == 0) {   // the exchange of a multi-device handle (gnnvc_multi.cpp): "multi_pieces", "multi_pack", "multi_push", "multi_only_part"
         if (!e->multi) return fail(e, GNNVC_ERR_INVALID, "option '%s' needs a multi-device handle (gnnvc_create_multi)", key);
         const int rc = gnnvc::multi_set_option(e->multi, key, value);
         return rc ? fail(e, rc, "unknown option '%s'", key) : GNNVC_OK;
     }
-    if (k == "poison_features") {
-        e->opt_poison = value != 0 ? 1 : 0;
-        return e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
-    }
-    if (k == "verdict_period") {
-        e->opt_verdict_period = value < 1 ? 1u : (value > 64 ? 64u : (uint32_t)value);
-        return e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
-    }
-    // the audit (k_audit_stage): touches nothing a forward has cached.  A multi-device handle decides per forward whether its
-    // parts audit (gnnvc_multi.cpp); the others go to every part.
-    if (k == "audit_period") {
-        e->opt_audit_period = value < 0 ? 0u : (uint32_t)std::min<long>(value, 0x7FFFFFFF);
-        e->audit_calls = 0;   // (calls are counted from here)
-        return GNNVC_OK;
-    }
-    if (k == "generic_stages") {   // (k_stage_any: takes effect at once, touches nothing a forward has cached; a multi-device handle's parts keep their kernels)
-        e->opt_generic = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
-        return GNNVC_OK;
-    }
-    if (k == "audit_log") {   // (the front handle of several devices prints for all its parts)
-        e->opt_audit_log = value != 0 ? 1 : 0;
-        return GNNVC_OK;
-    }
-    if (k == "audit_repair" || k == "audit_flip_stage" || k == "audit_flip_row" || k == "audit_quiet") {
-        if (k == "audit_repair") e->opt_audit_repair = value != 0 ? 1 : 0;
-        else if (k == "audit_flip_stage") e->opt_audit_flip_stage = value < 0 ? -1 : (int)std::min<long>(value, 64);
-        else if (k == "audit_flip_row") e->opt_audit_flip_row = value < 0 ? 0xFFFFFFFFu : (uint32_t)std::min<long>(value, 0xFFFFFFFFl);
-        else e->opt_audit_quiet = value != 0 ? 1 : 0;
-        return e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
-    }
-    if (k == "forward_timing") {   // (touches nothing a forward has cached)
-        e->opt_timing = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
-        return e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
-    }
-    e->short_from = 0;   // (lists a filtered stage left go by the thresholds and variants of the call that wrote them)
-    if (k == "blocked_stage0") e->opt_blocked = value < 0 ? 0 : (value > 2 ? 2 : (int)value);   // 2 = also on skewed graphs
-    else if (k == "block_cols") e->opt_block_cols = value > 0 ? (uint32_t)value : 0;
-    else if (k == "blocked_min_n") e->opt_blocked_min_n = value > 0 ? (uint32_t)value : 0;
-    else if (k == "compact_min_n") e->opt_compact_min_n = value > 0 ? (uint32_t)value : 0;
-    else if (k == "compact_first_forward_entries") e->opt_compact_first_entries = value > 0 ? (uint64_t)value : 0;
-    else if (k == "plan_chunk_rows") e->opt_plan_chunk_rows = value > 0 ? (uint32_t)value : 0;
-    else if (k == "overlap_dense") e->opt_overlap = value != 0 ? 1 : 0;
-    else if (k == "long_row_threshold") { e->opt_long_thresh = value > 0 ? (uint32_t)value : 0; e->opt_long_auto = false; }
-    else if (k == "giant_row_threshold") {   // (an explicit threshold holds for every stage; "giant_row_threshold_f16" afterwards refines it)
-        e->opt_giant_thresh = value > 0 ? (uint32_t)std::max<long>(value, 64) : 0;
-        e->opt_giant_f16 = e->opt_giant_thresh ? e->opt_giant_thresh : 1u;
-        e->giant_f16_auto = false;
-    }
-    else if (k == "giant_row_threshold_f16") { e->opt_giant_f16 = value > 0 ? (uint32_t)value : 1u; e->giant_f16_auto = false; for (auto &pp : e->prune) pp.forget(); }
-    else if (k == "giant_segments") e->opt_giant_segments = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "side_streams") e->opt_side_streams = value != 0 ? 1 : 0;
-    else if (k == "kernel_trace") e->opt_ktrace = value != 0 ? 1 : 0;
-    else if (k == "compact_gather") e->opt_compact = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
-    else if (k == "prune_zero_rows") { e->opt_prune = value > 0 ? 1 : 0; for (auto &pp : e->prune) pp.forget(); }
-    else if (k == "prune_class_by_entries_left") { e->opt_prune_eff = value != 0 ? 1 : 0; for (auto &pp : e->prune) pp.forget(); }
-    else if (k == "prune_heavy_entries") { e->opt_prune_heavy_entries = value > 0 ? (uint64_t)value : 0; for (auto &pp : e->prune) pp.forget(); }
-    else if (k == "prune_early_entries") e->opt_prune_early_nnz = value > 0 ? (uint64_t)value : 0;
-    else if (k == "prune_giant_rows") e->opt_prune_giant = value != 0 ? 1 : 0;
-    else if (k == "prune_predict") e->opt_prune_predict = value != 0 ? 1 : 0;
-    else if (k == "wide_tiles") e->opt_wide = value != 0 ? 1 : 0;
-    else if (k == "wide_tiles_max_n") e->opt_wide_max_n = value > 0 ? (uint32_t)value : 0u;
-    else if (k == "wide_tiles_max_n_f16") e->opt_wide_max_n16 = value > 0 ? (uint32_t)value : 0u;
-    else if (k == "dense_skip_zeros") e->opt_dense_skip = value != 0 ? 1 : 0;
-    else if (k == "table_tiles") e->opt_t4 = value != 0 ? 1 : 0;
-    else if (k == "table_tiles_solo") e->opt_t4_solo = value != 0 ? 1 : 0;
-    else if (k == "table_tiles_min_n") e->opt_t4_min_n = value > 0 ? (uint32_t)value : 0u;
-    else if (k == "table_tiles_max_bytes") e->opt_t4_max_bytes = value > 0 ? (uint64_t)value : 0ull;
-    else if (k == "prune_predict_min_entries") e->opt_predict_min_nnz = value > 0 ? (uint64_t)value : 0;
-    else if (k == "giant_gather_first") e->opt_giant_gather_first = value < 0 ? -1 : (value != 0 ? 1 : 0);
-    else if (k == "long_rows_on_main") e->opt_long_on_main = value < 0 ? -1 : (value != 0 ? 1 : 0);
-    else if (k == "filter_zero_rows") e->opt_filter = value != 0 ? 1 : 0;
-    else if (k == "filter_keep_lists") e->opt_filter_keep = value != 0 ? 1 : 0;
-    else if (k == "filter_min_entries") e->opt_filter_min_nnz = value > 0 ? (uint64_t)value : 0;
-    else if (k == "filter_min_long_percent") e->opt_filter_min_long_pct = value < 0 ? 0u : (value > 100 ? 101u : (uint32_t)value);
-    else if (k == "filter_min_percent") e->opt_filter_min_pct = value < 0 ? 0u : (value > 100 ? 101u : (uint32_t)value);
-    else if (k == "prune_min_entries") e->opt_prune_min_nnz = value > 0 ? (uint64_t)value : 0;
-    else if (k == "prune_min_drop_percent") e->opt_prune_min_drop = value < 0 ? 0u : (value > 100 ? 100u : (uint32_t)value);
-    else if (k == "lds_table_skewed") e->opt_lds_skewed = value != 0 ? 1 : 0;
-    else if (k == "lds_table_skewed_rows") e->opt_lds_skewed_rows = value > 0 ? (uint32_t)value : 0u;
-    else if (k == "lds_table") e->opt_lds_table = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
-    else if (k == "lds_table_min_chunks") e->opt_lt_min_chunks = value > 0 ? (uint32_t)value : 1u;
-    else if (k == "lds_table_bits") e->opt_lt_bits = (value == 8 || value == 10 || value == 16) ? (int)value : 0;
-    else if (k == "plans_at_handoff") e->opt_handoff = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
-    else if (k == "handoff_min_entries") e->opt_handoff_min_nnz = value > 0 ? (uint64_t)value : 0;
-    else if (k == "pilot_rows") e->opt_pilot_rows = value > 0 ? (uint32_t)value : 0u;
-    else if (k == "sorted_min_nnz") e->opt_sorted_min_nnz = value > 0 ? (uint64_t)value : 0;
-    else if (k == "sorted_long_row_threshold") { e->opt_sorted_long_thresh = value > 0 ? (uint32_t)value : 1; e->opt_long_auto = false; }
-    else if (k == "mfma_dense") e->opt_mfma = (value >= 0 && value <= 2) ? (int)value : 2;
-    else if (k == "sorted_tiles") { e->opt_sorted = value < 0 ? -1 : (value ? 1 : 0); for (auto &r : e->srt) r.valid = false; }
-    else return fail(e, GNNVC_ERR_INVALID, "unknown option '%s'", key);
-    if (e->multi) return gnnvc::multi_set_option(e->multi, key, value);
-    return GNNVC_OK;
+    uint32_t fx = 0;   // (the keys, their clamps and their effects: gnnvc_options.h)
+    if (!gnnvc::apply_option(e->opt, key, value, &fx)) return fail(e, GNNVC_ERR_INVALID, "unknown option '%s'", key);
+    if (fx & gnnvc::kFxShortLists) e->pg.short_from = 0;
+    if (fx & gnnvc::kFxForgetPruned)
+        for (auto &pp : e->prune) pp.forget();
+    if (fx & gnnvc::kFxSortedStale)
+        for (auto &r : e->srt) r.valid = false;
+    if (fx & gnnvc::kFxAuditRestart) e->audit_calls = 0;
+    return (fx & gnnvc::kFxForward) && e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
 }
 
 int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
@@ -977,7 +851,7 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (e->multi && k.rfind("audit_", 0) == 0) {   // the parts' audits (gnnvc_multi.cpp)
         if (!gnnvc::multi_audit_info(e->multi, key, value)) return GNNVC_ERR_INVALID;
     }
-    else if (k == "generic_stages") *value = e->opt_generic;
+    else if (k == "generic_stages" || k == "plans_at_handoff" || k == "mfma_dense") (void)gnnvc::read_option(e->opt, key, value);   // (as set)
     else if (k == "generic_stages_model") *value = e->generic_on() ? 1 : 0;   // would a forward run k_stage_any now
     else if (k == "generic_stages_active") *value = e->generic_ran ? 1 : 0;   // did the last one
     else if (k == "audit_runs") *value = (long)e->audit_runs;
@@ -994,11 +868,11 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k.rfind("multi_", 0) == 0) {
         if (!e->multi || !gnnvc::multi_get_info(e->multi, key, value)) return GNNVC_ERR_INVALID;
     }
-    else if (k == "compact_gather_active") *value = e->c4_ready ? 1 : 0;
-    else if (k == "compact_gather_chunks") *value = e->c4_ready ? (long)e->c4_chunks : 0;
-    else if (k == "compact_gather_block_cols") *value = e->c4_ready ? (long)e->c4_block : 0;
-    else if (k == "compact_gather_rows_per_chunk") *value = e->c4_ready ? (long)e->c4_rows : 0;
-    else if (k == "compact_gather_steps") *value = e->c4_ready ? (long)e->c4_steps_total : 0;
+    else if (k == "compact_gather_active") *value = e->pg.c4_ready ? 1 : 0;
+    else if (k == "compact_gather_chunks") *value = e->pg.c4_ready ? (long)e->c4_chunks : 0;
+    else if (k == "compact_gather_block_cols") *value = e->pg.c4_ready ? (long)e->c4_block : 0;
+    else if (k == "compact_gather_rows_per_chunk") *value = e->pg.c4_ready ? (long)e->c4_rows : 0;
+    else if (k == "compact_gather_steps") *value = e->pg.c4_ready ? (long)e->c4_steps_total : 0;
     else if (k == "pruned_stage1" || k == "pruned_stage2") *value = e->prune[k.back() - '0'].ready ? 1 : 0;
     else if (k == "side_queue_probes") *value = e->side_probes;
     else if (k == "side_queue_runs_beside") *value = e->side_beside ? 1 : 0;
@@ -1033,7 +907,7 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
             *value = bad == 0 ? 1 : 0;
         }
     }
-    else if (k == "wide_tiles_used") *value = e->wide_used ? 1 : 0;   // (did any stage since the graph was handed over run on wide tiles)
+    else if (k == "wide_tiles_used") *value = e->pg.wide_used ? 1 : 0;   // (did any stage since the graph was handed over run on wide tiles)
     else if (k == "table_tiles_active") *value = e->t4_ok ? 1 : 0;
     else if (k == "table_tiles_fit_stage1" || k == "table_tiles_fit_stage2") {   // did the last forward's stage run on the table?  (waits for the stream)
         *value = 0;
@@ -1046,15 +920,15 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
             *value = (long)fit;
         }
     }
-    else if (k == "lds_table_off") *value = e->lt_off ? 1 : 0;
-    else if (k == "lds_table_bits") *value = e->lt_ready ? (long)e->lt_bits : 0;
-    else if (k == "compact_gather_off_stage1" || k == "compact_gather_off_stage2") *value = e->c4_stage_off[k.back() - '0'] ? 1 : 0;
-    else if (k == "compact_gather_blocks") *value = e->c4_ready ? (long)e->c4_nblocks : 0;
+    else if (k == "lds_table_off") *value = e->pg.lt_off ? 1 : 0;
+    else if (k == "lds_table_bits") *value = e->pg.lt_ready ? (long)e->lt_bits : 0;
+    else if (k == "compact_gather_off_stage1" || k == "compact_gather_off_stage2") *value = e->pg.c4_stage_off[k.back() - '0'] ? 1 : 0;
+    else if (k == "compact_gather_blocks") *value = e->pg.c4_ready ? (long)e->c4_nblocks : 0;
     else if (k == "compact_gather_last_ok" || k == "compact_gather_last_dirty" || k == "compact_gather_last_passes" ||
              k == "compact_table_written_by_producer") {
         // what the device decided at the last launch of the plan (waits for the stream; for tests and tools)
         *value = 0;
-        if (e->c4_ready && e->c4_desc.p) {
+        if (e->pg.c4_ready && e->c4_desc.p) {
             uint32_t d[8] = {0};
             if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
                 hipMemcpy(d, e->c4_desc.p + e->c4_last_desc, sizeof d, hipMemcpyDeviceToHost) != hipSuccess)
@@ -1063,10 +937,10 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
             else *value = k == "compact_gather_last_ok" ? (d[0] ? 1 : 0) : (k == "compact_gather_last_passes" ? (long)d[0] : (long)d[5]);
         }
     }
-    else if (k == "lds_table_active") *value = e->lt_ready ? 1 : 0;
+    else if (k == "lds_table_active") *value = e->pg.lt_ready ? 1 : 0;
     else if (k == "lds_table_last_ok") {   // did the last forward's input fit the table?  (waits for the stream; tests and tools)
         *value = 0;
-        if (e->lt_ready && e->lt_bad.p) {
+        if (e->pg.lt_ready && e->lt_bad.p) {
             uint32_t bad = 1;
             if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
                 hipMemcpy(&bad, e->lt_bad.p, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess)
@@ -1074,26 +948,24 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
             *value = bad == 0 ? 1 : 0;
         }
     }
-    else if (k == "lds_table_mapped") *value = e->lt_ready && e->lt_mapped ? 1 : 0;
-    else if (k == "lds_table_blocks") *value = e->lt_ready ? (long)e->lt_blocks : 0;
-    else if (k == "lds_table_chunks") *value = e->lt_ready ? (long)e->lt_chunks : 0;
-    else if (k == "lds_table_steps") *value = e->lt_ready ? (long)e->lt_steps_total : 0;
-    else if (k == "blocked_stage0_active") *value = e->blocked_ready ? 1 : 0;
-    else if (k == "blocked_blocks") *value = e->blocked_ready ? (long)e->blk_count : 0;
-    else if (k == "block_cols") *value = e->blocked_ready ? (long)e->blk_cols : 0;
+    else if (k == "lds_table_mapped") *value = e->pg.lt_ready && e->lt_mapped ? 1 : 0;
+    else if (k == "lds_table_blocks") *value = e->pg.lt_ready ? (long)e->lt_blocks : 0;
+    else if (k == "lds_table_chunks") *value = e->pg.lt_ready ? (long)e->lt_chunks : 0;
+    else if (k == "lds_table_steps") *value = e->pg.lt_ready ? (long)e->lt_steps_total : 0;
+    else if (k == "blocked_stage0_active") *value = e->pg.blocked_ready ? 1 : 0;
+    else if (k == "blocked_blocks") *value = e->pg.blocked_ready ? (long)e->blk_count : 0;
+    else if (k == "block_cols") *value = e->pg.blocked_ready ? (long)e->blk_cols : 0;
     else if (k == "long_rows") *value = (long)e->n_long;
-    else if (k == "plan_build_us") *value = (long)(e->plan_build_ms * 1000.0);
+    else if (k == "plan_build_us") *value = (long)(e->pg.plan_build_ms * 1000.0);
     else if (k == "handoff_build_us") *value = (long)(e->handoff_build_ms * 1000.0);
-    else if (k == "handoff_early_us") *value = (long)(e->early_ms * 1000.0);
-    else if (k == "plans_at_handoff") *value = e->opt_handoff;
-    else if (k == "graph_uses") *value = (long)e->graph_uses;
+    else if (k == "handoff_early_us") *value = (long)(e->pg.early_ms * 1000.0);
+    else if (k == "graph_uses") *value = (long)e->pg.graph_uses;
     else if (k == "slice_rows") *value = e->empty_slice ? 0 : (long)(e->g.hi() - e->g.lo());
     else if (k == "slice_entries") *value = (long)e->g.nnz;
     else if (k == "giant_rows") *value = (long)e->n_giant;
     else if (k == "giant_segments") *value = e->n_giant ? (long)e->gi_maxseg : 0;
     else if (k == "giant_entries") *value = (long)e->giant_entries;
     else if (k == "giant_row_threshold") *value = e->n_giant ? (long)e->giant_thresh : 0;
-    else if (k == "mfma_dense") *value = e->opt_mfma;
     else if (k == "sorted_tiles_active") *value = e->sorted_wanted ? 1 : 0;
     else if (k == "tile_waste_x100") *value = (long)(e->srt_waste * 100.0);
     else if (k == "heavy_tail_x1000") *value = (long)(e->srt_tail * 1000.0);
@@ -1150,7 +1022,7 @@ static int handoff_progress(gnnvc_engine *e, const RP *rp, uint32_t n, uint64_t 
         if (rc == GNNVC_OK) rc = c4_advance(e, c4_to, e->aux_stream);
         if (rc) return rc;
     }
-    e->early_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    e->pg.early_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return GNNVC_OK;
 }
 }   // extern "C++"
@@ -1314,8 +1186,8 @@ int gnnvc_staged_columns_ready(gnnvc_engine *e, uint64_t first, uint64_t count) 
     e->staged_sent = first + count;
     // Large graphs: the row pointers and weights are final by now (step 1 of the protocol) — they go out, the graph is classed
     // and its plans begun, and from here on every announced piece lets the second stream regroup the slices it completes.
-    if (!e->early_open && !e->early_declined && e->opt_handoff && e->staged_n &&
-        (e->opt_handoff >= 2 || e->staged_nnz >= e->opt_handoff_min_nnz) && e->pin_rowptr.p[e->staged_n] == e->staged_nnz) {
+    if (!e->early_open && !e->early_declined && e->opt.handoff && e->staged_n &&
+        (e->opt.handoff >= 2 || e->staged_nnz >= e->opt.handoff_min_nnz) && e->pin_rowptr.p[e->staged_n] == e->staged_nnz) {
         const uint32_t n = e->staged_n;
         HIP_TRY(e, e->rowptr.reserve((size_t)n + 1));
         HIP_TRY(e, e->w.reserve(n));
@@ -1577,7 +1449,7 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     rc = run_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits, false, &plan);
     if (rc == GNNVC_OK) rc = audit_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits, plan);
     rc = audit_finish(e, rc);
-    if (e->opt_audit_log) audit_log_line(e, rc);
+    if (e->opt.audit_log) audit_log_line(e, rc);
     return rc;
 }
 
@@ -1607,13 +1479,13 @@ int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, flo
         rc = gnnvc::multi_forward_device(e->multi, d_x, d_scores, d_logits, audit, err);
         (void)hipSetDevice(e->device);
         if (rc) rc = fail(e, rc, "%s", err.c_str());
-        if (audit && e->opt_audit_log) audit_log_line(e, rc);
+        if (audit && e->opt.audit_log) audit_log_line(e, rc);
         return rc;
     }
     // (an unfused model runs the layer-by-layer kernels, a generic-stage model k_stage_any: nothing to audit)
     e->audit_now = audit && !e->stages.empty() && !e->generic_on();
     const int rc = audit_finish(e, forward_single(e, d_x, d_scores, d_logits));
-    if (audit && e->opt_audit_log) audit_log_line(e, rc);
+    if (audit && e->opt.audit_log) audit_log_line(e, rc);
     return rc;
 }
 
@@ -1632,11 +1504,11 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     if (e->generic_ran || e->stages.empty()) {
         rc = ensure_events(e, 2);
         if (rc) return rc;
-        if (e->opt_timing >= 1) HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
+        if (e->opt.timing >= 1) HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
         rc = e->generic_ran ? forward_generic(e, d_x, d_scores, d_logits) : forward_unfused(e, d_x, d_scores, d_logits);
         if (rc) return rc;
-        if (e->opt_timing >= 1) HIP_TRY(e, hipEventRecord(e->ev[1], e->stream));
-        e->ev_count = e->opt_timing >= 1 ? 2 : 0;
+        if (e->opt.timing >= 1) HIP_TRY(e, hipEventRecord(e->ev[1], e->stream));
+        e->ev_count = e->opt.timing >= 1 ? 2 : 0;
         e->ev_stages = false;
         return GNNVC_OK;
     }
@@ -1645,14 +1517,14 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     if (rc) return rc;
     const float *cur = d_x;   // (the pad rows of e->h were zeroed when the graph was handed over: reserve_features)
     e->c4_fused_for = -1;
-    e->c4_prepared_stage = -1;
-    if (e->fit_pending && hipEventQuery(e->ev_fit) == hipSuccess) {   // the previous forward's verdicts have arrived
-        e->fit_pending = false;
-        const uint32_t before = e->lt_unfit_runs + e->t4_unfit_runs + e->c4_unfit_runs[1] + e->c4_unfit_runs[2];
+    e->pg.c4_prepared_stage = -1;
+    if (e->pg.fit_pending && hipEventQuery(e->ev_fit) == hipSuccess) {   // the previous forward's verdicts have arrived
+        e->pg.fit_pending = false;
+        const uint32_t before = e->pg.lt_unfit_runs + e->t4_unfit_runs + e->pg.c4_unfit_runs[1] + e->pg.c4_unfit_runs[2];
         const bool seen1 = e->t4_fit_seen[1], seen2 = e->t4_fit_seen[2];
-        if (e->lt_used && e->lt_ready) {
-            e->lt_unfit_runs = e->fit_pin.p[2] != 0u ? e->lt_unfit_runs + 1 : 0u;
-            if (e->lt_unfit_runs >= (e->lt_mapped ? 1u : 3u)) e->lt_off = true;
+        if (e->pg.lt_used && e->pg.lt_ready) {
+            e->pg.lt_unfit_runs = e->fit_pin.p[2] != 0u ? e->pg.lt_unfit_runs + 1 : 0u;
+            if (e->pg.lt_unfit_runs >= (e->lt_mapped ? 1u : 3u)) e->pg.lt_off = true;
         }
         if (e->t4_used && e->t4_ok) {
             // table tiles: a graph whose first 16-wide stage keeps missing (more than four live columns: sparse graphs) stops paying
@@ -1666,39 +1538,39 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
             e->t4_fit_seen[2] = e->fit_pin.p[4] != 0u;
         }
         for (int s = 1; s <= 2; ++s) {
-            if (!e->fit_used[s]) continue;
+            if (!e->pg.fit_used[s]) continue;
             // (a stage whose statistics were to come from a producer that itself fell back had no chance: not its miss)
-            if (s == 2 && e->fit_used[1] && e->fit_pin.p[0] == 0u) continue;
-            e->c4_unfit_runs[s] = e->fit_pin.p[s - 1] == 0u ? e->c4_unfit_runs[s] + 1 : 0u;
-            if (e->c4_unfit_runs[s] >= 3u) e->c4_stage_off[s] = true;
+            if (s == 2 && e->pg.fit_used[1] && e->fit_pin.p[0] == 0u) continue;
+            e->pg.c4_unfit_runs[s] = e->fit_pin.p[s - 1] == 0u ? e->pg.c4_unfit_runs[s] + 1 : 0u;
+            if (e->pg.c4_unfit_runs[s] >= 3u) e->pg.c4_stage_off[s] = true;
         }
-        const uint32_t after = e->lt_unfit_runs + e->t4_unfit_runs + e->c4_unfit_runs[1] + e->c4_unfit_runs[2];
+        const uint32_t after = e->pg.lt_unfit_runs + e->t4_unfit_runs + e->pg.c4_unfit_runs[1] + e->pg.c4_unfit_runs[2];
         const bool calm = after == 0u && before == 0u && seen1 == e->t4_fit_seen[1] && seen2 == e->t4_fit_seen[2];
-        e->fit_calm = calm ? e->fit_calm + 1u : 0u;
+        e->pg.fit_calm = calm ? e->pg.fit_calm + 1u : 0u;
     }
-    if (!e->fit_pending) {
-        for (int s = 0; s < 4; ++s) e->fit_used[s] = false;
-        e->lt_used = false;
+    if (!e->pg.fit_pending) {
+        for (int s = 0; s < 4; ++s) e->pg.fit_used[s] = false;
+        e->pg.lt_used = false;
         e->t4_used = false;
     }
     struct SinkGuard {   // the thread-local sink never outlives this call, whichever way it returns
         ~SinkGuard() { gnnvc::set_kernel_trace(nullptr); }
     } sink_guard;
-    if (e->opt_ktrace && e->ktrace.used < 16384) {   // records pile up over forwards until gnnvc_kernel_trace reads them
+    if (e->opt.ktrace && e->ktrace.used < 16384) {   // records pile up over forwards until gnnvc_kernel_trace reads them
         e->ktrace.stream = e->stream;
         gnnvc::set_kernel_trace(&e->ktrace);
     }
     // Table tiles are offered from a graph's SECOND forward on — or from its first, when the engine carries a choice of columns
     // over from its previous graph: a fresh engine's first forward on a graph has no table to gather from, and the counting, the
     // choice and the launches that leave at once would only cost the caller who scores the graph once (ER-100K: 0.14 vs 0.11 ms).
-    e->t4_now = e->t4_ok && (e->t4_choice_live || e->graph_uses >= 1);
+    e->t4_now = e->t4_ok && (e->t4_choice_live || e->pg.graph_uses >= 1);
     // Events (option "forward_timing"): none by default — a record costs the stream ~1.8 us, four of them were 5.5 us of a small
     // graph's 31 - 82 us forward (scratch/experiments/r4_gaps.sh) — 1 = the forward's first and last, 2 = one per stage as well.
     // (ev[0] is also what the first-forward plan build on the second stream waits for, below.)
-    const bool build_under_stage0 = ns >= 2 && !e->c4_tried && !e->c4_range_mode && e->aux_stream && e->n_long == 0 && !e->sorted_wanted &&
-                                    e->opt_compact_first_entries && e->g.nnz >= e->opt_compact_first_entries;
-    if (e->opt_timing >= 1 || build_under_stage0) HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
-    if (e->opt_poison)   // (tests, fuzz: rows 0 .. n - 1 of both feature buffers; the pad row n stays zero)
+    const bool build_under_stage0 = ns >= 2 && !e->pg.c4_tried && !e->pg.c4_range_mode && e->aux_stream && e->n_long == 0 && !e->sorted_wanted &&
+                                    e->opt.compact_first_entries && e->g.nnz >= e->opt.compact_first_entries;
+    if (e->opt.timing >= 1 || build_under_stage0) HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
+    if (e->opt.poison)   // (tests, fuzz: rows 0 .. n - 1 of both feature buffers; the pad row n stays zero)
         for (size_t b = 0; b + 1 < ns && b < 2; ++b) HIP_TRY(e, hipMemsetAsync(e->h[b].p, 0xFF, (size_t)n * 16 * sizeof(float), e->stream));
     for (size_t s = 0; s < ns; ++s) {
         const bool last = s + 1 == ns;
@@ -1707,8 +1579,8 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
         rc = run_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, /*in_forward=*/true, e->audit_now ? &plan : nullptr);
         if (rc) break;
         if (e->audit_now && (rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan)) != GNNVC_OK) break;
-        if ((e->opt_timing >= 2 || (last && e->opt_timing == 1)) && hipEventRecord(e->ev[s + 1], e->stream) != hipSuccess) { rc = fail(e, GNNVC_ERR_DEVICE, "hipEventRecord failed"); break; }
-        if (s == 0 && build_under_stage0 && !e->c4_tried) {
+        if ((e->opt.timing >= 2 || (last && e->opt.timing == 1)) && hipEventRecord(e->ev[s + 1], e->stream) != hipSuccess) { rc = fail(e, GNNVC_ERR_DEVICE, "hipEventRecord failed"); break; }
+        if (s == 0 && build_under_stage0 && !e->pg.c4_tried) {
             // A large graph's first forward: the compact-table plan of the stages to come depends on the graph alone — it is
             // built now, on the second stream, under the kernels of stage 0 that were just queued (the build synchronises with
             // its own stream only; it is complete when it returns).
@@ -1728,23 +1600,23 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
         e->t4_parity ^= 1u;
         e->t4_choice_live = true;
     }
-    e->ev_count = e->opt_timing >= 1 ? (int)ns + 1 : 0;
-    e->ev_stages = e->opt_timing >= 2;
-    const bool c4_verdicts = (e->fit_used[1] || e->fit_used[2]) && e->c4_ready && e->c4_desc.p;
-    const bool lt_verdict = e->lt_used && e->lt_ready && e->lt_bad.p;
+    e->ev_count = e->opt.timing >= 1 ? (int)ns + 1 : 0;
+    e->ev_stages = e->opt.timing >= 2;
+    const bool c4_verdicts = (e->pg.fit_used[1] || e->pg.fit_used[2]) && e->pg.c4_ready && e->c4_desc.p;
+    const bool lt_verdict = e->pg.lt_used && e->pg.lt_ready && e->lt_bad.p;
     const bool t4_verdict = e->t4_now && e->t4_desc.p;
-    if (t4_verdict && !e->fit_pending) e->t4_used = true;
-    if (!e->fit_pending && (c4_verdicts || lt_verdict || t4_verdict)) {   // this forward's verdicts, written out behind it
+    if (t4_verdict && !e->pg.fit_pending) e->t4_used = true;
+    if (!e->pg.fit_pending && (c4_verdicts || lt_verdict || t4_verdict)) {   // this forward's verdicts, written out behind it
         // ONE small kernel stores the words into page-locked host memory (round 4: they were up to five 4-byte hipMemcpyAsync, ~20 us
         // of a small graph's forward + wait, scratch/experiments/r4_gaps.sh), and once four verdicts in a row have changed nothing
         // only every eighth forward asks — a verdict steers which kernels the NEXT forwards launch, never a result: every plan
         // proves its input on the device in every call.
-        const bool ask = e->fit_calm < 4u || (++e->fit_skip % e->opt_verdict_period) == 0u;
+        const bool ask = e->pg.fit_calm < 4u || (++e->pg.fit_skip % e->opt.verdict_period) == 0u;
         if (!ask) {
-            if (!c4_verdicts) for (int s = 1; s <= 2; ++s) e->fit_used[s] = false;
+            if (!c4_verdicts) for (int s = 1; s <= 2; ++s) e->pg.fit_used[s] = false;
             return GNNVC_OK;
         }
-        if (!e->ev_fit) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_fit, hipEventDisableTiming));
+        if (!e->ev_fit) HIP_TRY(e, e->ev_fit.create(hipEventDisableTiming));
         if (!e->fit_dev) {
             HIP_TRY(e, e->fit_pin.reserve(8));
             HIP_TRY(e, hipHostGetDevicePointer(reinterpret_cast<void **>(&e->fit_dev), e->fit_pin.p, 0));
@@ -1753,13 +1625,13 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
         if (c4_verdicts)
             for (int s = 1; s <= 2; ++s) vw.src[s - 1] = e->c4_desc.p + gnnvc_engine::kDescWords * (s - 1);
         else
-            for (int s = 1; s <= 2; ++s) e->fit_used[s] = false;
+            for (int s = 1; s <= 2; ++s) e->pg.fit_used[s] = false;
         if (lt_verdict) vw.src[2] = e->lt_bad.p;
         if (t4_verdict)   // (the parity has flipped: the descriptors this forward wrote are the current ones)
             for (int s = 1; s <= 2; ++s) vw.src[2 + s] = e->t4_desc_of(s, e->t4_parity) + 8;
         HIP_TRY(e, gnnvc::write_verdicts(vw, e->fit_dev, e->stream));
         HIP_TRY(e, hipEventRecord(e->ev_fit, e->stream));
-        e->fit_pending = true;
+        e->pg.fit_pending = true;
     }
     return GNNVC_OK;
 }
@@ -1771,28 +1643,28 @@ int gnnvc_stage_input_ready(gnnvc_engine *e, int stage, const float *d_in, uint3
     if (e->stages.empty()) return fail(e, GNNVC_ERR_UNSUPPORTED, "model is not fused into stages");
     if (stage < 1 || stage >= (int)e->stages.size()) return fail(e, GNNVC_ERR_INVALID, "stage %d has no 16-wide input", stage);
     if (row_lo > row_hi || row_hi > e->g.n) return fail(e, GNNVC_ERR_INVALID, "row range [%u, %u) outside the graph", row_lo, row_hi);
-    e->c4_prepared_stage = -1;
+    e->pg.c4_prepared_stage = -1;
     if (e->g.n == 0 || row_lo == row_hi || e->empty_slice) return GNNVC_OK;
     if (!d_in) return fail(e, GNNVC_ERR_INVALID, "null feature buffer");
     int rc = use_device(e);
     if (rc) return rc;
-    const bool same_range = e->c4_range_mode && e->c4_tried && e->c4_base == row_lo && e->c4_end == row_hi;
-    e->c4_range_mode = true;
+    const bool same_range = e->pg.c4_range_mode && e->pg.c4_tried && e->c4_base == row_lo && e->c4_end == row_hi;
+    e->pg.c4_range_mode = true;
     if (!same_range) {
         rc = build_compact(e, row_lo, row_hi);
         if (rc) return rc;
-        if (!e->c4_ready) {   // remember what was tried, so that the next forward does not try again
+        if (!e->pg.c4_ready) {   // remember what was tried, so that the next forward does not try again
             e->c4_base = row_lo;
             e->c4_end = row_hi;
         }
     }
-    if (!e->c4_ready || e->n_long > 0) return GNNVC_OK;   // the plan does not apply to this graph: nothing to prepare
+    if (!e->pg.c4_ready || e->n_long > 0) return GNNVC_OK;   // the plan does not apply to this graph: nothing to prepare
     uint32_t *desc = e->c4_desc.p + gnnvc_engine::kDescWords * (stage - 1);
     e->c4_last_desc = gnnvc_engine::kDescWords * (stage - 1);
     HIP_TRY(e, gnnvc::column_counts(d_in, e->g.n, e->c4_counts.p, e->stream));
     HIP_TRY(e, gnnvc::launch_compact_gather(e->g, compact_plan(e), d_in, e->c4_counts.p, 1, desc, e->c4_table.p, e->c4_acc.p, e->c4_base,
                                             e->c4_end, e->c4_dirty.p, e->c4_dirty_cap, e->c4_agg16.p, e->stream, /*what=*/1));
-    e->c4_prepared_stage = stage;
+    e->pg.c4_prepared_stage = stage;
     e->c4_prepared_in = d_in;
     return GNNVC_OK;
 }
@@ -2025,7 +1897,7 @@ int gnnvc_last_forward_ms(gnnvc_engine *e, float *total_ms, float *stage_ms, int
         return GNNVC_OK;
     }
     if (e->ev_count < 2)
-        return fail(e, GNNVC_ERR_STATE, e->opt_timing ? "no timed forward yet" : "no timed forward: option forward_timing is 0 (1 = total, 2 = per stage)");
+        return fail(e, GNNVC_ERR_STATE, e->opt.timing ? "no timed forward yet" : "no timed forward: option forward_timing is 0 (1 = total, 2 = per stage)");
     int rc = use_device(e);
     if (rc) return rc;
     HIP_TRY(e, hipEventSynchronize(e->ev[e->ev_count - 1]));
@@ -2040,7 +1912,7 @@ int gnnvc_last_forward_ms(gnnvc_engine *e, float *total_ms, float *stage_ms, int
 int gnnvc_kernel_trace(gnnvc_engine *e, int max, const char **names, float *ms, int *count) {
     if (!e || !count) return GNNVC_ERR_INVALID;
     *count = 0;
-    if (!e->opt_ktrace) return fail(e, GNNVC_ERR_STATE, "option kernel_trace is off");
+    if (!e->opt.ktrace) return fail(e, GNNVC_ERR_STATE, "option kernel_trace is off");
     int rc = use_device(e);
     if (rc) return rc;
     const size_t used = e->ktrace.used;
@@ -2102,23 +1974,17 @@ int gnnvc_linear_forward(gnnvc_engine *e, uint32_t n, uint32_t k, uint32_t m, co
     if (!in || !W || !bias || !out) return fail(e, GNNVC_ERR_INVALID, "null host buffers");
     int rc = use_device(e);
     if (rc) return rc;
-    DevBuf<float> dW;
+    DevBuf<float> dW;   // (freed when the call returns: run_host_op has waited for the stream by then)
     HIP_TRY(e, dW.reserve((size_t)k * m + m));
-    rc = GNNVC_OK;
     hipError_t h1 = hipMemcpy(dW.p, W, (size_t)k * m * sizeof(float), hipMemcpyHostToDevice);
     hipError_t h2 = hipMemcpy(dW.p + (size_t)k * m, bias, (size_t)m * sizeof(float), hipMemcpyHostToDevice);
-    if (h1 != hipSuccess || h2 != hipSuccess) {
-        dW.release();
-        return fail(e, GNNVC_ERR_DEVICE, "parameter upload failed");
-    }
+    if (h1 != hipSuccess || h2 != hipSuccess) return fail(e, GNNVC_ERR_DEVICE, "parameter upload failed");
     struct Ctx { uint32_t n, k, m; const float *W; } ctx{n, k, m, dW.p};
-    rc = run_host_op(e, (size_t)n * k, in, (size_t)n * m, out, false,
-                     [](gnnvc_engine *en, const float *di, float *dout, void *c) {
-                         auto *x = (Ctx *)c;
-                         return gnnvc::launch_linear(x->n, x->k, x->m, di, x->W, x->W + (size_t)x->k * x->m, dout, en->stream);
-                     }, &ctx);
-    dW.release();
-    return rc;
+    return run_host_op(e, (size_t)n * k, in, (size_t)n * m, out, false,
+                       [](gnnvc_engine *en, const float *di, float *dout, void *c) {
+                           auto *x = (Ctx *)c;
+                           return gnnvc::launch_linear(x->n, x->k, x->m, di, x->W, x->W + (size_t)x->k * x->m, dout, en->stream);
+                       }, &ctx);
 }
 
 int gnnvc_relu_forward(gnnvc_engine *e, size_t count, const float *in, float *out) {
@@ -2174,7 +2040,6 @@ int gnnvc_stream_sum(gnnvc_engine *e, const float *values, uint32_t streams, uin
     std::vector<float> host((size_t)streams * 16);
     if (h == hipSuccess) h = hipMemcpyAsync(host.data(), agg.p, host.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream);
     if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
-    slab.release(); agg.release(); meta.release(); off.release(); segsum.release(); segmap.release();
     if (h != hipSuccess) return fail(e, h == hipErrorOutOfMemory ? GNNVC_ERR_NOMEM : GNNVC_ERR_DEVICE, "stream sum: %s", hipGetErrorString(h));
     for (uint32_t i = 0; i < streams; ++i) sums[i] = host[(size_t)i * 16];
     return GNNVC_OK;
@@ -2198,20 +2063,16 @@ int gnnvc_sgemm(gnnvc_engine *e, int trans_a, int trans_b, uint32_t m, uint32_t 
     const size_t c_elems = (size_t)(m - 1) * ldc + n;
     DevBuf<float> dB;
     HIP_TRY(e, dB.reserve(b_elems + 1));
-    if (b_elems && hipMemcpy(dB.p, B, b_elems * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        dB.release();
+    if (b_elems && hipMemcpy(dB.p, B, b_elems * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(e, GNNVC_ERR_DEVICE, "B upload failed");
-    }
     struct Ctx { int ta, tb; uint32_t m, n, k, lda, ldb, ldc; float beta; const float *B; } ctx{
         trans_a, trans_b, m, n, k, lda, ldb, ldc, beta, dB.p};
-    rc = run_host_op(e, a_elems, A, c_elems, C, true,
-                     [](gnnvc_engine *en, const float *dA, float *dC, void *c) {
-                         auto *x = (Ctx *)c;
-                         return gnnvc::launch_sgemm(x->ta, x->tb, x->m, x->n, x->k, dA, x->lda, x->B, x->ldb,
-                                                    x->beta, dC, x->ldc, en->stream);
-                     }, &ctx);
-    dB.release();
-    return rc;
+    return run_host_op(e, a_elems, A, c_elems, C, true,
+                       [](gnnvc_engine *en, const float *dA, float *dC, void *c) {
+                           auto *x = (Ctx *)c;
+                           return gnnvc::launch_sgemm(x->ta, x->tb, x->m, x->n, x->k, dA, x->lda, x->B, x->ldb,
+                                                      x->beta, dC, x->ldc, en->stream);
+                       }, &ctx);
 }
 
 }  // extern "C"

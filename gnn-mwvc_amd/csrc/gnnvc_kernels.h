@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "gnnvc_device_mem.h"
+
 namespace gnnvc {
 
 // Device view of what the forward reads from reduction_graph
@@ -83,8 +85,8 @@ struct SortedOrder {
 // sink->stream is bracketed by two HIP events (recs[0 .. used): name = the kernel as written at the launch site).
 struct KernelTraceSink {
     struct Rec {
-        const char *name;
-        hipEvent_t a, b;
+        const char *name = nullptr;
+        Event a, b;
     };
     hipStream_t stream = nullptr;
     std::vector<Rec> recs;

@@ -67,9 +67,9 @@ struct KernelTimer {
         KernelTraceSink *k = t_sink;
         if (!k || k->stream != s) return;
         if (k->used == k->recs.size()) {
-            KernelTraceSink::Rec fresh{name, nullptr, nullptr};
-            if (hipEventCreate(&fresh.a) != hipSuccess || hipEventCreate(&fresh.b) != hipSuccess) return;
-            k->recs.push_back(fresh);
+            KernelTraceSink::Rec fresh;
+            if (fresh.a.create() != hipSuccess || fresh.b.create() != hipSuccess) return;
+            k->recs.push_back(std::move(fresh));
         }
         rec = &k->recs[k->used++];
         rec->name = name;
@@ -5003,9 +5003,9 @@ __global__ void k_nothing() {}
 
 hipError_t streams_run_side_by_side(hipStream_t a, hipStream_t b, bool *yes) {
     *yes = false;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    hipError_t rc = hipEventCreateWithFlags(&ea, hipEventDisableTiming);
-    if (rc == hipSuccess) rc = hipEventCreateWithFlags(&eb, hipEventDisableTiming);
+    Event ea, eb;
+    hipError_t rc = ea.create(hipEventDisableTiming);
+    if (rc == hipSuccess) rc = eb.create(hipEventDisableTiming);
     if (rc == hipSuccess) {
         hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, a, 30000ull);
         rc = hipEventRecord(ea, a);
@@ -5019,8 +5019,6 @@ hipError_t streams_run_side_by_side(hipStream_t a, hipStream_t b, bool *yes) {
         *yes = hipEventQuery(ea) == hipErrorNotReady;
         rc = hipEventSynchronize(ea);
     }
-    if (ea) (void)hipEventDestroy(ea);
-    if (eb) (void)hipEventDestroy(eb);
     (void)hipGetLastError();   // (hipErrorNotReady is sticky for hipGetLastError)
     return rc;
 }
@@ -5772,10 +5770,17 @@ hipError_t launch_zero_pad_row(float *buf, uint32_t n, uint32_t width, hipStream
 
 }  // namespace gnnvc
 
-#if GNNVC_PHASE_PROBE
+// Debugging aid, not part of include/gnnvc.h.  (nullptr, gnnvc::kProbeLiveObjects): the number of device / page-locked
+// allocations, events and streams this library holds in the process (gnnvc_device_mem.h; tests/test_gpu_lifetime.py).  Any other
+// kind: where the phase probe of a -DGNNVC_PHASE_PROBE=1 build writes its clock stamps (-3 in an ordinary build).
 extern "C" int gnnvc_debug_probe(void *buf, int kind) {
+    if (kind == gnnvc::kProbeLiveObjects) return (int)gnnvc::g_live_objects.load();
+#if GNNVC_PHASE_PROBE
     if (hipMemcpyToSymbol(HIP_SYMBOL(gnnvc::gnnvc_probe_buf), &buf, sizeof buf) != hipSuccess) return -1;
     if (hipMemcpyToSymbol(HIP_SYMBOL(gnnvc::gnnvc_probe_kind), &kind, sizeof kind) != hipSuccess) return -2;
     return 0;
-}
+#else
+    (void)buf;
+    return -3;
 #endif
+}

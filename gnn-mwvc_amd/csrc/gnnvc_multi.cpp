@@ -27,7 +27,9 @@
 #include <vector>
 
 #include "../../include/gnnvc.h"
+#include "gnnvc_device_mem.h"
 #include "gnnvc_multi.h"
+#include "gnnvc_options.h"
 
 namespace gnnvc {
 
@@ -35,26 +37,6 @@ namespace {
 
 constexpr int kMaxPieces = 8;
 constexpr uint32_t kExcWordsPerEntry = 4;   // {row - row_lo, column, value bits, 0}
-
-template <class T>
-struct Buf {
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t count) {   // (the caller has made the buffer's device current)
-        if (count <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t rc = hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T));
-        if (rc == hipSuccess) cap = count;
-        return rc;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 // how the rows of one exchanged stage travel: the `kp` densest columns (mask) + an exception list of room `cap` per piece
 struct Packing {
@@ -67,20 +49,19 @@ struct Part {
     int index = 0, device = 0;
     gnnvc_engine *eng = nullptr;
     hipStream_t stream = nullptr;   // the ENGINE'S OWN stream (its side queue was probed against it, gnnvc_create)
-    hipStream_t copy = nullptr;     // pushes: under the next piece's kernels
+    Stream copy;                    // pushes: under the next piece's kernels
     uint32_t lo = 0, hi = 0;
     uint64_t nnz = 0;
     int pieces = 1;
     uint32_t cut[kMaxPieces + 1] = {0};   // piece k = rows [cut[k], cut[k + 1])
-    Buf<uint32_t> rowptr, col, w, nw;
-    Buf<float> x, h[2], scores, logits;
-    Buf<float> send[2], recv[2];          // packed pieces of stage s: mine / my peers'
-    Buf<uint32_t> flag;                   // [2]: gnnvc_pack_rows' flags of stage 0 / 1
-    Buf<uint32_t> flag_host;              // (page-locked) their copy for the host
-    uint32_t *flag_pin = nullptr;
-    hipEvent_t packed[2][kMaxPieces] = {{nullptr}};   // piece k of stage s is computed (and packed): on `stream`
-    hipEvent_t pushed[2][kMaxPieces] = {{nullptr}};   // ... and has reached every peer: on `copy`
-    hipEvent_t t0 = nullptr, t1 = nullptr;            // this part's span of the last forward (timing enabled)
+    DevBuf<uint32_t> rowptr, col, w, nw;
+    DevBuf<float> x, h[2], scores, logits;
+    DevBuf<float> send[2], recv[2];       // packed pieces of stage s: mine / my peers'
+    DevBuf<uint32_t> flag;                // [2]: gnnvc_pack_rows' flags of stage 0 / 1
+    PinBuf<uint32_t> flag_pin;            // (page-locked) their copy for the host
+    Event packed[2][kMaxPieces];          // piece k of stage s is computed (and packed): on `stream`
+    Event pushed[2][kMaxPieces];          // ... and has reached every peer: on `copy`
+    Event t0, t1;                         // this part's span of the last forward (timing enabled)
     uint64_t counts[2][16] = {{0}};                   // first forward on a graph: non-zeros per column of my rows of stage s
     int rc = GNNVC_OK;                                // of the job at hand
     std::string err;
@@ -100,16 +81,18 @@ struct MultiState {
     int stages = 0;
     double last_ms = 0.0;
     bool peer_stores = true;     // every pair of distinct devices can store into each other's memory
-    // options (gnnvc_set_option on the front handle, keys "multi_*")
-    int opt_pieces = 0;          // pieces per part and stage: 0 = by the number of parts
-    int opt_pack = 1;            // 0 = full rows always
-    int opt_push = 1;            // 0 = hipMemcpyPeerAsync per peer instead of the push kernel
-    int opt_only_part = -1;      // >= 0: a forward runs THIS part's share only (timing rehearsal on one device; results are not complete)
-    int opt_poison = 0;          // "poison_features": a forward starts by filling every part's feature buffers with NaN bit patterns (tests, fuzz)
-    int opt_audit_repair = 0;    // "audit_repair" (also set on every part): a part's mismatch repaired is no failure of the forward
+    // options (gnnvc_set_option on the front handle: keys "multi_*", and what the front hands on — kMultiRows)
+    struct Opts {
+        int pieces = 0;          // pieces per part and stage: 0 = by the number of parts
+        int pack = 1;            // 0 = full rows always
+        int push = 1;            // 0 = hipMemcpyPeerAsync per peer instead of the push kernel
+        int only_part = -1;      // >= 0: a forward runs THIS part's share only (timing rehearsal on one device; results are not complete)
+        int poison = 0;          // "poison_features": a forward starts by filling every part's feature buffers with NaN bit patterns (tests, fuzz)
+        int audit_repair = 0;    // "audit_repair" (also set on every part): a part's mismatch repaired is no failure of the forward
+        int announce = -1;       // a part announces a 16-wide stage's complete input (compact table over its rows): -1 = up to 4 parts, 0 / 1
+    } opt;
     bool parts_audit = false;    // the parts' "audit_period" is 1 (this forward is audited) — the handle counts the calls
     int audit_last_part = -1;    // the first failing part of the last forward whose audit failed
-    int opt_announce = -1;       // a part announces a 16-wide stage's complete input (compact table over its rows): -1 = up to 4 parts, 0 / 1
     Packing pk[2];
     std::vector<uint64_t> region_words[2];   // [r * kMaxPieces + k]: words of part r's piece k of stage s (dense + list)
     std::vector<uint64_t> region_pre[2];     // prefix over (r, k) in that order
@@ -186,11 +169,21 @@ void fail_job(MultiState *m) {
 int pieces_for(const MultiState *m) {
     const int P = (int)m->parts.size();
     if (P <= 1) return 1;
-    if (m->opt_pieces > 0) return std::min(m->opt_pieces, kMaxPieces);
+    if (m->opt.pieces > 0) return std::min(m->opt.pieces, kMaxPieces);
     // up to 4 parts a part's rows are many enough for the per-rank plans (LDS table over the slice, announced compact table:
     // whole-range calls — measured per-rank compute, metric graph: P = 4 2.02 ms on the plans against 2.88 in plain pieces);
     // beyond, four plain pieces whose pushes run under the next piece's kernels (P = 8: 1.48 plain against 1.67 on the plans)
     return P <= 4 ? 1 : 4;
+}
+
+// piece k of a part = rows [cut[k], cut[k + 1]): K nearly equal ranges of its rows, cut at multiples of 64 rows
+void cut_pieces(Part &p, int K) {
+    p.pieces = K;
+    for (int k = 0; k <= K; ++k) {
+        const uint64_t at = p.lo + (uint64_t)(p.hi - p.lo) * k / K;
+        p.cut[k] = k == K ? p.hi : (uint32_t)std::min<uint64_t>(p.hi, std::max<uint64_t>(p.lo, at / 64u * 64u));
+    }
+    for (int k = 1; k < K; ++k) p.cut[k] = std::max(p.cut[k], p.cut[k - 1]);
 }
 
 // ---- the packing of one exchanged stage, from the non-zeros per column of ALL rows (every part computes the same choice)
@@ -273,7 +266,7 @@ int upload_part(MultiState *m, Part &p, std::string &err) {
     MTRY(p.scores.reserve(frows));
     MTRY(p.logits.reserve(frows));
     MTRY(p.flag.reserve(2));
-    if (!p.flag_pin) MTRY(hipHostMalloc(reinterpret_cast<void **>(&p.flag_pin), 4 * sizeof(uint32_t), hipHostMallocDefault));
+    MTRY(p.flag_pin.reserve(4));
     std::vector<uint32_t> local((size_t)rows + 1);
     for (uint32_t i = 0; i <= rows; ++i) local[i] = (uint32_t)(rp(p.lo + i) - first);
     MTRY(hipMemcpyAsync(p.rowptr.p, local.data(), ((size_t)rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p.stream));
@@ -312,14 +305,14 @@ int ship_piece(MultiState *m, Part &me, int s, int k, float *out, std::string &e
     const size_t P = m->parts.size();
     const Packing &pk = m->pk[s];
     const uint32_t r0 = me.cut[k], r1 = me.cut[k + 1], rows = r1 - r0;
-    const bool solo = m->opt_only_part >= 0;
+    const bool solo = m->opt.only_part >= 0;
     if (pk.on) {
         float *region = me.send[s].p + (m->region_pre[s][(size_t)me.index * kMaxPieces + k] - m->region_pre[s][(size_t)me.index * kMaxPieces]);
         uint32_t *exc = reinterpret_cast<uint32_t *>(region + (size_t)rows * pk.kp);
         PTRY(me, gnnvc_pack_rows(me.eng, out, 16, r0, r1, pk.mask, pk.kp, region, exc, pk.cap, me.flag.p + s), "gnnvc_pack_rows");
         MTRY(hipEventRecord(me.packed[s][k], me.stream));
         MTRY(hipStreamWaitEvent(me.copy, me.packed[s][k], 0));
-        if (m->opt_push && m->peer_stores) {
+        if (m->opt.push && m->peer_stores) {
             float *dst[64];
             uint32_t nd = 0;
             for (size_t q = 0; q < P; ++q)
@@ -349,8 +342,8 @@ int forward_part(MultiState *m, Part &me, std::string &err) {
     const uint32_t n = m->n;
     const size_t P = m->parts.size();
     const int dev0 = m->parts[0].device;
-    const bool solo = m->opt_only_part >= 0;
-    if (solo && m->opt_only_part != me.index) return GNNVC_OK;
+    const bool solo = m->opt.only_part >= 0;
+    if (solo && m->opt.only_part != me.index) return GNNVC_OK;
     MTRY(hipSetDevice(me.device));
     MTRY(hipEventRecord(me.t0, me.stream));
     MTRY(hipMemsetAsync(me.flag.p, 0, 2 * sizeof(uint32_t), me.stream));
@@ -377,7 +370,7 @@ int forward_part(MultiState *m, Part &me, std::string &err) {
                 if (nl) PTRY(me, gnnvc_unpack_pieces(me.eng, list, nl, pk.cap, 16, pk.mask, pk.kp, me.h[(s - 1) & 1].p), "gnnvc_unpack_pieces");
             }
         }
-        if (me.hi > me.lo && s >= 1 && me.pieces == 1 && (m->opt_announce < 0 ? P <= 4 : m->opt_announce != 0))
+        if (me.hi > me.lo && s >= 1 && me.pieces == 1 && (m->opt.announce < 0 ? P <= 4 : m->opt.announce != 0))
             PTRY(me, gnnvc_stage_input_ready(me.eng, s, in, me.lo, me.hi), "gnnvc_stage_input_ready");
         const bool choose = s < 2 && P > 1 && !m->pk[s].known;
         for (int k = 0; k < me.pieces; ++k) {
@@ -407,7 +400,7 @@ int forward_part(MultiState *m, Part &me, std::string &err) {
                     for (int c = 0; c < 16; ++c) tot[c] += p.counts[s][c];
                     total_pieces += p.pieces;
                 }
-                m->pk[s] = choose_packing(tot, n, total_pieces, m->opt_pack != 0);
+                m->pk[s] = choose_packing(tot, n, total_pieces, m->opt.pack != 0);
                 layout_stage(m, s);
             }
             if (!barrier(m, (int)P)) {
@@ -434,7 +427,7 @@ int forward_part(MultiState *m, Part &me, std::string &err) {
                 MTRY(hipMemcpyPeerAsync(m->fw_logits + me.lo, dev0, me.logits.p + me.lo, me.device, rows * sizeof(float), me.stream));
         }
     }
-    MTRY(hipMemcpyAsync(me.flag_pin, me.flag.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, me.stream));
+    MTRY(hipMemcpyAsync(me.flag_pin.p, me.flag.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, me.stream));
     for (int s = 0; s < 2; ++s)   // (the span ends when the last push has landed; an event never recorded waits for nothing)
         MTRY(hipStreamWaitEvent(me.stream, me.pushed[s][std::max(me.pieces - 1, 0)], 0));
     MTRY(hipEventRecord(me.t1, me.stream));
@@ -468,7 +461,7 @@ void worker(MultiState *m, Part *p) {
         if (p->rc != GNNVC_OK) fail_job(m);
         if (job == kForward) {
             drain_part(*p);
-            if (p->rc == GNNVC_OK && p->t0 && p->t1 && (m->opt_only_part < 0 || m->opt_only_part == p->index))
+            if (p->rc == GNNVC_OK && p->t0 && p->t1 && (m->opt.only_part < 0 || m->opt.only_part == p->index))
                 if (hipEventElapsedTime(&p->span_ms, p->t0, p->t1) != hipSuccess) p->span_ms = 0.0f;
         }
         {
@@ -558,14 +551,14 @@ int multi_create(MultiState **out, const char *model_text, size_t len, const int
         void *own = nullptr;
         if (h == hipSuccess && gnnvc_get_stream(p.eng, &own) != GNNVC_OK) h = hipErrorInvalidValue;
         p.stream = reinterpret_cast<hipStream_t>(own);
-        if (h == hipSuccess) h = hipStreamCreateWithFlags(&p.copy, hipStreamNonBlocking);
+        if (h == hipSuccess) h = p.copy.create(hipStreamNonBlocking);
         for (int s = 0; s < 2 && h == hipSuccess; ++s)
             for (int k = 0; k < kMaxPieces && h == hipSuccess; ++k) {
-                h = hipEventCreateWithFlags(&p.packed[s][k], hipEventDisableTiming);
-                if (h == hipSuccess) h = hipEventCreateWithFlags(&p.pushed[s][k], hipEventDisableTiming);
+                h = p.packed[s][k].create(hipEventDisableTiming);
+                if (h == hipSuccess) h = p.pushed[s][k].create(hipEventDisableTiming);
             }
-        if (h == hipSuccess) h = hipEventCreate(&p.t0);
-        if (h == hipSuccess) h = hipEventCreate(&p.t1);
+        if (h == hipSuccess) h = p.t0.create();
+        if (h == hipSuccess) h = p.t1.create();
         if (h != hipSuccess) {
             rc = hip_fail(err, h, "stream / event creation");
             break;
@@ -621,24 +614,9 @@ void multi_destroy(MultiState *m) {
         (void)hipSetDevice(p.device);
         if (p.copy) (void)hipStreamSynchronize(p.copy);
         if (p.stream) (void)hipStreamSynchronize(p.stream);
-        p.rowptr.release(); p.col.release(); p.w.release(); p.nw.release();
-        p.x.release(); p.h[0].release(); p.h[1].release(); p.scores.release(); p.logits.release();
-        for (auto &b : p.send) b.release();
-        for (auto &b : p.recv) b.release();
-        p.flag.release();
-        if (p.flag_pin) (void)hipHostFree(p.flag_pin);
-        for (auto &row : p.packed)
-            for (auto &ev : row)
-                if (ev) (void)hipEventDestroy(ev);
-        for (auto &row : p.pushed)
-            for (auto &ev : row)
-                if (ev) (void)hipEventDestroy(ev);
-        if (p.t0) (void)hipEventDestroy(p.t0);
-        if (p.t1) (void)hipEventDestroy(p.t1);
-        if (p.copy) (void)hipStreamDestroy(p.copy);
         if (p.eng) gnnvc_destroy(p.eng);   // (owns p.stream)
     }
-    delete m;
+    delete m;   // (the parts' buffers, events and copy streams: gnnvc_device_mem.h)
 }
 
 int multi_devices(const MultiState *m) { return m ? (int)m->parts.size() : 0; }
@@ -684,7 +662,7 @@ bool multi_get_info(MultiState *m, const char *key, long *value) {
         (void)hipSetDevice(m->parts[0].device);
         *value = (long)most;
     }
-    else if (k == "multi_peer_stores") *value = m->peer_stores && m->opt_push ? 1 : 0;
+    else if (k == "multi_peer_stores") *value = m->peer_stores && m->opt.push ? 1 : 0;
     else if (k.rfind("multi_part_span_us_", 0) == 0) {
         const int r = atoi(k.c_str() + 19);
         if (r < 0 || r >= (int)m->parts.size()) return false;
@@ -701,43 +679,49 @@ int multi_set_weight_scale(MultiState *m, float ws) {
     return GNNVC_OK;
 }
 
-int multi_set_option(MultiState *m, const char *key, long value) {
-    const std::string k(key);
-    if (k.rfind("multi_", 0) == 0) {   // the exchange's own options
-        if (k == "multi_pieces") m->opt_pieces = value < 0 ? 0 : (int)std::min<long>(value, kMaxPieces);
-        else if (k == "multi_pack") m->opt_pack = value != 0 ? 1 : 0;
-        else if (k == "multi_push") m->opt_push = value != 0 ? 1 : 0;
-        else if (k == "multi_only_part") m->opt_only_part = (value >= 0 && value < (long)m->parts.size()) ? (int)value : -1;
-        else if (k == "multi_announce") m->opt_announce = value < 0 ? -1 : (value != 0 ? 1 : 0);
-        else return GNNVC_ERR_INVALID;
-        if (k == "multi_pieces" || k == "multi_pack") {   // (they shape the pieces and the receive buffers: decided again on the next graph / forward)
-            m->pk[0] = m->pk[1] = Packing();
-            if (m->have_graph) {
-                const int K = pieces_for(m);
-                for (Part &p : m->parts) {
-                    p.pieces = K;
-                    for (int kk = 0; kk <= K; ++kk) {
-                        const uint64_t at = p.lo + (uint64_t)(p.hi - p.lo) * kk / K;
-                        p.cut[kk] = kk == K ? p.hi : (uint32_t)std::min<uint64_t>(p.hi, std::max<uint64_t>(p.lo, at / 64u * 64u));
-                    }
-                    for (int kk = 1; kk < K; ++kk) p.cut[kk] = std::max(p.cut[kk], p.cut[kk - 1]);
-                }
-            }
-        }
-        return GNNVC_OK;
-    }
-    if (k == "poison_features") {   // (the parts run stage by stage on THIS driver's buffers)
-        m->opt_poison = value != 0 ? 1 : 0;
-        return GNNVC_OK;
-    }
+// What a multi-device handle does with the keys it is handed (gnnvc_options.h has the engine's own table): write a member of
+// its own, and then
+enum MultiEffect : uint32_t {
+    kMxRepack = 1u << 0,   // the pieces and the receive buffers are shaped again: decided on the next graph / forward
+    kMxParts = 1u << 1,    // every part's engine gets the key too
+};
+using MultiRow = OptionRow<MultiState::Opts>;
+static const MultiRow kMultiRows[] = {
+    // the exchange's own options
+    {"multi_pieces", &MultiState::Opts::pieces, range(0, kMaxPieces), kMxRepack},
+    {"multi_pack", &MultiState::Opts::pack, kBool, kMxRepack},
+    {"multi_push", &MultiState::Opts::push, kBool, 0},
+    {"multi_only_part", &MultiState::Opts::only_part, range(-1, 64), 0},   // (and below the number of parts, multi_set_option)
+    {"multi_announce", &MultiState::Opts::announce, kTri, 0},
+    // handed on by the front engine
+    {"poison_features", &MultiState::Opts::poison, kBool, 0},   // (the parts run stage by stage on THIS driver's buffers)
     // (audit_period: the front handle counts the calls, multi_forward_device switches the parts; audit_quiet: the parts stay quiet;
     // audit_log: the front handle prints for every part)
-    if (k == "audit_period" || k == "audit_quiet" || k == "audit_log") return GNNVC_OK;
-    if (k == "audit_repair") m->opt_audit_repair = value != 0 ? 1 : 0;   // (and on every part, below)
-    for (Part &p : m->parts) {
-        int rc = gnnvc_set_option(p.eng, key, value);
-        if (rc) return rc;
+    {"audit_period", 0},
+    {"audit_quiet", 0},
+    {"audit_log", 0},
+    {"audit_repair", &MultiState::Opts::audit_repair, kBool, kMxParts},
+};
+
+int multi_set_option(MultiState *m, const char *key, long value) {
+    const MultiRow *r = find_option(kMultiRows, key);
+    if (!r && strncmp(key, "multi_", 6) == 0) return GNNVC_ERR_INVALID;
+    uint32_t fx = kMxParts;   // (any other key is an engine's)
+    if (r) {
+        r->store(m->opt, value);
+        if (m->opt.only_part >= (int)m->parts.size()) m->opt.only_part = -1;   // (no such part: off)
+        fx = r->fx;
     }
+    if (fx & kMxRepack) {
+        m->pk[0] = m->pk[1] = Packing();
+        if (m->have_graph)
+            for (Part &p : m->parts) cut_pieces(p, pieces_for(m));
+    }
+    if (fx & kMxParts)
+        for (Part &p : m->parts) {
+            int rc = gnnvc_set_option(p.eng, key, value);
+            if (rc) return rc;
+        }
     return GNNVC_OK;
 }
 
@@ -791,12 +775,7 @@ int multi_upload(MultiState *m, uint32_t n, const uint64_t *rowptr64, const uint
             return GNNVC_ERR_INVALID;
         }
         p.nnz = b - a;
-        p.pieces = K;
-        for (int k = 0; k <= K; ++k) {
-            const uint64_t at = p.lo + (uint64_t)(p.hi - p.lo) * k / K;
-            p.cut[k] = k == K ? p.hi : (uint32_t)std::min<uint64_t>(p.hi, std::max<uint64_t>(p.lo, at / 64u * 64u));
-        }
-        for (int k = 1; k < K; ++k) p.cut[k] = std::max(p.cut[k], p.cut[k - 1]);
+        cut_pieces(p, K);
     }
     m->up_rp64 = rowptr64;
     m->up_rp32 = rowptr32;
@@ -835,7 +814,7 @@ int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float
         return GNNVC_ERR_STATE;
     }
     if (m->n == 0) return GNNVC_OK;
-    if (m->opt_only_part >= 0 && m->parts.size() > 1 && !(m->pk[0].known && m->pk[1].known)) {
+    if (m->opt.only_part >= 0 && m->parts.size() > 1 && !(m->pk[0].known && m->pk[1].known)) {
         err = "multi_only_part needs a complete forward on this graph first";
         return GNNVC_ERR_STATE;
     }
@@ -860,7 +839,7 @@ int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float
     // Two attempts were one too few: a stage-0 overflow hands stage 1 a damaged input in the first attempt, so stage 1's own overflow
     // only shows in the second — fuzz_multi.py case 232 returned that attempt's lossy rows.)
     for (int attempt = 0; attempt < 3; ++attempt) {
-        if (m->opt_poison && m->opt_only_part < 0) {   // (tests, fuzz; before any part starts: peers write into these buffers on their own streams)
+        if (m->opt.poison && m->opt.only_part < 0) {   // (tests, fuzz; before any part starts: peers write into these buffers on their own streams)
             for (Part &p : m->parts) {
                 if (hipSetDevice(p.device) != hipSuccess) continue;
                 for (int b = 0; b < 2; ++b)
@@ -873,11 +852,11 @@ int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float
         if (rc != GNNVC_OK) break;
         // lossless or repeated: a pack step raises its flag when a non-zero fits neither the dense columns nor the list
         bool again = false;
-        if (m->opt_only_part < 0)
+        if (m->opt.only_part < 0)
             for (int s = 0; s < 2; ++s) {
                 if (!m->pk[s].on) continue;
                 bool over = false;
-                for (const Part &p : m->parts) over |= p.flag_pin && p.flag_pin[s] != 0;
+                for (const Part &p : m->parts) over |= p.flag_pin.p && p.flag_pin.p[s] != 0;
                 if (over) {   // full rows for this stage from now on (the lists were sized from this graph's own counts: it never fit)
                     m->pk[s].on = false;
                     layout_stage(m, s);
@@ -892,7 +871,7 @@ int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float
             long now = 0;
             if (gnnvc_get_info(m->parts[r].eng, "audit_failures", &now) != GNNVC_OK || now == failures[r]) continue;
             m->audit_last_part = (int)r;
-            if (!m->opt_audit_repair) {
+            if (!m->opt.audit_repair) {
                 err = "part " + std::to_string(r) + ": " + gnnvc_last_error(m->parts[r].eng);
                 rc = GNNVC_ERR_AUDIT;
             }

@@ -13,7 +13,7 @@ namespace gnnvc_eng {
 // hub mode: every long row).  Their neighbour values go through a column-major slab, one stream per (row, feature
 // column), laid out here on the host — heaviest row first, so the longest streams start first.
 int find_giant(gnnvc_engine *e) {
-    uint32_t gt = e->opt_giant_thresh ? std::max(e->opt_giant_thresh, e->long_thresh) : 0xFFFFFFFFu;
+    uint32_t gt = e->opt.giant_thresh ? std::max(e->opt.giant_thresh, e->long_thresh) : 0xFFFFFFFFu;
     if (gt == 0xFFFFFFFFu || e->n_long == 0) return GNNVC_OK;
     HIP_TRY(e, e->gi_meta.reserve((size_t)e->n_long + 1));
     HIP_TRY(e, gnnvc::find_giant_rows(e->g, e->long_list.p, e->n_long, gt, e->gi_meta.p, e->long_count.p, e->stream));
@@ -46,8 +46,8 @@ int find_giant(gnnvc_engine *e) {
     // anyway (R-MAT-22: 0.32 ms of walk inside a 1.2 ms stage) the extra kernels of the high-priority stream only take
     // slots from the tile kernel: 2.98 -> 3.16 ms.  Auto: on when the walk exceeds half of nnz / 50 G entries per second.
     e->giant_walk_bound = (double)meta[0].z * 2.0e-9 > 0.5 * (double)e->g.nnz / 50.0e9;
-    bool segments = e->opt_giant_segments > 0;
-    if (e->opt_giant_segments < 0) segments = e->giant_walk_bound;
+    bool segments = e->opt.giant_segments > 0;
+    if (e->opt.giant_segments < 0) segments = e->giant_walk_bound;
     if (segments && e->gi_maxseg > 1 && (uint64_t)cnt * 16 * e->gi_maxseg < (1ull << 31)) {
         HIP_TRY(e, e->gi_segsum.reserve((size_t)cnt * 16 * e->gi_maxseg));
         HIP_TRY(e, e->gi_segmap.reserve((size_t)cnt * 16 * e->gi_maxseg));
@@ -87,16 +87,16 @@ int classify_hand_off(gnnvc_engine *e, const GraphDev &cand, uint32_t &bad) {
     pre.hi = ghi;
     if (classes) {
         a.cuts = pre.cuts = cand.nnz && ghi - glo >= 4096;
-        if (e->opt_sorted != 0 && cand.nnz) {
+        if (e->opt.sorted != 0 && cand.nnz) {
             a.waste = pre.waste = true;
-            a.waste_thresh = pre.waste_thresh = e->opt_long_thresh ? e->opt_long_thresh : 0xFFFFFFFFu;
+            a.waste_thresh = pre.waste_thresh = e->opt.long_thresh ? e->opt.long_thresh : 0xFFFFFFFFu;
             a.heavy_from = pre.heavy_from =
                 (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, std::max<uint64_t>(1, 4 * cand.nnz / std::max<uint32_t>(ghi - glo, 1)));
         }
-        if (e->opt_long_thresh) {
+        if (e->opt.long_thresh) {
             HIP_TRY(e, e->long_list.reserve(ghi - glo));
             a.longs = pre.longs = true;
-            a.long_thresh = pre.long_thresh = e->opt_long_auto ? 256u : e->opt_long_thresh;
+            a.long_thresh = pre.long_thresh = e->opt.long_auto ? 256u : e->opt.long_thresh;
             a.long_list = e->long_list.p;
         }
     }
@@ -152,8 +152,8 @@ int find_long(gnnvc_engine *e) {
         for (int k = 0; k < 8; ++k) mx = std::max(mx, cut[k + 1] - cut[k]);
         e->interleave = (double)mx > 1.25 * (double)g.nnz / 8.0;
     }
-    const uint32_t base_thresh = e->opt_long_thresh ? e->opt_long_thresh : 0xFFFFFFFFu;
-    if (e->opt_sorted != 0 && g.nnz) {
+    const uint32_t base_thresh = e->opt.long_thresh ? e->opt.long_thresh : 0xFFFFFFFFu;
+    if (e->opt.sorted != 0 && g.nnz) {
         // lockstep cost of natural 64-row tiles (64 x sum of per-tile maxima) against the useful work
         HIP_TRY(e, e->srt_sum.reserve(2));
         const uint32_t heavy_from = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, std::max<uint64_t>(1, 4 * g.nnz / std::max<uint32_t>(ghi - glo, 1)));
@@ -178,14 +178,14 @@ int find_long(gnnvc_engine *e) {
         // separates the families (fuzz_large.py, 130 graphs): the share of entries in non-long rows of at least 4 x the mean degree —
         // at most 0.05 there, 0.16 and more on power-law and R-MAT graphs (sorted tiles 1.1 - 3 x faster on those).
         e->srt_tail = (double)sums[1] / (double)g.nnz;
-        e->sorted_wanted = e->opt_sorted > 0 ||
-                           (e->srt_waste >= 2.0 && g.nnz >= e->opt_sorted_min_nnz && mean_tile_max >= 24.0 && e->srt_tail >= 0.10);
+        e->sorted_wanted = e->opt.sorted > 0 ||
+                           (e->srt_waste >= 2.0 && g.nnz >= e->opt.sorted_min_nnz && mean_tile_max >= 24.0 && e->srt_tail >= 0.10);
     }
-    if (!e->opt_long_thresh) return GNNVC_OK;
+    if (!e->opt.long_thresh) return GNNVC_OK;
     // One list at the base threshold serves every stage.  With degree-sorted tiles the 16-wide
     // tile kernel copes with longer rows, so those stages send only rows >= thresh_f16 long
     // (the others return at once from the long kernel and sit in the sorted tile list instead).
-    uint32_t thresh = e->opt_long_thresh;
+    uint32_t thresh = e->opt.long_thresh;
     e->thresh_f16 = 0xFFFFFFFFu;
     HIP_TRY(e, e->long_list.reserve(ghi - glo));
     HIP_TRY(e, e->long_count.reserve(4));
@@ -193,7 +193,7 @@ int find_long(gnnvc_engine *e) {
     uint32_t found[4] = {0, 0, 0, 0};   // {rows, -, their entries (64 bits)}
     e->long_entries = 0;
     bool few_long = false;
-    if (e->opt_long_auto) {
+    if (e->opt.long_auto) {
         // A row of d entries holds its tile for d / 3 gather trips (~1.2 us each): with only a few thousand rows above 256 the
         // graph's stages are as long as those tiles (power-law 1 M: 1.16 -> 1.03 ms with the threshold at 256), so they get
         // workgroups of their own; where a hundred thousand rows sit there (R-MAT-22: 110 K) a workgroup each costs more than
@@ -211,7 +211,7 @@ int find_long(gnnvc_engine *e) {
         if (few_long) thresh = 256u;
     }
     if (!few_long) {
-        if (!e->opt_long_auto && have_pre && pre.longs && pre.long_thresh == thresh) {
+        if (!e->opt.long_auto && have_pre && pre.longs && pre.long_thresh == thresh) {
             for (int k = 0; k < 4; ++k) found[k] = pre.found[k];
         } else {
             HIP_TRY(e, gnnvc::find_long_rows(g, thresh, e->long_list.p, e->long_count.p, e->stream));
@@ -229,8 +229,8 @@ int find_long(gnnvc_engine *e) {
     e->n_long = cnt;
     e->long_thresh = thresh;
     // (never above the giant threshold: the rows from there on have their own kernels in every stage)
-    const uint32_t gt = e->opt_giant_thresh ? std::max(e->opt_giant_thresh, thresh) : 0xFFFFFFFFu;
-    e->thresh_f16 = (e->sorted_wanted && !few_long) ? std::max(thresh, std::min(e->opt_sorted_long_thresh, gt)) : thresh;
+    const uint32_t gt = e->opt.giant_thresh ? std::max(e->opt.giant_thresh, thresh) : 0xFFFFFFFFu;
+    e->thresh_f16 = (e->sorted_wanted && !few_long) ? std::max(thresh, std::min(e->opt.sorted_long_thresh, gt)) : thresh;
     return find_giant(e);
 }
 
@@ -305,17 +305,17 @@ int ensure_sorted(gnnvc_engine *e, uint32_t lo, uint32_t hi) {
 // Column-blocked index of the current graph (stage 0 only).  Not used when the
 // model is not fused, the graph is small, or a row's block ids are not monotone.
 int build_blocked_impl(gnnvc_engine *e) {
-    e->blocked_ready = false;
-    e->blocked_tried = true;
+    e->pg.blocked_ready = false;
+    e->pg.blocked_tried = true;
     const GraphDev &g = e->g;
-    if (!e->opt_blocked || e->stages.empty() || e->stages[0].f != 1 || e->stages[0].variant != 0) return GNNVC_OK;
+    if (!e->opt.blocked || e->stages.empty() || e->stages[0].f != 1 || e->stages[0].variant != 0) return GNNVC_OK;
     if (g.sliced()) return GNNVC_OK;   // (the per-graph plans index whole graphs)
-    if (g.n < e->opt_blocked_min_n || g.nnz == 0) return GNNVC_OK;
-    if (e->opt_blocked_min_n >= (1u << 20) && g.nnz < (uint64_t)g.n * 10) return GNNVC_OK;   // (as for the LDS-table plan: too few entries per row)
+    if (g.n < e->opt.blocked_min_n || g.nnz == 0) return GNNVC_OK;
+    if (e->opt.blocked_min_n >= (1u << 20) && g.nnz < (uint64_t)g.n * 10) return GNNVC_OK;   // (as for the LDS-table plan: too few entries per row)
     // skewed graphs gather mostly from a few hot (hub) entries of x that stay cached anyway, and
     // the per-row accumulate passes run in lockstep to each wave's largest count: measured slower
-    if (e->sorted_wanted && e->opt_blocked < 2) return GNNVC_OK;
-    const uint32_t wb = e->opt_block_cols ? e->opt_block_cols : (512u << 10);  // 2 MiB of x per block
+    if (e->sorted_wanted && e->opt.blocked < 2) return GNNVC_OK;
+    const uint32_t wb = e->opt.block_cols ? e->opt.block_cols : (512u << 10);  // 2 MiB of x per block
     const uint32_t nb = (g.n + wb - 1) / wb;
     if (nb < 2 || nb > 4096) return GNNVC_OK;
     const size_t elems = (size_t)nb * g.n + 1;
@@ -333,7 +333,7 @@ int build_blocked_impl(gnnvc_engine *e) {
     if (bad) return GNNVC_OK;  // rows not block-monotone: the blocked order would differ from CSR order
     e->blk_count = nb;
     e->blk_cols = wb;
-    e->blocked_ready = true;
+    e->pg.blocked_ready = true;
     return GNNVC_OK;
 }
 
@@ -443,31 +443,31 @@ int layout_skewed_plan(gnnvc_engine *e, uint32_t class_thresh, uint32_t max_rows
 // not skewed; whether a given forward's input really is W / ws is checked on the device at every launch.
 // lt_begin: eligibility, geometry, buffers (on e->stream); leaves lt_pb.open set if there is a plan to build.
 int lt_begin(gnnvc_engine *e) {
-    e->lt_ready = false;
-    e->lt_tried = true;
+    e->pg.lt_ready = false;
+    e->pg.lt_tried = true;
     e->lt_mapped = false;
     gnnvc_engine::PlanBuild &pb = e->lt_pb;
     pb = gnnvc_engine::PlanBuild();
     const GraphDev &g = e->g;
-    if (!e->opt_lds_table || e->stages.empty() || e->stages[0].f != 1 || e->stages[0].variant != 0) return GNNVC_OK;
+    if (!e->opt.lds_table || e->stages.empty() || e->stages[0].f != 1 || e->stages[0].variant != 0) return GNNVC_OK;
     // The plan covers the rows this engine holds: the whole graph, or (round 3) the SLICE of one rank of a partitioned run —
     // the byte table is made from each forward's x (replicated on every rank), not from the vertex weights, so a slice has
     // everything the plan needs; the columns are always the whole graph's.
     const uint32_t base = g.lo(), end = g.hi(), held = end - base;
     if (e->empty_slice || held == 0) return GNNVC_OK;
-    if (g.n < e->opt_blocked_min_n || g.nnz == 0 || g.nnz >= (1ull << 31)) return GNNVC_OK;
+    if (g.n < e->opt.blocked_min_n || g.nnz == 0 || g.nnz >= (1ull << 31)) return GNNVC_OK;
     // (every chunk streams the whole byte table whatever the rows hold: below ~10 entries per row the gathering kernel is as fast —
     // 0.56 vs 0.50 ms per forward on an Erdős–Rényi graph of 1.1 M vertices and 8 entries per row)
-    if (e->opt_blocked_min_n >= (1u << 20) && g.nnz < (uint64_t)held * 10) return GNNVC_OK;
+    if (e->opt.blocked_min_n >= (1u << 20) && g.nnz < (uint64_t)held * 10) return GNNVC_OK;
     // Skewed graphs (sorted tiles wanted, or long rows present): the plan covers the rows below the giant-row threshold, dealt
     // from the degree-sorted list to slices of equal weight, over column blocks of equal entry mass (layout_skewed_plan); the
     // giant rows keep their kernels.  "lds_table" 2 forces the consecutive-row layout onto such a graph instead (tests).
     const bool skewed = e->sorted_wanted || e->n_long > 0;
     // (on a skewed graph most gathers of x go to hubs, which the L2s hold: the plan pays from 2 M vertices on — R-MAT-22 stage 0
     // 1.07 -> 0.86 ms, R-MAT-20 0.27 -> 0.34 ms; a lowered "blocked_min_n" — tests — lowers this bound too)
-    const uint32_t skewed_min_n = e->opt_blocked_min_n < (1u << 20) ? e->opt_blocked_min_n : e->opt_lds_skewed_min_n;
-    const bool mapped = skewed && e->opt_lds_table < 2 && e->opt_lds_skewed && g.n >= skewed_min_n && !g.sliced();   // (the skewed layout deals whole graphs)
-    if (skewed && !mapped && e->opt_lds_table < 2) return GNNVC_OK;   // long runs would serialise in one thread
+    const uint32_t skewed_min_n = e->opt.blocked_min_n < (1u << 20) ? e->opt.blocked_min_n : e->opt.lds_skewed_min_n;
+    const bool mapped = skewed && e->opt.lds_table < 2 && e->opt.lds_skewed && g.n >= skewed_min_n && !g.sliced();   // (the skewed layout deals whole graphs)
+    if (skewed && !mapped && e->opt.lds_table < 2) return GNNVC_OK;   // long runs would serialise in one thread
     // How wide a table entry has to be (round 4): the largest k = W(v) among the rows held here and the weight scale (the
     // original graph's largest weight, src/GNN_VC.cpp:272-278) decide between a byte, ten bits (three to a word) and sixteen bits
     // per vertex — and with it how many vertices a column block's 80 KiB of LDS hold.  Weights beyond 65 535: no table.  (One
@@ -481,13 +481,13 @@ int lt_begin(gnnvc_engine *e) {
         HIP_TRY(e, hipStreamSynchronize(e->stream));
         const uint32_t wmax = e->pin_info.p[13];
         const double scale = (e->ws >= 1.0f && e->ws < 4.0e9f) ? (double)e->ws : 0.0;
-        bits = e->opt_lt_bits ? (uint32_t)e->opt_lt_bits : gnnvc::lds_table_bits_for(std::max<uint32_t>(wmax, (uint32_t)scale));
+        bits = e->opt.lt_bits ? (uint32_t)e->opt.lt_bits : gnnvc::lds_table_bits_for(std::max<uint32_t>(wmax, (uint32_t)scale));
         if (bits == 0 || gnnvc::lds_table_bits_for(wmax) == 0 || gnnvc::lds_table_bits_for(wmax) > bits) return GNNVC_OK;
         if (mapped && bits != 8) return GNNVC_OK;
     }
     const uint32_t bc = gnnvc::lds_table_block(bits);
     uint32_t max_rows = gnnvc::lds_table_max_rows(bits);
-    if (e->opt_plan_chunk_rows) max_rows = std::min(max_rows, std::max(16u, e->opt_plan_chunk_rows / 16u * 16u));
+    if (e->opt.plan_chunk_rows) max_rows = std::min(max_rows, std::max(16u, e->opt.plan_chunk_rows / 16u * 16u));
     uint32_t nblocks = (g.n + bc - 1) / bc, chunks = 0, rows = 0, slice_rows = 0, slices = 0;
     uint64_t plan_nnz = g.nnz;
     if (mapped) {
@@ -497,7 +497,7 @@ int lt_begin(gnnvc_engine *e) {
         // long as x (4 N bytes) mostly sits in the L2s.  Beyond that (R-MAT-24: 67 MB, k_long_f1 at 34 G entries/s) the plan is
         // the better place for them: forward 13.5 -> 12.8 ms.  "lds_table_skewed_rows" overrides.
         const uint32_t below_giant = e->n_giant ? e->giant_thresh : 16384u;
-        const uint32_t want = e->opt_lds_skewed_rows ? e->opt_lds_skewed_rows : ((uint64_t)g.n * 4 > (32ull << 20) ? below_giant : 2048u);
+        const uint32_t want = e->opt.lds_skewed_rows ? e->opt.lds_skewed_rows : ((uint64_t)g.n * 4 > (32ull << 20) ? below_giant : 2048u);
         // (the rows that stay outside are the long-row kernels': with no long-row list — no row reaches its threshold, or the list
         // is switched off — there is nobody to sum them, so the plan takes every row.  Found by fuzz_plans.py case 22174 in round 4:
         // "long_row_threshold" 0 with "lds_table_skewed_rows" 64 left the rows of 64 entries and more unwritten in every forward
@@ -519,10 +519,10 @@ int lt_begin(gnnvc_engine *e) {
         if (nblocks > 4096) return GNNVC_OK;
         // chunks: a multiple of the 256 CUs, each within the LDS budget; a chunk = 16 slices of rows (one per wave).  Every chunk
         // streams the whole byte table once, so a range of FEW rows (a rank's slice at 8 ranks: 64 full chunks) is not cut finer
-        // than the CUs need to be busy at half a chunk's rows each — opt_lt_min_chunks — instead of a full multiple of 256.
+        // than the CUs need to be busy at half a chunk's rows each — opt.lt_min_chunks — instead of a full multiple of 256.
         chunks = (held + max_rows - 1) / max_rows;
         if (chunks >= 256u) chunks = (chunks + 255u) / 256u * 256u;
-        else chunks = std::max(chunks, std::min(e->opt_lt_min_chunks, (held + 255u) / 256u));
+        else chunks = std::max(chunks, std::min(e->opt.lt_min_chunks, (held + 255u) / 256u));
         rows = (held + chunks - 1) / chunks;
         rows = (rows + 15u) / 16u * 16u;
         chunks = (held + rows - 1) / rows;
@@ -623,7 +623,7 @@ int lt_finish(gnnvc_engine *e) {
     e->lt_blocks = pb.nblocks;
     e->lt_steps_total = (uint32_t)total;
     e->lt_mapped = pb.mapped;
-    e->lt_ready = true;
+    e->pg.lt_ready = true;
     return GNNVC_OK;
 }
 
@@ -645,10 +645,10 @@ int build_lds_table_impl(gnnvc_engine *e) {
 // stay with their own kernels beside the plan.
 // c4_begin: eligibility, geometry, buffers (on e->stream); leaves c4_pb.open set if there is a plan to build.
 int c4_begin(gnnvc_engine *e, uint32_t base, uint32_t end) {
-    e->c4_ready = false;
-    e->c4_tried = true;
-    e->c4_prepared_stage = -1;
-    for (bool &b : e->c4_seeded) b = false;
+    e->pg.c4_ready = false;
+    e->pg.c4_tried = true;
+    e->pg.c4_prepared_stage = -1;
+    for (bool &b : e->pg.c4_seeded) b = false;
     gnnvc_engine::PlanBuild &pb = e->c4_pb;
     pb = gnnvc_engine::PlanBuild();
     const GraphDev &g = e->g;
@@ -656,24 +656,24 @@ int c4_begin(gnnvc_engine *e, uint32_t base, uint32_t end) {
     if (base >= end) return GNNVC_OK;
     if (base < g.lo() || end > g.hi()) return GNNVC_OK;   // rows this engine does not hold (a slice): no plan
     const uint32_t span = end - base;
-    if (!e->opt_compact || e->stages.size() < 2) return GNNVC_OK;
+    if (!e->opt.compact || e->stages.size() < 2) return GNNVC_OK;
     for (size_t st = 1; st < e->stages.size(); ++st)
         if (e->stages[st].f != 16) return GNNVC_OK;
     // (the 64-byte feature rows outgrow the L2s long before x does: the 16-wide stages' plan pays from a quarter of a million vertices on —
     // ER-1M 0.87 -> 0.58 ms per forward — the F = 1 plans from a million)
-    if (g.n < std::min(e->opt_blocked_min_n, e->opt_compact_min_n) || g.nnz == 0 || g.nnz >= (1ull << 31)) return GNNVC_OK;
+    if (g.n < std::min(e->opt.blocked_min_n, e->opt.compact_min_n) || g.nnz == 0 || g.nnz >= (1ull << 31)) return GNNVC_OK;
     // (... and the plan's fixed ~0.1 ms per forward needs entries to earn it back: ~25 ps per entry and stage)
-    if (e->opt_blocked_min_n >= (1u << 20) && g.nnz < e->opt_compact_min_nnz) return GNNVC_OK;
+    if (e->opt.blocked_min_n >= (1u << 20) && g.nnz < e->opt.compact_min_nnz) return GNNVC_OK;
     // (degree-uniform graphs only.  Rounds 2 - 3 also carried the plan in a layout for SKEWED graphs — rows dealt to slices of
     // equal weight, column blocks of equal entry mass, up to three tables per input, "compact_skewed" — which tied with the
     // gathering kernels at three passes and lost 2 x to the pruned adjacency: removed in round 4.)
     const bool skewed = e->sorted_wanted || e->n_long > 0;
-    if (skewed && e->opt_compact < 2) return GNNVC_OK;
+    if (skewed && e->opt.compact < 2) return GNNVC_OK;
     if (e->n_long > 0) return GNNVC_OK;   // (the long-row kernels write their rows themselves)
     // a chunk = 16 slices (one per wave of the workgroup that sums it); the plan is laid out per slice
     const uint32_t nsl = gnnvc::compact_slices();
     uint32_t max_rows = gnnvc::compact_max_rows();
-    if (e->opt_plan_chunk_rows) max_rows = std::min(max_rows, std::max(nsl, e->opt_plan_chunk_rows / nsl * nsl));
+    if (e->opt.plan_chunk_rows) max_rows = std::min(max_rows, std::max(nsl, e->opt.plan_chunk_rows / nsl * nsl));
     uint32_t plan_rows = span;          // rows the plan sums
     uint64_t range_nnz = g.nnz;         // ... and their entries
     // column blocks: wide enough that a slice brings about 160 entries per block (5/6 of a 192-entry step: room for
@@ -803,7 +803,7 @@ int c4_finish(gnnvc_engine *e) {
     e->c4_chunks = pb.chunks;
     e->c4_nslices = slices;
     e->c4_steps_total = (uint32_t)total;
-    e->c4_ready = true;
+    e->pg.c4_ready = true;
     return GNNVC_OK;
 }
 
@@ -847,14 +847,27 @@ gnnvc::LdsTablePlan lds_table_plan(const gnnvc_engine *e) {
 }
 
 int build_blocked(gnnvc_engine *e) {
-    return timed_build(e, [&] { return build_blocked_impl(e); }, e->opt_blocked && e->g.n >= e->opt_blocked_min_n && e->g.nnz != 0);
+    return timed_build(e, [&] { return build_blocked_impl(e); }, e->opt.blocked && e->g.n >= e->opt.blocked_min_n && e->g.nnz != 0);
 }
 int build_lds_table(gnnvc_engine *e) {
-    return timed_build(e, [&] { return build_lds_table_impl(e); }, e->opt_lds_table && e->g.n >= e->opt_blocked_min_n && e->g.nnz != 0);
+    return timed_build(e, [&] { return build_lds_table_impl(e); }, e->opt.lds_table && e->g.n >= e->opt.blocked_min_n && e->g.nnz != 0);
 }
 int build_compact(gnnvc_engine *e, uint32_t base, uint32_t end) {
     return timed_build(e, [&] { return build_compact_impl(e, base, end); },
-                       e->opt_compact && e->g.n >= std::min(e->opt_blocked_min_n, e->opt_compact_min_n) && e->g.nnz != 0);
+                       e->opt.compact && e->g.n >= std::min(e->opt.blocked_min_n, e->opt.compact_min_n) && e->g.nnz != 0);
+}
+
+// up to four candidates for the side queue, probed against the main stream in force: the first that runs beside it (beside),
+// else the last one made (a serialised side queue is slow, not wrong); the others are destroyed on the way out
+static int probe_side_queue(gnnvc_engine *e, gnnvc::Stream &pick, bool &beside, int &tried_n) {
+    gnnvc::Stream tried[4];
+    beside = false;
+    for (tried_n = 0; tried_n < 4 && !beside; ++tried_n) {
+        HIP_TRY(e, tried[tried_n].create(hipStreamNonBlocking));
+        HIP_TRY(e, gnnvc::streams_run_side_by_side(e->stream, tried[tried_n], &beside));
+    }
+    pick = std::move(tried[tried_n - 1]);
+    return GNNVC_OK;
 }
 
 // The engine's SIDE queue, made once per engine (gnnvc_create): what runs beside the main stream's kernels — the dense part of a
@@ -868,26 +881,13 @@ int build_compact(gnnvc_engine *e, uint32_t base, uint32_t end) {
 // stream costs ~10 ms on this stack (scratch/experiments/stream_cost.py): none is made inside a hand-off or a forward.
 int ensure_side_streams(gnnvc_engine *e) {
     if (e->aux_stream) return GNNVC_OK;
-    hipStream_t tried[4] = {nullptr, nullptr, nullptr, nullptr};
-    int n = 0;
-    hipStream_t good = nullptr;
-    while (n < 4 && !good) {
-        HIP_TRY(e, hipStreamCreateWithFlags(&tried[n], hipStreamNonBlocking));
-        bool beside = false;
-        HIP_TRY(e, gnnvc::streams_run_side_by_side(e->stream, tried[n], &beside));
-        if (beside) good = tried[n];
-        ++n;
-    }
-    e->side_probes = n;
-    e->side_beside = good != nullptr;
-    if (!good) good = tried[n - 1];   // (none passed: a serialised side queue is slow, not wrong)
-    for (int i = 0; i < n; ++i)
-        if (tried[i] != good) (void)hipStreamDestroy(tried[i]);
-    e->aux_stream = e->long_stream = e->giant_stream = good;
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_long, hipEventDisableTiming));
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_giant, hipEventDisableTiming));
+    int rc = probe_side_queue(e, e->aux_stream, e->side_beside, e->side_probes);
+    if (rc) return rc;
+    e->long_stream = e->giant_stream = e->aux_stream;   // (aliases: aux_stream owns the queue)
+    HIP_TRY(e, e->ev_fork.create(hipEventDisableTiming));
+    HIP_TRY(e, e->ev_join.create(hipEventDisableTiming));
+    HIP_TRY(e, e->ev_long.create(hipEventDisableTiming));
+    HIP_TRY(e, e->ev_giant.create(hipEventDisableTiming));
     return GNNVC_OK;
 }
 
@@ -902,24 +902,15 @@ int reprobe_side_streams(gnnvc_engine *e) {
     HIP_TRY(e, gnnvc::streams_run_side_by_side(e->stream, e->aux_stream, &beside));
     e->side_probes = 1;
     if (!beside) {
-        hipStream_t tried[4] = {nullptr, nullptr, nullptr, nullptr};
+        gnnvc::Stream good;
         int n = 0;
-        hipStream_t good = nullptr;
-        while (n < 4 && !good) {
-            HIP_TRY(e, hipStreamCreateWithFlags(&tried[n], hipStreamNonBlocking));
-            bool ok = false;
-            HIP_TRY(e, gnnvc::streams_run_side_by_side(e->stream, tried[n], &ok));
-            if (ok) good = tried[n];
-            ++n;
-        }
+        int rc = probe_side_queue(e, good, beside, n);
+        if (rc) return rc;
         e->side_probes += n;
-        for (int i = 0; i < n; ++i)
-            if (tried[i] != good) (void)hipStreamDestroy(tried[i]);
-        if (good) {
+        if (beside) {   // (none passed: the queue in place stays)
             (void)hipStreamSynchronize(e->aux_stream);
-            (void)hipStreamDestroy(e->aux_stream);
-            e->aux_stream = e->long_stream = e->giant_stream = good;
-            beside = true;
+            e->aux_stream = std::move(good);
+            e->long_stream = e->giant_stream = e->aux_stream;
         }
     }
     e->side_beside = beside;
@@ -932,9 +923,9 @@ int ensure_round_events(gnnvc_engine *e, size_t count) {
         if (rc) return rc;
     }
     while (e->round_ev.size() < count) {
-        hipEvent_t v;
-        HIP_TRY(e, hipEventCreateWithFlags(&v, hipEventDisableTiming));
-        e->round_ev.push_back(v);
+        gnnvc::Event v;
+        HIP_TRY(e, v.create(hipEventDisableTiming));
+        e->round_ev.push_back(std::move(v));
     }
     return GNNVC_OK;
 }
@@ -950,7 +941,7 @@ int reserve_prune(gnnvc_engine *e, int stage) {
     HIP_TRY(e, e->pin_info.reserve(64));
     HIP_TRY(e, e->dev_info.reserve(64));
     HIP_TRY(e, pp.heavy.reserve(((size_t)g.n + 31) / 32 + 1));
-    if (e->opt_filter) {
+    if (e->opt.filter) {
         HIP_TRY(e, e->filter_bits[stage].reserve((size_t)g.n / 32 + 1));
         HIP_TRY(e, e->filter_info.reserve(16));
     }
@@ -959,7 +950,7 @@ int reserve_prune(gnnvc_engine *e, int stage) {
     HIP_TRY(e, e->prune_scratch.reserve(gnnvc::blocked_scan_scratch_elems(chunks + 1)));
     HIP_TRY(e, pp.prp.reserve((size_t)held + 1));
     HIP_TRY(e, pp.pcol.reserve((size_t)g.nnz + GNNVC_COL_PAD));
-    if (e->sorted_wanted && e->opt_prune_eff) {
+    if (e->sorted_wanted && e->opt.prune_eff) {
         HIP_TRY(e, pp.svertex.reserve(held));
         HIP_TRY(e, pp.smeta.reserve(held));
         HIP_TRY(e, e->srt_hist.reserve(4096));
@@ -975,7 +966,7 @@ int build_prune_impl(gnnvc_engine *e, int stage, const float *in, bool early, bo
     pp.ready = false;
     pp.predicted = pp.verified = false;
     const GraphDev &g = e->g;
-    if (!e->opt_prune || g.n == 0 || e->empty_slice || g.nnz == 0 || g.nnz < e->opt_prune_min_nnz) return GNNVC_OK;   // (no entries: nothing to prune — and no buffers: fuzz_multi.py, a part of rows without entries under "prune_min_entries" 0)
+    if (!e->opt.prune || g.n == 0 || e->empty_slice || g.nnz == 0 || g.nnz < e->opt.prune_min_nnz) return GNNVC_OK;   // (no entries: nothing to prune — and no buffers: fuzz_multi.py, a part of rows without entries under "prune_min_entries" 0)
     if (predicted && (g.sliced() || stage != 1 || e->stages.size() < 2)) return GNNVC_OK;
     if (g.nnz >= (1ull << 32)) return GNNVC_OK;
     int rc = reserve_prune(e, stage);
@@ -1015,7 +1006,7 @@ int build_prune_impl(gnnvc_engine *e, int stage, const float *in, bool early, bo
     pp.members = members;
     if (members == 0) return GNNVC_OK;   // degree-uniform graphs: every row has a non-zero, nothing to prune
     if (!g.sliced()) {
-        if (mass * 100 < g.nnz * (uint64_t)std::min(e->opt_prune_min_drop, 100u) / 2)   // (half the bound: the estimate is exact only for symmetric graphs)
+        if (mass * 100 < g.nnz * (uint64_t)std::min(e->opt.prune_min_drop, 100u) / 2)   // (half the bound: the estimate is exact only for symmetric graphs)
             return GNNVC_OK;
         if (early && mass * 100 < g.nnz * 40ull) {   // in a graph's FIRST forward the build has to pay within that forward: not at a 15 - 25 % cut
             pp.tried = false;                         // (nearly degree-uniform graphs with hubs: first forward 1.1 - 1.2 x) — with the other plans, then
@@ -1036,8 +1027,8 @@ int build_prune_impl(gnnvc_engine *e, int stage, const float *in, bool early, bo
     // whole stage on the power-law graph (8 M entries left: 0.57 -> 0.64 ms at 1024; R-MAT-22: 1.35 -> 1.25 ms).
     // (decided from the estimate of the entries left: the count itself arrives with the second round trip)
     const uint64_t kept_est = g.sliced() ? g.nnz : g.nnz - std::min<uint64_t>(mass, g.nnz);
-    pp.eff_thresh = kept_est >= e->opt_prune_heavy_entries ? e->thresh_f16 : std::max(e->long_thresh, std::min(e->thresh_f16, 512u));
-    const bool slist = e->sorted_wanted && e->opt_prune_eff;
+    pp.eff_thresh = kept_est >= e->opt.prune_heavy_entries ? e->thresh_f16 : std::max(e->long_thresh, std::min(e->thresh_f16, 512u));
+    const bool slist = e->sorted_wanted && e->opt.prune_eff;
     if (slist) {
         // tiles of the 16-wide stages from the rows sorted by the entries they have LEFT; the giant rows (by degree) are not in it
         GraphDev view = g;
@@ -1049,7 +1040,7 @@ int build_prune_impl(gnnvc_engine *e, int stage, const float *in, bool early, bo
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     const uint32_t kept = pin[4];
     pp.kept = kept;
-    if ((uint64_t)kept * 100 > g.nnz * (uint64_t)(100 - std::min(e->opt_prune_min_drop, 100u))) return GNNVC_OK;   // too little to gain
+    if ((uint64_t)kept * 100 > g.nnz * (uint64_t)(100 - std::min(e->opt.prune_min_drop, 100u))) return GNNVC_OK;   // too little to gain
     if (slist) {
         pp.sn = pin[6];
         pp.slist = true;
@@ -1066,7 +1057,7 @@ int gather_view(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
                 GraphDev &gv, gnnvc::SortedOrder &so_p, bool matrix_cores, uint32_t long_from) {
     gv = e->g;
     so_p = gnnvc::SortedOrder();
-    if (stage < 1 || stage > 3 || e->stages[stage].f != 16 || !e->opt_prune) return GNNVC_OK;
+    if (stage < 1 || stage > 3 || e->stages[stage].f != 16 || !e->opt.prune) return GNNVC_OK;
     gnnvc_engine::PrunePlan &pp = e->prune[stage];
     if (!gathering) return GNNVC_OK;   // (a compact-table plan has this call: its kernels do not gather, nothing to build or check)
     // Built with the rest of the plans when the graph is scored a second time — but on a LARGE skewed graph (sorted tiles or
@@ -1080,13 +1071,13 @@ int gather_view(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
     // ... on graphs whose LONG rows hold a good share of the entries (known since the hand-off): that is where the model zeroes
     // most targets (R-MAT: 73 - 86 % of the entries point to zero rows; power-law graphs and uniform graphs with hubs, 1 - 55 %,
     // lose 0.1 - 0.3 ms of their first forward to the look-ups)
-    const bool filter = e->opt_filter && matrix_cores && skewed && e->g.nnz >= e->opt_filter_min_nnz && e->g.nnz < (1ull << 32) &&
-                        e->n_long > 0 && e->long_entries * 100ull >= e->g.nnz * (uint64_t)e->opt_filter_min_long_pct;
-    const bool early = !filter && skewed && e->opt_prune_early_nnz && e->g.nnz >= e->opt_prune_early_nnz;
+    const bool filter = e->opt.filter && matrix_cores && skewed && e->g.nnz >= e->opt.filter_min_nnz && e->g.nnz < (1ull << 32) &&
+                        e->n_long > 0 && e->long_entries * 100ull >= e->g.nnz * (uint64_t)e->opt.filter_min_long_pct;
+    const bool early = !filter && skewed && e->opt.prune_early_nnz && e->g.nnz >= e->opt.prune_early_nnz;
     const uint32_t uses_needed = (early && !pp.deferred) ? 1u : 2u;
     e->filtered[stage] = e->short_used[stage] = e->borrowed[stage] = false;
-    if (e->short_from >= stage) e->short_from = 0;   // (the stage that left the lists runs again: they are this call's to leave, or nobody's)
-    if (pp.predicted && !pp.verified && e->graph_uses >= 2) {
+    if (e->pg.short_from >= stage) e->pg.short_from = 0;   // (the stage that left the lists runs again: they are this call's to leave, or nobody's)
+    if (pp.predicted && !pp.verified && e->pg.graph_uses >= 2) {
         // A plan built at hand-off from the PREDICTED set has served a forward: did its check pass there?  If the caller's input
         // is not what the prediction assumed, the set is wrong for this graph's stage inputs (which are the same on every
         // forward) and every call would fall back to the full adjacency: the plan goes, and is rebuilt below from the input the
@@ -1097,10 +1088,10 @@ int gather_view(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
         if (pin[12] != 0u) pp.forget();
         else pp.verified = true;
     }
-    if (!pp.tried && e->graph_uses >= uses_needed) {
-        const bool first_forward = e->graph_uses < 2;
+    if (!pp.tried && e->pg.graph_uses >= uses_needed) {
+        const bool first_forward = e->pg.graph_uses < 2;
         int rc = timed_build(e, [&] { return build_prune_impl(e, stage, in, first_forward); },
-                             e->opt_prune && e->g.n != 0 && e->g.nnz >= e->opt_prune_min_nnz);
+                             e->opt.prune && e->g.n != 0 && e->g.nnz >= e->opt.prune_min_nnz);
         if (rc) return rc;
     }
     // A graph's FIRST forward, the stage behind one that runs on a predicted plan: it borrows that plan — the model keeps the hubs'
@@ -1119,17 +1110,17 @@ int gather_view(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
             HIP_TRY(e, e->filter_bits[stage].reserve((size_t)g.n / 32 + 1));
             HIP_TRY(e, e->filter_info.reserve(16));
             // an earlier stage of this graph left its long rows' lists — of every row this call's long-row kernel will take?
-            const int from = e->short_from;
+            const int from = e->pg.short_from;
             const uint32_t giant_from = e->giant_f16();
             const bool consume = from >= 1 && from < stage && long_from >= e->short_min && giant_from <= e->short_max;
             // (gv, not g: the verdict on the earlier stage's lists has to be reached with the bound that stage's kernels used)
-            gv.zero_min_pct = e->opt_filter_min_pct;
+            gv.zero_min_pct = e->opt.filter_min_pct;
             HIP_TRY(e, gnnvc::filter_mark(gv, in, e->filter_bits[stage].p, e->filter_info.p + 4 * stage, e->stream,
                                           consume ? e->filter_bits[from].p : nullptr, consume ? e->filter_info.p + 4 * from : nullptr));
             gv.zero_bits = e->filter_bits[stage].p;
             gv.zero_info = e->filter_info.p + 4 * stage;
             e->filtered[stage] = true;
-            if (e->opt_filter_keep && e->n_long > 0) {
+            if (e->opt.filter_keep && e->n_long > 0) {
                 // the long rows' short lists of this call go where the plan's entries will go once it is built
                 HIP_TRY(e, pp.pcol.reserve((size_t)g.nnz + GNNVC_COL_PAD));
                 HIP_TRY(e, pp.prp.reserve((size_t)(g.hi() - g.lo()) + 1));
@@ -1143,7 +1134,7 @@ int gather_view(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
                 }
                 // a call that sees every row the engine holds leaves them for the next 16-wide stage, if there is one
                 if (lo == g.lo() && hi == g.hi() && stage + 1 < (int)e->stages.size() && stage + 1 <= 3 && e->stages[stage + 1].f == 16) {
-                    e->short_from = stage;
+                    e->pg.short_from = stage;
                     e->short_min = long_from;
                     e->short_max = giant_from;
                 }
@@ -1155,7 +1146,7 @@ int gather_view(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
     gv.prp = use->prp.p - e->g.lo();   // (indexed by global row id, like rowptr)
     gv.pcol = use->pcol.p;
     gv.prune_bad = e->prune_flags.p + stage;
-    if (e->opt_prune_eff) {
+    if (e->opt.prune_eff) {
         const bool whole = lo == e->g.lo() && hi == e->g.hi();
         if (!sorted_tiles) {
             gv.prune_eff = 1;
@@ -1199,9 +1190,9 @@ int reserve_multi_front(gnnvc_engine *e, uint32_t n) {
 
 int ensure_events(gnnvc_engine *e, size_t count) {
     while (e->ev.size() < count) {
-        hipEvent_t v;
-        HIP_TRY(e, hipEventCreate(&v));
-        e->ev.push_back(v);
+        gnnvc::Event v;
+        HIP_TRY(e, v.create());
+        e->ev.push_back(std::move(v));
     }
     return GNNVC_OK;
 }
@@ -1218,12 +1209,12 @@ int prepare_table_tiles(gnnvc_engine *e) {
     e->t4_used = false;
     for (bool &b : e->t4_fit_seen) b = false;
     const GraphDev &g = e->g;
-    if (!e->opt_t4 || !e->opt_compact || e->opt_mfma == 1 || e->stages.size() != 3 || g.n == 0 || e->empty_slice || g.sliced()) return GNNVC_OK;
+    if (!e->opt.t4 || !e->opt.compact || e->opt.mfma == 1 || e->stages.size() != 3 || g.n == 0 || e->empty_slice || g.sliced()) return GNNVC_OK;
     if (e->stages[0].variant != 0 || e->stages[1].variant != 1 || e->stages[2].variant != 2) return GNNVC_OK;
     if (e->n_long > 0 || e->sorted_wanted || g.nnz == 0) return GNNVC_OK;
-    if (g.n < e->opt_t4_min_n || ((uint64_t)g.n + 1) * 16 > e->opt_t4_max_bytes) return GNNVC_OK;
-    const bool plan_range = g.n >= std::min(e->opt_blocked_min_n, e->opt_compact_min_n) &&
-                            (e->opt_blocked_min_n < (1u << 20) || g.nnz >= e->opt_compact_min_nnz);
+    if (g.n < e->opt.t4_min_n || ((uint64_t)g.n + 1) * 16 > e->opt.t4_max_bytes) return GNNVC_OK;
+    const bool plan_range = g.n >= std::min(e->opt.blocked_min_n, e->opt.compact_min_n) &&
+                            (e->opt.blocked_min_n < (1u << 20) || g.nnz >= e->opt.compact_min_nnz);
     if (plan_range) return GNNVC_OK;   // (the compact-table plan has these graphs)
     for (auto &t : e->t4_table) {
         HIP_TRY(e, t.reserve(((size_t)g.n + 1) * 4));
@@ -1252,9 +1243,9 @@ int prepare_plans(gnnvc_engine *e) {
         const int rc = prepare_table_tiles(e);
         if (rc) return rc;
     }
-    if (!e->opt_handoff || e->stages.empty() || e->g.n == 0 || e->empty_slice) return GNNVC_OK;
+    if (!e->opt.handoff || e->stages.empty() || e->g.n == 0 || e->empty_slice) return GNNVC_OK;
     const GraphDev &g = e->g;
-    const double before = e->plan_build_ms;
+    const double before = e->pg.plan_build_ms;
     const bool skewed = e->sorted_wanted || e->n_long > 0;
     int rc = GNNVC_OK;
     HIP_TRY(e, e->pin_info.reserve(64));
@@ -1264,7 +1255,7 @@ int prepare_plans(gnnvc_engine *e) {
         rc = timed_build(e, [&] { return ensure_sorted(e, g.lo(), g.hi()); });
         if (rc) return rc;
     }
-    // The per-graph plans.  By default only where ONE use repays the build: degree-uniform graphs from opt_handoff_min_nnz
+    // The per-graph plans.  By default only where ONE use repays the build: degree-uniform graphs from opt.handoff_min_nnz
     // entries on (metric graph: ~3.5 ms of builds against 4.3 ms saved in the very first forward; a skewed graph's F = 1 plan
     // costs 9 - 29 ms to build and saves 0.2 - 2 ms a forward — it keeps waiting for a second forward unless asked for, "2").
     if (e->lt_pb.open || e->c4_pb.open) {   // begun while the column array was arriving (handoff_early): the rest, and the step records
@@ -1277,14 +1268,14 @@ int prepare_plans(gnnvc_engine *e) {
         });
         if (rc) return rc;
     }
-    if (!g.sliced() && (e->opt_handoff >= 2 || (!skewed && g.nnz >= e->opt_handoff_min_nnz))) {
-        if (!e->lt_tried) rc = build_lds_table(e);
+    if (!g.sliced() && (e->opt.handoff >= 2 || (!skewed && g.nnz >= e->opt.handoff_min_nnz))) {
+        if (!e->pg.lt_tried) rc = build_lds_table(e);
         if (rc) return rc;
-        if (!e->c4_tried && !e->c4_range_mode) rc = build_compact(e);
+        if (!e->pg.c4_tried && !e->pg.c4_range_mode) rc = build_compact(e);
         if (rc) return rc;
     }
     // pruned adjacency: it needs a stage's INPUT and is built inside a forward — with every buffer it wants already here
-    if (skewed && e->opt_prune && g.nnz >= e->opt_prune_min_nnz && g.nnz < (1ull << 32) && true) {
+    if (skewed && e->opt.prune && g.nnz >= e->opt.prune_min_nnz && g.nnz < (1ull << 32) && true) {
         for (int st = 1; st < (int)e->stages.size() && st < 4; ++st)
             if (e->stages[st].f == 16) {
                 rc = reserve_prune(e, st);
@@ -1294,8 +1285,8 @@ int prepare_plans(gnnvc_engine *e) {
         // filtered gather's graphs: large, their long rows hold a good share of the entries): the reference's driver feeds
         // x = W / ws (src/GNN_VC.cpp:189-191), so that stage's zero rows follow from the graph's own weights, and the plan for the
         // PREDICTED set is built here — proven per call like any other.  R-MAT-22: +0.9 ms of hand-off, first forward 3.5 -> 2.8 ms.
-        if (e->opt_prune_predict && !g.sliced() && g.nnz >= e->opt_predict_min_nnz && e->n_long > 0 &&
-            e->long_entries * 100ull >= g.nnz * (uint64_t)e->opt_filter_min_long_pct && e->stages.size() >= 2 &&
+        if (e->opt.prune_predict && !g.sliced() && g.nnz >= e->opt.predict_min_nnz && e->n_long > 0 &&
+            e->long_entries * 100ull >= g.nnz * (uint64_t)e->opt.filter_min_long_pct && e->stages.size() >= 2 &&
             e->stages[0].variant == 0 && e->stages[1].f == 16 && !e->prune[1].tried) {
             rc = timed_build(e, [&] { return build_prune_impl(e, 1, nullptr, /*early=*/true, /*predicted=*/true); });
             if (rc) return rc;
@@ -1306,31 +1297,15 @@ int prepare_plans(gnnvc_engine *e) {
         rc = ensure_events(e, e->stages.size() + 1);
         if (rc) return rc;
     }
-    e->handoff_build_ms = e->plan_build_ms - before;
+    e->handoff_build_ms = e->pg.plan_build_ms - before;
     return GNNVC_OK;
 }
 
 // per-graph state of the plans: nothing of the previous graph's survives
 void reset_graph_state(gnnvc_engine *e) {
-    e->wide_used = false;
-    e->lt_ready = e->lt_tried = false;
-    e->lt_used = e->lt_off = false;
-    e->lt_unfit_runs = 0;
-    e->c4_ready = e->c4_tried = false;
-    e->lt_pb.open = e->c4_pb.open = false;
+    e->pg = gnnvc_engine::PerGraph{};
     for (auto &pp : e->prune) pp.forget();
-    e->short_from = 0;
-    for (int s = 0; s < 4; ++s) { e->c4_stage_off[s] = false; e->c4_unfit_runs[s] = 0; e->fit_used[s] = false; }
-    e->fit_pending = false;
-    e->fit_calm = e->fit_skip = 0;
-    e->c4_range_mode = false;
-    e->c4_prepared_stage = -1;
-    e->blocked_ready = false;   // the column-blocked index is built on the graph's SECOND forward:
-    e->blocked_tried = false;   // it costs about as much as it saves on one, and the reference's
-    e->graph_uses = 0;          // driver uses every graph exactly once (src/GNN_VC.cpp:171-192)
-    e->plan_build_ms = 0.0;
-    e->early_ms = 0.0;
-    for (bool &b : e->c4_seeded) b = false;
+    e->lt_pb.open = e->c4_pb.open = false;
 }
 
 // A host hand-off (upload / staged) of a large graph: the row pointers and weights are on the device before most of the
@@ -1342,8 +1317,8 @@ void reset_graph_state(gnnvc_engine *e) {
 int handoff_early(gnnvc_engine *e, uint32_t n, uint64_t nnz) {
     if (e->early_open || e->early_declined) return GNNVC_OK;
     e->early_declined = true;
-    if (!e->opt_handoff || e->multi || e->stages.empty() || n == 0 || !e->aux_stream) return GNNVC_OK;
-    if (e->opt_handoff < 2 && nnz < e->opt_handoff_min_nnz) return GNNVC_OK;
+    if (!e->opt.handoff || e->multi || e->stages.empty() || n == 0 || !e->aux_stream) return GNNVC_OK;
+    if (e->opt.handoff < 2 && nnz < e->opt.handoff_min_nnz) return GNNVC_OK;
     const auto t0 = std::chrono::steady_clock::now();
     e->have_graph = false;
     e->empty_slice = false;
@@ -1368,13 +1343,13 @@ int handoff_early(gnnvc_engine *e, uint32_t n, uint64_t nnz) {
         rc = c4_begin(e, 0, 0xFFFFFFFFu);
         if (rc) return rc;
         // (only the flat builders work piece by piece; anything else waits for the commit)
-        if (e->lt_pb.open && !gnnvc::lds_table_is_flat(e->lt_pb.slice_rows, e->lt_pb.pm)) e->lt_pb.open = false, e->lt_tried = false;
-        if (e->c4_pb.open && !gnnvc::lds_table_is_flat(e->c4_pb.slice_rows, e->c4_pb.pm)) e->c4_pb.open = false, e->c4_tried = false;
+        if (e->lt_pb.open && !gnnvc::lds_table_is_flat(e->lt_pb.slice_rows, e->lt_pb.pm)) e->lt_pb.open = false, e->pg.lt_tried = false;
+        if (e->c4_pb.open && !gnnvc::lds_table_is_flat(e->c4_pb.slice_rows, e->c4_pb.pm)) e->c4_pb.open = false, e->pg.c4_tried = false;
     }
-    if (!e->ev_piece) HIP_TRY(e, hipEventCreateWithFlags(&e->ev_piece, hipEventDisableTiming));
+    if (!e->ev_piece) HIP_TRY(e, e->ev_piece.create(hipEventDisableTiming));
     e->early_open = true;
     e->early_declined = false;
-    e->early_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    e->pg.early_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return GNNVC_OK;
 }
 

@@ -17,7 +17,8 @@ _PKG = pathlib.Path(__file__).resolve().parent
 # GNNVC_LIBRARY: another build of the same library (A/B experiments with compile-time variants); default: the in-tree one
 _LIB = pathlib.Path(os.environ["GNNVC_LIBRARY"]).resolve() if os.environ.get("GNNVC_LIBRARY") else _PKG / "libgnnvc_hip.so"
 
-# every symbol include/gnnvc.h declares (tests check the library exports all of them)
+# every symbol include/gnnvc.h declares (tests check the library exports all of them).  gnnvc_debug_probe is exported too and
+# deliberately left out: a debugging aid outside the header (Option C), used by tests/test_gpu_lifetime.py
 ABI_SYMBOLS = [
     "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_destroy",
     "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_num_layers", "gnnvc_is_fused",
