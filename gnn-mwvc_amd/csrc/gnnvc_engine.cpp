@@ -134,6 +134,8 @@ int plan_model(gnnvc_engine *e) {
         sp.param_offset = L[1].w_off;
         // the parameter buffer is laid out in layer order, so W1 b1 W2 b2 W3 b3 are contiguous
         sp.variant = gnnvc::stage_variant(sp.f, sp.n1, sp.n2, sp.n3, sp.sigmoid_last);
+        sp.nd = 3;
+        sp.wn[0] = sp.n1; sp.wn[1] = sp.n2; sp.wn[2] = sp.n3;
         const bool last = (i + 7 == e->layers.size());
         ok = sp.variant >= 0 && (int)L[1].k == 2 * f + 3 && (sp.sigmoid_last ? last : true) &&
              (last || sp.n3 == 16);
@@ -143,27 +145,40 @@ int plan_model(gnnvc_engine *e) {
     }
     if (ok && !st.empty() && st.back().sigmoid_last) e->stages = std::move(st);
 
-    // generic stages (k_stage_any): the same layer pattern, any widths within stage_any_fits; a sigmoid ends the last
-    // stage and no other (a model that ends in a ReLU stays layer by layer, as for the trained shapes), the last n3 is the
-    // output width
+    // generic stages (k_stage_any): (Graph, (Linear, activation){d})+ with 1 <= d <= kMaxDenseLayers, d free per stage, any widths
+    // within stage_any_fits (which knows the LDS bound too); every activation a ReLU but the model's last, a sigmoid (a model that
+    // ends in a ReLU stays layer by layer, as for the trained shapes).  One stage outside the bounds leaves the whole model layer
+    // by layer.
     std::vector<StagePlan> gs;
-    bool gok = !e->layers.empty() && e->layers.size() % 7 == 0;
+    bool gok = !e->layers.empty();
     f = e->in_width;
-    for (i = 0; gok && i < e->layers.size(); i += 7) {
+    for (i = 0; gok && i < e->layers.size();) {
         const Layer *L = &e->layers[i];
-        gok = L[0].kind == kGraph && L[1].kind == kLinear && L[2].kind == kRelu && L[3].kind == kLinear && L[4].kind == kRelu &&
-              L[5].kind == kLinear && (L[6].kind == kRelu || L[6].kind == kSigmoid);
+        const size_t left = e->layers.size() - i;
+        gok = L[0].kind == kGraph;
         if (!gok) break;
         StagePlan sp;
         sp.f = f;
-        sp.n1 = (int)L[1].m; sp.n2 = (int)L[3].m; sp.n3 = (int)L[5].m;
-        sp.sigmoid_last = L[6].kind == kSigmoid;
-        sp.param_offset = L[1].w_off;
-        const bool last = (i + 7 == e->layers.size());
-        gok = gnnvc::stage_any_fits(sp.f, sp.n1, sp.n2, sp.n3) && (int)L[1].k == 2 * f + 3 && (int)L[3].k == sp.n1 &&
-              (int)L[5].k == sp.n2 && sp.sigmoid_last == last;
+        sp.nd = 0;
+        int k = 2 * f + 3;
+        size_t at = 1;
+        while (gok && at + 1 < left && L[at].kind == kLinear) {   // (a pair needs its activation: at + 1 is inside the model)
+            const bool model_end = at + 2 == left;
+            gok = sp.nd < gnnvc::kMaxDenseLayers && (int)L[at].k == k && L[at + 1].kind == (model_end ? kSigmoid : kRelu);
+            if (!gok) break;
+            if (sp.nd == 0) sp.param_offset = L[at].w_off;   // (the parameter buffer is in layer order: W b W b ... are contiguous)
+            sp.wn[sp.nd++] = k = (int)L[at].m;
+            sp.sigmoid_last = model_end;
+            at += 2;
+        }
+        gok = gok && sp.nd >= 1 && (at == left || L[at].kind == kGraph);
+        if (!gok) break;
+        sp.n3 = sp.wn[sp.nd - 1];
+        if (sp.nd == 3) { sp.n1 = sp.wn[0]; sp.n2 = sp.wn[1]; }
+        gok = gnnvc::stage_any_fits(sp);
         gs.push_back(sp);
         f = sp.n3;
+        i += at;
     }
     if (gok && !gs.empty()) e->gstages = std::move(gs);
     return GNNVC_OK;
@@ -854,6 +869,14 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k == "generic_stages" || k == "plans_at_handoff" || k == "mfma_dense") (void)gnnvc::read_option(e->opt, key, value);   // (as set)
     else if (k == "generic_stages_model") *value = e->generic_on() ? 1 : 0;   // would a forward run k_stage_any now
     else if (k == "generic_stages_active") *value = e->generic_ran ? 1 : 0;   // did the last one
+    else if (k == "generic_max_dense_layers") *value = gnnvc::kMaxDenseLayers;
+    else if (k.rfind("generic_stage_layers_", 0) == 0) {   // "generic_stage_layers_<s>": dense layers of stage s of a generic model
+        const char *num = k.c_str() + sizeof("generic_stage_layers_") - 1;
+        char *end = nullptr;
+        const long s = strtol(num, &end, 10);
+        if (!e->generic_on() || *num < '0' || *num > '9' || *end != 0 || s >= (long)e->gstages.size()) return GNNVC_ERR_INVALID;
+        *value = e->gstages[(size_t)s].nd;
+    }
     else if (k == "audit_runs") *value = (long)e->audit_runs;
     else if (k == "audit_failures") *value = (long)e->audit_failures;
     else if (k == "audit_repairs") *value = (long)e->audit_repairs;

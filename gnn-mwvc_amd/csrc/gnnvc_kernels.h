@@ -63,15 +63,20 @@ struct GraphDev {
 #endif
 };
 
-// One fused stage = graph layer (input width F) followed by up to three dense
-// layers.  Parameter block layout in device memory (floats):
-//   W1[K1 x N1] b1[N1] W2[N1 x N2] b2[N2] W3[N2 x N3] b3[N3],  K1 = 2F + 3.
+// One fused stage = graph layer (input width F) followed by its dense layers: three for the trained shapes and the
+// specialised launchers (n1, n2, n3), one to kMaxDenseLayers for a generic stage (k_stage_any).  Parameter block layout in
+// device memory (floats), in layer order:
+//   W1[K1 x N1] b1[N1] W2[N1 x N2] b2[N2] ... ,  K1 = 2F + 3.
+constexpr int kMaxDenseLayers = 6;
 struct StagePlan {
-    int f = 0;                // graph-layer input width: 1 or 16
-    int n1 = 0, n2 = 0, n3 = 0;
+    int f = 0;                // graph-layer input width: 1 or 16 (a generic stage: 1 .. 32)
+    int n1 = 0, n2 = 0, n3 = 0;   // n3: the stage's output width (of its last dense layer, whatever their number); n1, n2: the
+                                  // first two widths of a three-deep stage, 0 otherwise
     int sigmoid_last = 0;     // last activation is a sigmoid (else ReLU)
     size_t param_offset = 0;  // float offset of W1 in the engine's parameter buffer
     int variant = -1;         // index into the compiled instantiations, -1 = none
+    int nd = 3;               // dense layers
+    int wn[kMaxDenseLayers] = {0, 0, 0, 0, 0, 0};   // their widths, wn[nd - 1] == n3 (filled for generic stages)
 };
 
 // Degree-sorted tile order of the non-long rows of one row range (device arrays).
@@ -179,11 +184,14 @@ hipError_t launch_audit_stage(const StageCall &c, unsigned long long *rec, bool 
 // the audit's test hook: out[at]'s lowest mantissa bit flipped by one lane
 hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 
-// A fused stage of ANY widths within stage_any_fits (k_stage_any, gnnvc_stage_any.hip): 1 <= f <= 32, n1, n2 <= 64, n3 <= 32 —
-// models laid out like the trained one, (Graph, Linear, ReLU, Linear, ReLU, Linear, ReLU | Sigmoid)+, that are not of its
-// widths.  One launch per call; the graph's rowptr / col / w / nw only (no plan); rows of every degree.  in: (n + 1) x f rows
-// (the pad row is never read), out: rows [row_lo, row_hi) of an (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
-bool stage_any_fits(int f, int n1, int n2, int n3);
+// A fused stage of ANY widths and depth within stage_any_fits (k_stage_any, gnnvc_stage_any.hip) — models of the pattern
+// (Graph, (Linear, ReLU){d})+ with 1 <= d <= kMaxDenseLayers per stage and a sigmoid in place of the model's last ReLU, that are
+// not of the trained shapes.  stage_any_fits: 1 <= f <= 32, every width but the last <= 64, the last <= 32, and the stage's LDS
+// layout (transposed weights, biases, sixteen pairs of vectors) within the 64 KiB a launch gets without raising the kernel's
+// limit — plan_model and the launcher both ask this one function.  One launch per call; the graph's rowptr / col / w / nw only
+// (no plan); rows of every degree.  in: (n + 1) x f rows (the pad row is never read), out: rows [row_lo, row_hi) of an
+// (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
+bool stage_any_fits(const StagePlan &sp);
 hipError_t launch_stage_any(const StageCall &c);
 
 // a whole stage (variants 0, 1, 2) on WIDE tiles — a workgroup per 64-vertex tile, the tile's gather and each dense layer's outputs

@@ -1,7 +1,8 @@
-// gnnvc_stage_any.hip — k_stage_any: one fused stage (graph layer, three dense layers, ReLU | sigmoid) whose widths are
-// kernel ARGUMENTS, for models that are laid out like the trained one but are not of its widths (a retrain with 8-, 24- or
-// 64-wide hidden layers, another feature width, several input features or outputs).  The trained widths keep their own
-// kernels in gnnvc_kernels.hip; nothing here is shared with them or with k_audit_stage.
+// gnnvc_stage_any.hip — k_stage_any: one fused stage (graph layer, one to six dense layers, ReLU | sigmoid) whose depth and
+// widths are kernel ARGUMENTS, for models that are laid out like the trained one but are not of its shape (a retrain with 8-,
+// 24- or 64-wide hidden layers, two or four dense layers after a graph layer, another feature width, several input features or
+// outputs).  The trained shapes keep their own kernels in gnnvc_kernels.hip; nothing here is shared with them or with
+// k_audit_stage.
 //
 // What is computed is the layer-by-layer kernels' arithmetic (k_graph_layer, k_linear, k_relu, k_sigmoid):
 //   neighbour-sum column c   one fp32 add chain in stored CSR order from +0.0f;
@@ -11,12 +12,15 @@
 //   relu_ref, or sigmoid_ref on the last layer of the last stage (the logits are its input).
 // Compile with -ffp-contract=off, like the rest of the library.
 //
-// Bounds (stage_any_fits): 1 <= f <= 32, 1 <= n1, n2 <= 64, 1 <= n3 <= 32.
+// Bounds (stage_any_fits): 1 <= f <= 32, 1 <= d <= 6 dense layers, every width but the last 1 .. 64, the last 1 .. 32, and the LDS
+// layout below within 64 KiB (the dynamic LDS a launch gets without raising the kernel's limit, which nothing here does).
 //
 // Shape of the kernel: 256-thread workgroups walk the row range 16 rows at a time (grid-stride; no workgroup barrier inside
 // the walk, so a wave that sits on a very long row holds up nobody else).  Each workgroup first transposes the stage's
-// three weight matrices into LDS (wNt[o * pitch + k], pitch an odd number of 16-byte slots: the sixteen lanes of a group
-// read sixteen different 16-byte slots of the bank row).  A 16-lane group owns a row:
+// weight matrices into LDS (wt[o * pitch + k], a pitch per layer, any_pitch(K): an odd number of 16-byte slots, so the sixteen
+// lanes of a group read sixteen different 16-byte slots of the bank row).  A 16-lane group owns a row and two LDS vectors, A
+// and B: the graph row goes to A, layer 1 writes B, layer 2 A, ... (each vector as long as the longest that ever lands in
+// it), and the last layer goes from whichever holds its input — A itself when d = 1 — straight to memory:
 //   gather   lane j owns neighbour columns j and j + 16.  The group fetches the column ids of a round (32 entries; 16 when
 //            f > 16), the next round's already on their way, issues the round's 32 row loads per lane, then adds them in
 //            order.  f = 1: every lane fetches one neighbour's value per 16 entries, 64 entries a round, and all lanes add
@@ -24,7 +28,7 @@
 //   dense    the outputs of a layer are dealt to the lanes (o = j + 16 t); a lane runs its outputs' chains together, four
 //            k at a time: one 16-byte read of the group's input vector (same address for the group) and one per output of
 //            its transposed weight row.  The number of outputs per lane (1 .. 4) is a template argument chosen by a
-//            wave-uniform switch, so the accumulators stay in registers.
+//            wave-uniform switch per layer, so the accumulators stay in registers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,32 +59,44 @@ struct AnyGraph {
 
 }  // namespace
 
-// LDS layout, in floats (host and device agree through this one function)
+// what the kernel is told of the stage, by value: f, the number of dense layers and their widths
+struct AnyShape {
+    int f, d;
+    int n[kMaxDenseLayers];
+};
+
+// LDS layout, in floats (host and device agree through this one function): the layers' transposed weights one after the other
+// (layer l: n[l] rows of any_pitch(K_l) floats), the biases, then per group [A | B]
 struct StageAnyLayout {
-    int p;                       // pitch of the transposed weights
-    int w1, w2, w3, bias, grp;   // offsets
-    int gs, hb;                  // per group: gs floats — [0, hb) input vector, later the second layer's outputs; [hb, gs) the first layer's
+    int bias, grp;   // offsets (the weights start at 0)
+    int gs, hb;      // per group: gs floats — [0, hb) vector A, [hb, gs) vector B
     int total;
 };
 __host__ __device__ inline int any_round4(int v) { return (v + 3) / 4 * 4; }
 __host__ __device__ inline int any_pitch(int k) {
     return 4 * (((k + 3) / 4) | 1);   // an odd number of 16-byte slots: rows o .. o + 15 start in sixteen different slots
 }
-__host__ __device__ inline StageAnyLayout stage_any_layout(int f, int n1, int n2, int n3) {
+__host__ __device__ inline StageAnyLayout stage_any_layout(const AnyShape &S) {
     StageAnyLayout L;
-    const int k1 = 2 * f + 3;
-    const int kmax = k1 > n1 ? (k1 > n2 ? k1 : n2) : (n1 > n2 ? n1 : n2);
-    L.p = any_pitch(kmax);   // one pitch for the three matrices (fewer wave-uniform values to keep; the LDS it wastes is small)
-    L.w1 = 0;
-    L.w2 = L.w1 + n1 * L.p;
-    L.w3 = L.w2 + n2 * L.p;
-    L.bias = L.w3 + n3 * L.p;
-    L.grp = L.bias + any_round4(n1 + n2 + n3);
-    L.hb = any_round4(k1 > n2 ? k1 : n2);
-    L.gs = L.hb + any_round4(n1);
+    int K = 2 * S.f + 3, wsum = 0, nsum = 0, a = K, b = 0;   // a, b: the longest vector that lands in A, in B
+    for (int l = 0; l < S.d; ++l) {
+        const int N = S.n[l];
+        wsum += N * any_pitch(K);
+        nsum += N;
+        if (l + 1 < S.d) {   // (the last layer's outputs go to memory)
+            if (l & 1) a = a > N ? a : N;
+            else b = b > N ? b : N;
+        }
+        K = N;
+    }
+    L.bias = wsum;
+    L.grp = L.bias + any_round4(nsum);
+    L.hb = any_round4(a);
+    L.gs = L.hb + any_round4(b);
     L.total = L.grp + kAnyRows * L.gs;
     return L;
 }
+constexpr size_t kAnyLdsBytes = 64u * 1024u;
 
 namespace {
 
@@ -227,21 +243,30 @@ __device__ __forceinline__ float any_gather1(const uint32_t *__restrict__ col, c
 
 __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
                                                         float *__restrict__ out, float *__restrict__ logits, uint32_t lo, uint32_t hi,
-                                                        int f, int n1, int n2, int n3, int sig) {
+                                                        AnyShape S, int sig) {
     extern __shared__ float4 any_lds4[];
     float *lds = reinterpret_cast<float *>(any_lds4);
-    const StageAnyLayout L = stage_any_layout(f, n1, n2, n3);
-    const int k1 = 2 * f + 3;
-    float *w1t = lds + L.w1, *w2t = lds + L.w2, *w3t = lds + L.w3, *bs = lds + L.bias;
-    // parameters, transposed: wNt[o * p + k] = WN[k * N + o]   (W1 b1 W2 b2 W3 b3 are contiguous from P)
-    const float *W1 = P, *B1 = W1 + k1 * n1, *W2 = B1 + n1, *B2 = W2 + n1 * n2, *W3 = B2 + n2, *B3 = W3 + n2 * n3;
-    for (int i = threadIdx.x; i < k1 * n1; i += kAnyBlock) w1t[(i % n1) * L.p + i / n1] = W1[i];
-    for (int i = threadIdx.x; i < n1 * n2; i += kAnyBlock) w2t[(i % n2) * L.p + i / n2] = W2[i];
-    for (int i = threadIdx.x; i < n2 * n3; i += kAnyBlock) w3t[(i % n3) * L.p + i / n3] = W3[i];
-    for (int i = threadIdx.x; i < n1 + n2 + n3; i += kAnyBlock) bs[i] = i < n1 ? B1[i] : (i < n1 + n2 ? B2[i - n1] : B3[i - n1 - n2]);
+    const StageAnyLayout L = stage_any_layout(S);
+    const int f = S.f, d = S.d, k1 = 2 * f + 3;
+    float *bs = lds + L.bias;
+    // parameters, transposed: wt[o * pitch + k] = W[k * N + o]   (W1 b1 W2 b2 ... are contiguous from P)
+    {
+        const float *W = P;
+        float *wt = lds, *bl = bs;
+        int K = k1;
+        for (int l = 0; l < d; ++l) {
+            const int N = S.n[l], p = any_pitch(K);
+            for (int i = threadIdx.x; i < K * N; i += kAnyBlock) wt[(i % N) * p + i / N] = W[i];
+            for (int i = threadIdx.x; i < N; i += kAnyBlock) bl[i] = W[K * N + i];
+            W += K * N + N;
+            wt += N * p;
+            bl += N;
+            K = N;
+        }
+    }
     __syncthreads();
     const int lane = threadIdx.x & 63, j = lane & 15, grp = threadIdx.x >> 4, gbase = lane & 48;
-    float *xs = lds + L.grp + grp * L.gs, *h1 = xs + L.hb;
+    float *xs = lds + L.grp + grp * L.gs;   // the group's vector A; B follows at L.hb
     for (uint64_t base = (uint64_t)lo + (uint64_t)blockIdx.x * kAnyRows; base < hi; base += (uint64_t)gridDim.x * kAnyRows) {
         const uint64_t u64 = base + (uint64_t)grp;
         if (u64 >= hi) continue;   // (no workgroup barrier below: a group without a row just waits for the next round)
@@ -267,39 +292,62 @@ __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, c
             xs[c] = v;
         }
         wave_lds_sync();
-        // ---- linear + ReLU, linear + ReLU (xs -> h1 -> xs), linear + ReLU | sigmoid (xs -> memory)
-        any_hidden_n(xs, k1, w1t, L.p, bs, n1, j, h1);
-        wave_lds_sync();
-        any_hidden_n(h1, n1, w2t, L.p, bs + n1, n2, j, xs);
-        wave_lds_sync();
-        float *out_row = out + (size_t)u * (uint32_t)n3;
-        float *logit_row = logits ? logits + (size_t)u * (uint32_t)n3 : nullptr;   // (null unless this is the sigmoid stage)
-        if (n3 <= 16) any_last<1>(xs, n2, w3t, L.p, bs + n1 + n2, n3, j, sig, out_row, logit_row);
-        else any_last<2>(xs, n2, w3t, L.p, bs + n1 + n2, n3, j, sig, out_row, logit_row);
+        // ---- the hidden layers, linear + ReLU each (A -> B -> A ...), then the last: linear + ReLU | sigmoid (-> memory)
+        const float *src = xs;
+        float *dst = xs + L.hb;
+        const float *wt = lds, *bl = bs;
+        int K = k1;
+        for (int l = 0; l + 1 < d; ++l) {
+            const int N = S.n[l], p = any_pitch(K);
+            any_hidden_n(src, K, wt, p, bl, N, j, dst);
+            wave_lds_sync();
+            wt += N * p;
+            bl += N;
+            K = N;
+            float *t = const_cast<float *>(src);
+            src = dst;
+            dst = t;
+        }
+        const int n_out = S.n[d - 1];
+        float *out_row = out + (size_t)u * (uint32_t)n_out;
+        float *logit_row = logits ? logits + (size_t)u * (uint32_t)n_out : nullptr;   // (null unless this is the sigmoid stage)
+        if (n_out <= 16) any_last<1>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        else any_last<2>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
         wave_lds_sync();   // (the group's LDS is rewritten by its next row)
     }
 }
 
+AnyShape any_shape(const StagePlan &sp) {
+    AnyShape S{};
+    S.f = sp.f;
+    S.d = sp.nd;
+    for (int l = 0; l < kMaxDenseLayers; ++l) S.n[l] = (l < sp.nd) ? sp.wn[l] : 0;
+    return S;
+}
+
 }  // namespace
 
-bool stage_any_fits(int f, int n1, int n2, int n3) {
-    return f >= 1 && f <= 32 && n1 >= 1 && n1 <= 64 && n2 >= 1 && n2 <= 64 && n3 >= 1 && n3 <= 32;
+bool stage_any_fits(const StagePlan &sp) {
+    if (sp.f < 1 || sp.f > 32 || sp.nd < 1 || sp.nd > kMaxDenseLayers) return false;
+    for (int l = 0; l < sp.nd; ++l)
+        if (sp.wn[l] < 1 || sp.wn[l] > (l + 1 < sp.nd ? 64 : 32)) return false;
+    return (size_t)stage_any_layout(any_shape(sp)).total * sizeof(float) <= kAnyLdsBytes;
 }
 
 hipError_t launch_stage_any(const StageCall &c) {
     if (c.row_hi <= c.row_lo) return hipSuccess;
     const StagePlan &sp = *c.sp;
     const GraphDev &g = *c.g;
-    if (!stage_any_fits(sp.f, sp.n1, sp.n2, sp.n3) || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
+    if (!stage_any_fits(sp) || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
     const AnyGraph plain{g.rowptr, g.col, g.w, g.nw};
-    const StageAnyLayout L = stage_any_layout(sp.f, sp.n1, sp.n2, sp.n3);
-    const size_t lds = (size_t)L.total * sizeof(float);   // <= 53 KB at the largest widths
+    const AnyShape S = any_shape(sp);
+    const size_t lds = (size_t)stage_any_layout(S).total * sizeof(float);   // <= 64 KiB (stage_any_fits)
     // a persistent grid: as many workgroups as the LDS lets a CU hold (at most 8), on 256 CUs
     const unsigned per_cu = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (160u * 1024u) / (lds + 1024u)));
     const unsigned need = (unsigned)(((size_t)(c.row_hi - c.row_lo) + kAnyRows - 1) / kAnyRows);
     const dim3 grid(std::min(need, 256u * per_cu)), block(kAnyBlock);
     hipLaunchKernelGGL(k_stage_any, grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, c.out,
-                       sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, sp.f, sp.n1, sp.n2, sp.n3, sp.sigmoid_last ? 1 : 0);
+                       sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0);
     return hipGetLastError();
 }
 

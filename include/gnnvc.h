@@ -272,24 +272,30 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         "audit_last_mismatches", "audit_last_fused_bits", "audit_last_plain_bits" (-1 / 0 before any).  A
  *                         multi-device handle decides per forward whether its parts audit; it sums their counters and reports
  *                         the last_* of the first failing part, its message prefixed "part <p>: ".
- *   "generic_stages" 0|1|2  models of other widths than the trained one as fused stages (kernel k_stage_any; takes effect at
- *                         once).  The engine's specialised kernels and per-graph plans serve exactly the trained stage shapes
- *                         (5->32->32->16, 35->32->32->16, 35->32->16->1+sigmoid).  1 (default): a model of the same layer
- *                         pattern, (Graph, Linear, ReLU, Linear, ReLU, Linear, ReLU|Sigmoid)+ with a sigmoid ending the last
- *                         stage and no other (a model that ends in a ReLU stays layer by layer), whose widths fit 1 <= stage input width <= 32 (first linear layer k = 2 f + 3), n1, n2 <= 64,
- *                         n3 <= 32 — any number of stages, any input width up to 32, any output width up to 32 — runs one
- *                         fused kernel launch per stage with the layer-by-layer kernels' arithmetic bit for bit:
- *                         gnnvc_is_fused = 1, gnnvc_num_stages / gnnvc_stage_widths report its stages, gnnvc_forward,
- *                         gnnvc_forward_device and gnnvc_stage_forward_device run them (the pad row of d_in is never read).
+ *   "generic_stages" 0|1|2  models of other widths or depths than the trained one as fused stages (kernel k_stage_any; takes
+ *                         effect at once).  The engine's specialised kernels and per-graph plans serve exactly the trained stage
+ *                         shapes (5->32->32->16, 35->32->32->16, 35->32->16->1+sigmoid).  1 (default): a model of the pattern
+ *                         stage+, a stage being Graph_Layer followed by d pairs (Linear_Layer, activation), 1 <= d <= 6 and d
+ *                         free per stage, every activation a ReLU except the model's last, a sigmoid (a model that ends in a
+ *                         ReLU stays layer by layer), whose widths fit 1 <= stage input width f <= 32 (first linear layer
+ *                         k = 2 f + 3), every hidden width <= 64, a stage's last width <= 32, and whose every stage fits the
+ *                         kernel's 64 KiB of LDS (transposed weights at one pitch per layer, biases, sixteen pairs of row
+ *                         vectors; the kernel's LDS limit is not raised beyond that) — any number of stages, any input and
+ *                         output width up to 32 — runs one fused kernel launch per stage with the layer-by-layer kernels'
+ *                         arithmetic bit for bit: gnnvc_is_fused = 1, gnnvc_num_stages / gnnvc_stage_widths report its stages,
+ *                         gnnvc_forward, gnnvc_forward_device and gnnvc_stage_forward_device run them (the pad row of d_in is
+ *                         never read).  One stage outside the bounds leaves the whole model layer by layer.
  *                         A model whose every stage is of a trained shape is planned, launched and audited as ever.
- *                         0: such a model is not fused, has 0 stages and runs layer by layer (21 launches for three stages), as
+ *                         0: such a model is not fused, has 0 stages and runs layer by layer (one launch per layer), as
  *                         before this option existed.  2 (tests): the trained shape is sent through the generic kernel as well,
  *                         none of its plans used.  Generic stages have no per-graph plan and no audit ("audit_period" audits
  *                         nothing on them, as on an unfused model); gnnvc_stage_input_ready, the row codec (16-column rows) and
  *                         gnnvc_create_multi with several devices keep returning GNNVC_ERR_UNSUPPORTED for them.  On a
  *                         multi-device handle the option is stored and changes nothing.  gnnvc_get_info: "generic_stages",
  *                         "generic_stages_model" (1 = a forward would run the generic kernel now), "generic_stages_active"
- *                         (1 = the last forward did).
+ *                         (1 = the last forward did), "generic_stage_layers_<s>" (the dense-layer count d of stage s;
+ *                         GNNVC_ERR_INVALID for a stage that does not exist or while the model is not generic),
+ *                         "generic_max_dense_layers" (6).
  * gnnvc_get_info keys (further): "pruned_stage1|2", "pruned_entries_stage1|2", "pruned_vertices_stage1|2",
  * "pruned_last_ok_stage1|2" (did the last call of that stage use its pruned adjacency),
  * "compact_gather_last_ok", "compact_gather_last_passes", "compact_gather_last_dirty",
@@ -301,8 +307,8 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value);
 
 /* Model introspection (what model::layers holds). */
 int gnnvc_num_layers(const gnnvc_engine *e);
-/* 1 if the model runs as fused stages — the trained 3-stage shape, or (option "generic_stages", default on) any model of that
- * layer pattern within the generic kernel's width bounds — 0 if it runs layer by layer. */
+/* 1 if the model runs as fused stages — the trained 3-stage shape, or (option "generic_stages", default on) any model of the
+ * generic stage pattern within the generic kernel's width, depth and LDS bounds — 0 if it runs layer by layer. */
 int gnnvc_is_fused(const gnnvc_engine *e);
 /* Width of the forward's input / output rows. */
 int gnnvc_in_width(const gnnvc_engine *e);
