@@ -5,6 +5,8 @@
 // feature buffers, and sequences the stages like model::predict does
 // (reference src/gnn_inference.cpp:67-81).  All arithmetic happens in the HIP
 // kernels of gnnvc_kernels.hip; there is no CPU fallback here.
+#include <cmath>
+
 #include "gnnvc_engine_state.h"
 
 namespace {
@@ -75,6 +77,20 @@ int parse_model(gnnvc_engine *e, const char *text, size_t len) {
     return GNNVC_OK;
 }
 
+// May a term whose input is +-0 be left out of this layer's fma chains bit for bit?  fma(+-0, w, acc) == acc needs a finite w
+// (0 x inf is NaN) and an acc other than -0.0f; a chain that starts from +0.0f reaches -0.0f only by underflow, and a -0 / +0
+// difference in acc survives the separately rounded bias add only if the bias is -0.0f itself.
+bool zero_terms_may_go(const Layer &l) {
+    for (float w : l.W)
+        if (!std::isfinite(w)) return false;
+    for (float b : l.bias) {
+        uint32_t bits;
+        memcpy(&bits, &b, sizeof bits);
+        if (bits == 0x80000000u) return false;
+    }
+    return true;
+}
+
 // Widths through the network; decides fused vs layer-by-layer.
 int plan_model(gnnvc_engine *e) {
     // input width: a leading graph layer accepts any width; a leading linear fixes it.
@@ -136,6 +152,8 @@ int plan_model(gnnvc_engine *e) {
         sp.variant = gnnvc::stage_variant(sp.f, sp.n1, sp.n2, sp.n3, sp.sigmoid_last);
         sp.nd = 3;
         sp.wn[0] = sp.n1; sp.wn[1] = sp.n2; sp.wn[2] = sp.n3;
+        for (int l = 0; l < 3; ++l)
+            if (zero_terms_may_go(L[1 + 2 * l])) sp.skip_ok |= 1u << l;
         const bool last = (i + 7 == e->layers.size());
         ok = sp.variant >= 0 && (int)L[1].k == 2 * f + 3 && (sp.sigmoid_last ? last : true) &&
              (last || sp.n3 == 16);
@@ -317,7 +335,7 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
 gnnvc::StageCall stage_call(const gnnvc_engine *e, const gnnvc::StagePlan &sp, const float *in, float *out, float *logits, uint32_t lo,
                             uint32_t hi) {
     return {.sp = &sp, .g = &e->g, .ws = e->ws, .params = e->params.p, .in = in, .out = out, .logits = logits, .row_lo = lo,
-            .row_hi = hi, .stream = e->stream};
+            .row_hi = hi, .stream = e->stream, .skip = e->opt.dense_skip ? sp.skip_ok : 0u};
 }
 
 // fork: the long (and giant) rows of this stage beside the tile kernel
@@ -466,7 +484,7 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         desc = e->c4_desc.p + gnnvc_engine::kDescWords * (stage - 1);
         e->c4_last_desc = gnnvc_engine::kDescWords * (stage - 1);
         if (c.sums == StageChoice::kCompactWhole) e->pg.fit_used[stage] = true;
-        sums = {.acc4 = e->c4_acc.p, .c4desc = desc, .agg16 = e->c4_agg16.p, .table_in = e->opt.dense_skip ? e->c4_table.p : nullptr};
+        sums = {.acc4 = e->c4_acc.p, .c4desc = desc, .agg16 = e->c4_agg16.p, .table_in = (call.skip & 1u) ? e->c4_table.p : nullptr};   // (without the table: route C, the full chain)
         const bool whole = c.sums == StageChoice::kCompactWhole;
         if (whole && !c.fused_counts) HIP_TRY(e, gnnvc::column_counts(in, e->g.n, e->c4_counts.p, e->stream));
         const bool fused = whole && c.fused_counts;
@@ -890,6 +908,10 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k == "multi_last_forward_us") *value = e->multi ? (long)(gnnvc::multi_last_forward_ms(e->multi) * 1000.0) : 0;
     else if (k.rfind("multi_", 0) == 0) {
         if (!e->multi || !gnnvc::multi_get_info(e->multi, key, value)) return GNNVC_ERR_INVALID;
+    }
+    else if (k == "dense_skip_layers") {   // bit 3 s + l: dense layer l + 1 of fused stage s may leave out its zero terms (the model's weights allow it)
+        *value = 0;
+        for (size_t s = 0; s < e->stages.size() && s < 10; ++s) *value |= (long)(e->stages[s].skip_ok & 7u) << (3 * s);
     }
     else if (k == "compact_gather_active") *value = e->pg.c4_ready ? 1 : 0;
     else if (k == "compact_gather_chunks") *value = e->pg.c4_ready ? (long)e->c4_chunks : 0;

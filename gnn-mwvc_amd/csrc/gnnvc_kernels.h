@@ -77,6 +77,8 @@ struct StagePlan {
     int variant = -1;         // index into the compiled instantiations, -1 = none
     int nd = 3;               // dense layers
     int wn[kMaxDenseLayers] = {0, 0, 0, 0, 0, 0};   // their widths, wn[nd - 1] == n3 (filled for generic stages)
+    uint32_t skip_ok = 0;     // bit l set: dense layer l + 1 has finite weights only and no bias with the bits of -0.0f, so terms
+                              // whose input is +-0 may be left out of its chains bit for bit (set at model load)
 };
 
 // Degree-sorted tile order of the non-long rows of one row range (device arrays).
@@ -115,6 +117,8 @@ struct StageCall {
     float *out = nullptr, *logits = nullptr;
     uint32_t row_lo = 0, row_hi = 0;
     hipStream_t stream = nullptr;
+    uint32_t skip = 0;               // bits of sp->skip_ok the kernels may act on (option "dense_skip_zeros"): bit 0 = the first
+                                     // layer's known zeros (k_dense_f16's routes A / B), bits 1, 2 = dense_live in layers 2, 3
 };
 
 // Producer side of the compact-table plan: a stage kernel whose dense layers run on the VALU can count the

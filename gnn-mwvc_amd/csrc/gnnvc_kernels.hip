@@ -126,6 +126,46 @@ __device__ __forceinline__ void dense(const float (&in)[K], float (&out)[N],
     }
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// dense<>() for a hidden layer whose inputs come out of a ReLU: with `skip` set, term k is left out when in[k] is zero (+0 or
+// -0) in ALL 64 lanes of the wave — a wave-uniform branch around the term's N fmas.  Same bits: fma(+-0, w, acc) == acc for a
+// finite w unless acc is -0.0f, a chain from +0.0f gets there only by underflow, and a -0 / +0 difference in acc survives the
+// bias add only under a bias of -0.0f — the engine sets `skip` only for layers with finite weights and no such bias
+// (DESIGN.md §5).  Everything else is dense<>(): chains from +0.0f in ascending k, the separately rounded bias add, the
+// activation.  EVERY lane of the wave must be active at the call (__any looks at active lanes only, and the callers' clamped
+// lanes recompute a real row): k_stage_f1 and k_dense_f16 leave by whole waves before their dense layers and not at all after.
+// One test per term whatever `skip` says: the input's bits without the sign, or'ed with a uniform 1 when nothing is to be
+// skipped (NaNs count as non-zero: their terms stay).  The inputs are pinned in VGPRs first: otherwise the compiler computes
+// each of them just ahead of its test, from the previous layer's weights parked in VGPR lanes (hundreds of v_readlane).
+template <int K, int N, int ACT>
+__device__ __forceinline__ void dense_live(float (&in)[K], float (&out)[N], const float *__restrict__ W,
+                                           const float *__restrict__ b, bool skip) {
+    const uint32_t all = skip ? 0u : 1u;
+#pragma unroll
+    for (int k = 0; k < K; ++k) asm volatile("" : "+v"(in[k]));
+    // the chains as pairs (v_pk_fma_f32: two fmas, each rounded once, as two __builtin_fmaf): written out, because across
+    // these branches the compiler pairs out[1] with out[2] and pays for it in register moves
+    static_assert(N % 2 == 0, "outputs in pairs");
+    f32x2 acc[N / 2];
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) acc[j] = f32x2{0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float a = in[k];
+        if (__any(((__float_as_uint(a) << 1) | all) != 0u)) {   // (uniform)
+            const f32x2 aa = {a, a};
+#pragma unroll
+            for (int j = 0; j < N / 2; ++j) acc[j] = __builtin_elementwise_fma(aa, f32x2{W[k * N + 2 * j], W[k * N + 2 * j + 1]}, acc[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const float t = acc[j / 2][j % 2] + b[j];
+        out[j] = (ACT == 0) ? relu_ref(t) : t;
+    }
+}
+
 // XCD-aware tile mapping.  Workgroups are dealt round-robin over the 8 XCDs
 // (block b shares an L2 with block b + 8), so XCD-group x = b % 8 walks the
 // x-th contiguous eighth of the tile range: rows a graph stores close together
@@ -689,7 +729,8 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
                                                       const uint32_t *__restrict__ c4desc, const float4 *__restrict__ agg16,
                                                       const float4 *table_in /* may alias emit_table: each lane reads its row first */, uint32_t long_thresh,
                                                       const uint32_t *__restrict__ emit_spec, c4row *__restrict__ emit_table,
-                                                      unsigned long long *__restrict__ emit_counts) {
+                                                      unsigned long long *__restrict__ emit_counts, uint32_t skip) {
+    // skip: bit l set = dense layer l + 1 leaves out the hidden units that are zero in the whole wave (dense_live)
     static_assert(SIGMOID ? N3 == 1 : N3 == 16, "a feature stage writes 16 floats per row, the last stage one score");
     __shared__ float lds[SIGMOID ? 1 : kWavesPerBlock][SIGMOID ? 1 : kWave * kOutPitch];
     if (c4desc[0] == 0) return;
@@ -773,8 +814,9 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
         dense<32, 32, N1, 0>(x0, x1, W1, b1);   // rows 32..34 of W1 meet exact zeros
     }
     float x2[N2], x3[N3];
-    dense<N1, N1, N2, 0>(x1, x2, W2, b2);
-    dense<N2, N2, N3, SIGMOID ? 1 : 0>(x2, x3, W3, b3);
+    dense_live<N1, N2, 0>(x1, x2, W2, b2, (skip & 2u) != 0);
+    if constexpr (SIGMOID) dense<N2, N2, N3, 1>(x2, x3, W3, b3);   // (16 -> 1: one fma per term is not worth a branch)
+    else dense_live<N2, N3, 0>(x2, x3, W3, b3, (skip & 4u) != 0);
     if constexpr (SIGMOID) {
         if (mine) {
             if (logits) logits[u] = x3[0];
@@ -1362,7 +1404,8 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
         const float *__restrict__ acc_in, uint32_t long_thresh, int interleave,
         const uint32_t *__restrict__ acc_bad,
         const uint32_t *__restrict__ emit_spec, c4row *__restrict__ emit_table, unsigned long long *__restrict__ emit_counts,
-        const uint32_t *__restrict__ srt_vertex, const uint4 *__restrict__ srt_meta, uint32_t n_sorted) {
+        const uint32_t *__restrict__ srt_vertex, const uint4 *__restrict__ srt_meta, uint32_t n_sorted, uint32_t skip) {
+    // skip (VALU dense layers only): bit l set = dense layer l + 1 leaves out the hidden units that are zero in the whole wave
     // acc_bad (LDS-table plan only): *acc_bad == 0 -> acc_in holds the rows' COMPLETE sums and no entry is left
     // to add; != 0 -> the plan did not apply to this input, acc_in is ignored and every entry is gathered here.
     // srt_vertex (skewed graphs): tiles of 64 vertices of similar degree from the degree-sorted list (see
@@ -1468,8 +1511,8 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
             for (int r = 0; r < 8; ++r) T[(32 * vt + v) * kOutPitch + mfma_feat(r, h)] = d[vt][r];
     } else {
         float x2[N2], x3[N3];
-        dense<N1, N1, N2, 0>(x1, x2, W2, b2);
-        dense<N2, N2, N3, 0>(x2, x3, W3, b3);
+        dense_live<N1, N2, 0>(x1, x2, W2, b2, (skip & 2u) != 0);
+        dense_live<N2, N3, 0>(x2, x3, W3, b3, (skip & 4u) != 0);
         uint32_t nz = 0;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -4790,7 +4833,7 @@ hipError_t launch_dense_sigmoid(const StageCall &c, const CompactSums &s, uint32
     GNNVC_LAUNCH((k_dense_f16<32, 16, 1, true>), grid, block, 0, c.stream, *c.g, c.ws, reinterpret_cast<const float4 *>(c.in), c.out,
                        c.logits, c.params + c.sp->param_offset, c.row_lo, c.row_hi, reinterpret_cast<const float4 *>(s.acc4), s.c4desc,
                        reinterpret_cast<const float4 *>(s.agg16), reinterpret_cast<const float4 *>(s.table_in), long_thresh,
-                       (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr);
+                       (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr, c.skip);
     return hipGetLastError();
 }
 
@@ -4818,14 +4861,14 @@ hipError_t launch_stage(const StageCall &c, const TileArgs &a) {
         GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, P,
                            c.row_lo, c.row_hi, g.rowptr, g.col, nofloat, a.long_thresh, il, (const uint32_t *)nullptr,
                            a.emit.spec, reinterpret_cast<c4row *>(a.emit.table), a.emit.counts, sorted ? so->vertex : nullptr,
-                           sorted ? reinterpret_cast<const uint4 *>(so->meta) : nullptr, sorted ? so->n : 0u);
+                           sorted ? reinterpret_cast<const uint4 *>(so->meta) : nullptr, sorted ? so->n : 0u, c.skip);
         break;
     case 1:
         GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, P,
                            c.row_lo, c.row_hi, g.rowptr, g.col, nofloat, a.long_thresh, il, (const uint32_t *)nullptr,
                            (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr,
                            sorted ? so->vertex : nullptr, sorted ? reinterpret_cast<const uint4 *>(so->meta) : nullptr,
-                           sorted ? so->n : 0u);
+                           sorted ? so->n : 0u, c.skip);
         break;
 // neighbour rows in flight per vertex in the 16-wide tile kernel (x 4 vertices per quad).  Natural tiles: 2.  Degree-sorted
 // tiles (skewed graphs: rows of a tile have similar, mostly larger degrees): 3 — measured R-MAT-22 6.71 -> 6.53 ms, power-law
@@ -4901,7 +4944,7 @@ hipError_t launch_stage(const StageCall &c, const TileArgs &a) {
                 GNNVC_LAUNCH((k_dense_f16<32, 32, 16, false>), dgrid, block, 0, c.stream, g, c.ws, in4, c.out, (float *)nullptr, P, c.row_lo, c.row_hi,
                                    reinterpret_cast<const float4 *>(s.acc4), s.c4desc, reinterpret_cast<const float4 *>(s.agg16),
                                    reinterpret_cast<const float4 *>(s.table_in), a.long_thresh, a.emit.spec,
-                                   reinterpret_cast<c4row *>(a.emit.table), a.emit.counts);
+                                   reinterpret_cast<c4row *>(a.emit.table), a.emit.counts, c.skip);
             }
         } else {
             if (a.mfma_agg) GNNVC_LAUNCH_AGG(16, 1, true, true, c.logits);
@@ -5117,12 +5160,12 @@ hipError_t launch_stage0_blocked(const StageCall &c, const BlockedPlan &bp, cons
         GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, c.stream, g, c.ws, c.in, c.out,
                            c.params + sp.param_offset, c.row_lo, c.row_hi, ep, bp.colb, acc_in, a.long_thresh, a.interleave ? 1 : 0,
                            (const uint32_t *)nullptr, (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr,
-                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
+                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u, c.skip);
     else
         GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, c.stream, g, c.ws, c.in, c.out,
                            c.params + sp.param_offset, c.row_lo, c.row_hi, ep, bp.colb, acc_in, a.long_thresh, a.interleave ? 1 : 0,
                            (const uint32_t *)nullptr, a.emit.spec, reinterpret_cast<c4row *>(a.emit.table), a.emit.counts,
-                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
+                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u, c.skip);
     return hipGetLastError();
 }
 
@@ -5351,12 +5394,12 @@ hipError_t launch_stage0_lds_table(const StageCall &c, const LdsTablePlan &lp, u
         GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, true>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.params + sp.param_offset,
                            c.row_lo, c.row_hi, g.rowptr, g.col, acc, a.long_thresh, a.interleave ? 1 : 0, (const uint32_t *)bad,
                            (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr,
-                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
+                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u, c.skip);
     else
         GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.params + sp.param_offset,
                            c.row_lo, c.row_hi, g.rowptr, g.col, acc, a.long_thresh, a.interleave ? 1 : 0, (const uint32_t *)bad,
                            a.emit.spec, reinterpret_cast<c4row *>(a.emit.table), a.emit.counts,
-                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u);
+                           (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u, c.skip);
     return hipGetLastError();
 }
 

@@ -34,6 +34,8 @@ struct Options {
     int overlap = 1;                  // last stage: dense layers of round k under the sums of round k + 1
     int dense_skip = 1;               // option "dense_skip_zeros" (A/B): the aggregate-only dense kernels take a clean row's <= 11 non-zero
                                       // first-layer terms from its sums and the input's compact table instead of the 32-term chain (k_dense_f16)
+                                      // — and the VALU hidden layers of k_stage_f1 / k_dense_f16 leave out the units that are zero in a whole
+                                      // wave (dense_live).  Both only in layers whose weights allow it (StagePlan::skip_ok); 0 = neither
     // pruned adjacency of the 16-wide stages
     int prune = 1;               // option "prune_zero_rows": 1 = the rows found all zero when the plan is built (or predicted at hand-off), 0 = off
     uint64_t prune_heavy_entries = 16u << 20;   // option "prune_heavy_entries": from this many entries left, rows up to the sorted threshold stay with the tile kernel

@@ -209,7 +209,13 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         once runs its first forward on it and the next stage borrows it.  Default 1.  gnnvc_get_info:
  *                         "pruned_predicted_stage1", "pruned_borrowed_stage2"
  *   "dense_skip_zeros" 0|1  (round 4; A/B) the aggregate-only dense kernels of the compact-table plan leave out the first-layer
- *                         terms they know to be zero (default 1; bit-identical)
+ *                         terms they know to be zero, and the hidden layers that run on the VALU (the 32 -> 32 and 32 -> 16
+ *                         layers of the F = 1 stage kernel and of the aggregate-only dense kernels) leave out, wave by wave,
+ *                         the terms whose input unit is zero in all 64 rows of the wave.  Bit-identical: a layer takes part
+ *                         only if all its weights are finite and none of its biases has the bits of -0.0f, decided when
+ *                         the model is loaded — gnnvc_get_info "dense_skip_layers": bit 3 s + l set = dense layer l + 1
+ *                         of fused stage s may leave out zero terms (whatever this option says).  Default 1; 0 = every
+ *                         chain runs all its terms
  *   "forward_timing" 0|1|2  (round 4) HIP events of a forward for gnnvc_last_forward_ms: 0 (default) = none — a record costs the
  *                         stream ~1.8 us, four of them were 5.5 us of a 30 - 80 us forward —, 1 = the forward's first and last
  *                         (total only), 2 = one per stage too
