@@ -598,26 +598,32 @@ int run_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float 
     return GNNVC_OK;
 }
 
-// ---------------------------------------------------------------- the audit (options "audit_*", k_audit_stage)
+// ---------------------------------------------------------------- the audit (options "audit_*", k_audit_stage / k_audit_any)
 // Is this call of a forward entry point audited?  (calls k, 2k, 3k, ... since the period was set)
 bool audit_tick(gnnvc_engine *e) {
     if (!e->opt.audit_period) return false;
     return ++e->audit_calls % e->opt.audit_period == 0;
 }
 
-// right behind run_stage of `stage` over [lo, hi), on e->stream: the test hook, then the audit into the call's next record
-int audit_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float *in, float *out, float *logits, std::string &plan) {
+// right behind the launches of `stage` (of e->stage_list()) over [lo, hi), on e->stream: the test hook (hook: not when the
+// caller owns the buffers, gnnvc_audit_stage_device), then the audit into the call's next record — k_audit_stage for the trained
+// shapes, k_audit_any for a generic stage
+int audit_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float *in, float *out, float *logits, std::string &plan,
+                bool hook = true) {
+    const std::vector<StagePlan> &st = e->stage_list();
     const size_t slot = e->audit_pending.size();
     if (slot == 0) {   // the call's first check: its records
-        HIP_TRY(e, e->audit_rec.reserve(std::max<size_t>(e->stages.size(), 1) * gnnvc::kAuditWords));
+        HIP_TRY(e, e->audit_rec.reserve(std::max<size_t>(st.size(), 1) * gnnvc::kAuditWords));
         HIP_TRY(e, hipMemsetAsync(e->audit_rec.p, 0, e->audit_rec.cap * sizeof(unsigned long long), e->stream));
     }
-    if (slot >= e->stages.size()) return fail(e, GNNVC_ERR_STATE, "more audited stages than the model has");
-    const gnnvc::StagePlan &sp = e->stages[stage];
-    if (e->opt.audit_flip_stage == stage && e->opt.audit_flip_row >= lo && e->opt.audit_flip_row < hi)
+    if (slot >= st.size()) return fail(e, GNNVC_ERR_STATE, "more audited stages than the model has");
+    const gnnvc::StagePlan &sp = st[stage];
+    if (hook && e->opt.audit_flip_stage == stage && e->opt.audit_flip_row >= lo && e->opt.audit_flip_row < hi)
         HIP_TRY(e, gnnvc::launch_audit_flip(out, (size_t)e->opt.audit_flip_row * (size_t)sp.n3, e->stream));
-    HIP_TRY(e, gnnvc::launch_audit_stage(stage_call(e, sp, in, out, sp.sigmoid_last ? logits : nullptr, lo, hi),
-                                         e->audit_rec.p + slot * gnnvc::kAuditWords, /*repair=*/e->opt.audit_repair != 0));
+    const gnnvc::StageCall call = stage_call(e, sp, in, out, sp.sigmoid_last ? logits : nullptr, lo, hi);
+    unsigned long long *rec = e->audit_rec.p + slot * gnnvc::kAuditWords;
+    if (e->generic_on()) HIP_TRY(e, gnnvc::launch_audit_any(call, rec, /*repair=*/e->opt.audit_repair != 0));
+    else HIP_TRY(e, gnnvc::launch_audit_stage(call, rec, /*repair=*/e->opt.audit_repair != 0));
     e->audit_pending.push_back(gnnvc_engine::AuditCheck{stage, lo, hi, std::move(plan)});
     return GNNVC_OK;
 }
@@ -630,7 +636,7 @@ int audit_finish(gnnvc_engine *e, int rc) {
     checks.swap(e->audit_pending);
     if (rc != GNNVC_OK || checks.empty()) return rc;
     const size_t words = checks.size() * gnnvc::kAuditWords;
-    HIP_TRY(e, e->audit_pin.reserve(e->stages.size() * gnnvc::kAuditWords));
+    HIP_TRY(e, e->audit_pin.reserve(std::max(e->stage_list().size(), checks.size()) * gnnvc::kAuditWords));
     HIP_TRY(e, hipMemcpyAsync(e->audit_pin.p, e->audit_rec.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     std::string report;
@@ -700,7 +706,8 @@ int forward_unfused(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
 }
 
 // Forward of a generic-stage model (option "generic_stages"): one k_stage_any launch per stage, rows ping-ponging through the
-// scratch buffers.  No plan, no pad row (the kernel reads rows of neighbours only), nothing cached between calls.
+// scratch buffers.  No plan, no pad row (the kernel reads rows of neighbours only), nothing cached between calls.  In an audited
+// call (gnnvc_forward_audited*) each stage's check (k_audit_any) is queued right behind its launch.
 int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_logits) {
     const uint32_t n = e->g.n;
     const std::vector<StagePlan> &st = e->gstages;
@@ -713,6 +720,11 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
         const bool last = s + 1 == st.size();
         float *dst = last ? d_out : e->scratch[s & 1].p;
         HIP_TRY(e, gnnvc::launch_stage_any(stage_call(e, st[s], cur, dst, last ? d_logits : nullptr, 0, n)));
+        if (e->audit_now) {   // (gnnvc_forward_audited* only: "audit_period" never sets it for a generic-stage model)
+            std::string plan = "k_stage_any";
+            const int rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan);
+            if (rc != GNNVC_OK) return rc;
+        }
         cur = dst;
     }
     return GNNVC_OK;
@@ -1498,6 +1510,30 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     return rc;
 }
 
+// A pure check of the caller's buffers: no stage runs, the test hook does not apply, the period's counter is not ticked
+int gnnvc_audit_stage_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint32_t row_hi, const float *d_in, float *d_out,
+                             float *d_logits) {
+    if (!e) return GNNVC_ERR_INVALID;
+    NOT_ON_MULTI(e, "gnnvc_audit_stage_device");
+    if (!e->have_graph) return fail(e, GNNVC_ERR_STATE, "no graph attached");
+    if (stage < 0 || stage >= (int)e->stage_list().size()) return fail(e, GNNVC_ERR_INVALID, "stage %d out of range", stage);
+    if (row_lo > row_hi || row_hi > e->g.n) return fail(e, GNNVC_ERR_INVALID, "row range [%u,%u) outside graph of %u", row_lo, row_hi, e->g.n);
+    if (row_lo == row_hi) return GNNVC_OK;
+    if (e->empty_slice || row_lo < e->g.lo() || row_hi > e->g.hi())
+        return fail(e, GNNVC_ERR_INVALID, "rows [%u,%u) are not in the slice [%u,%u) this engine holds", row_lo, row_hi, e->g.lo(),
+                    e->empty_slice ? e->g.lo() : e->g.hi());
+    if (!d_in || !d_out) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
+    int rc = use_device(e);
+    if (rc) return rc;
+    e->audit_pending.clear();
+    e->audit_now = true;
+    std::string plan = e->generic_on() ? "the caller's buffers (k_stage_any's, if gnnvc_stage_forward_device filled them)" : "the caller's buffers";
+    rc = audit_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits, plan, /*hook=*/false);
+    rc = audit_finish(e, rc);
+    if (e->opt.audit_log) audit_log_line(e, rc);
+    return rc;
+}
+
 static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits);
 
 // option "audit_log": one stderr line per audited call with the engine's counters (for drivers that cannot read them)
@@ -1510,9 +1546,9 @@ static void audit_log_line(const gnnvc_engine *e, int rc) {
             rc == GNNVC_ERR_AUDIT ? " — " : "", rc == GNNVC_ERR_AUDIT ? e->err.c_str() : "");
 }
 
-int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits) {
-    if (!e) return GNNVC_ERR_INVALID;
-    const bool audit = audit_tick(e);
+// gnnvc_forward_device (audit = this call's turn by "audit_period") and gnnvc_forward_audited_device (explicit = true: every
+// fused stage audited in this call, generic stages included)
+static int forward_device_impl(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits, bool audit, bool explicit_audit) {
     if (e->multi) {   // pointers on the first device; complete (every device drained) when it returns
         if (!gnnvc::multi_has_graph(e->multi)) return fail(e, GNNVC_ERR_STATE, "no graph attached");
         if (gnnvc::multi_vertices(e->multi) == 0) return GNNVC_OK;
@@ -1527,11 +1563,28 @@ int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, flo
         if (audit && e->opt.audit_log) audit_log_line(e, rc);
         return rc;
     }
-    // (an unfused model runs the layer-by-layer kernels, a generic-stage model k_stage_any: nothing to audit)
-    e->audit_now = audit && !e->stages.empty() && !e->generic_on();
+    if (explicit_audit) {
+        if (!e->have_graph) return fail(e, GNNVC_ERR_STATE, "no graph attached");
+        if (e->layers.empty()) return fail(e, GNNVC_ERR_STATE, "engine was created without a model");
+        if (e->stage_list().empty()) return fail(e, GNNVC_ERR_UNSUPPORTED, "model is not fused into stages: there is nothing to audit");
+        e->audit_now = true;
+    } else {
+        // (an unfused model runs the layer-by-layer kernels, a generic-stage model k_stage_any: the period audits nothing)
+        e->audit_now = audit && !e->stages.empty() && !e->generic_on();
+    }
     const int rc = audit_finish(e, forward_single(e, d_x, d_scores, d_logits));
     if (audit && e->opt.audit_log) audit_log_line(e, rc);
     return rc;
+}
+
+int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits) {
+    if (!e) return GNNVC_ERR_INVALID;
+    return forward_device_impl(e, d_x, d_scores, d_logits, audit_tick(e), /*explicit_audit=*/false);
+}
+
+int gnnvc_forward_audited_device(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits) {
+    if (!e) return GNNVC_ERR_INVALID;
+    return forward_device_impl(e, d_x, d_scores, d_logits, /*audit=*/true, /*explicit_audit=*/true);   // (the period's counter is not ticked)
 }
 
 static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits) {
@@ -1714,8 +1767,9 @@ int gnnvc_stage_input_ready(gnnvc_engine *e, int stage, const float *d_in, uint3
     return GNNVC_OK;
 }
 
-int gnnvc_forward(gnnvc_engine *e, const float *x, float *scores, float *logits) {
-    if (!e) return GNNVC_ERR_INVALID;
+// gnnvc_forward, and gnnvc_forward_audited (audited = true)
+static int forward_host(gnnvc_engine *e, const float *x, float *scores, float *logits, bool audited) {
+    const auto device_forward = audited ? gnnvc_forward_audited_device : gnnvc_forward_device;
     if (e->multi) {
         if (!gnnvc::multi_has_graph(e->multi)) return fail(e, GNNVC_ERR_STATE, "no graph attached");
         const uint32_t n = gnnvc::multi_vertices(e->multi);
@@ -1726,7 +1780,7 @@ int gnnvc_forward(gnnvc_engine *e, const float *x, float *scores, float *logits)
         const size_t bytes = (size_t)n * sizeof(float);
         HIP_TRY(e, hipMemcpyAsync(e->x.p, x, bytes, hipMemcpyHostToDevice, e->stream));
         const bool want_logits = logits && e->ends_in_sigmoid;
-        rc = gnnvc_forward_device(e, e->x.p, e->scores.p, want_logits ? e->logits.p : nullptr);
+        rc = device_forward(e, e->x.p, e->scores.p, want_logits ? e->logits.p : nullptr);
         if (rc && rc != GNNVC_ERR_AUDIT) return rc;   // (a failed audit: the outputs as the fused path wrote them, and the error)
         HIP_TRY(e, hipMemcpyAsync(scores, e->scores.p, bytes, hipMemcpyDeviceToHost, e->stream));
         if (want_logits) HIP_TRY(e, hipMemcpyAsync(logits, e->logits.p, bytes, hipMemcpyDeviceToHost, e->stream));
@@ -1736,6 +1790,7 @@ int gnnvc_forward(gnnvc_engine *e, const float *x, float *scores, float *logits)
     if (!e->have_graph) return fail(e, GNNVC_ERR_STATE, "no graph attached");
     const uint32_t n = e->g.n;
     if (e->layers.empty()) return fail(e, GNNVC_ERR_STATE, "engine was created without a model");
+    if (audited && e->stage_list().empty()) return fail(e, GNNVC_ERR_UNSUPPORTED, "model is not fused into stages: there is nothing to audit");
     if (n == 0) return GNNVC_OK;
     // (before the copy below: a sliced engine has no feature buffers of its own — e->x may be null or sized for an earlier graph)
     if (e->g.sliced() || e->empty_slice)
@@ -1748,13 +1803,23 @@ int gnnvc_forward(gnnvc_engine *e, const float *x, float *scores, float *logits)
     const size_t out_b = (size_t)n * e->out_width * sizeof(float);
     HIP_TRY(e, hipMemcpyAsync(e->x.p, x, in_b, hipMemcpyHostToDevice, e->stream));
     const bool want_logits = logits && e->ends_in_sigmoid;
-    rc = gnnvc_forward_device(e, e->x.p, e->scores.p, want_logits ? e->logits.p : nullptr);
+    rc = device_forward(e, e->x.p, e->scores.p, want_logits ? e->logits.p : nullptr);
     if (rc && rc != GNNVC_ERR_AUDIT) return rc;   // (a failed audit: the outputs as the fused path wrote them, and the error)
     HIP_TRY(e, hipMemcpyAsync(scores, e->scores.p, out_b, hipMemcpyDeviceToHost, e->stream));
     if (want_logits)
         HIP_TRY(e, hipMemcpyAsync(logits, e->logits.p, out_b, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     return rc;
+}
+
+int gnnvc_forward(gnnvc_engine *e, const float *x, float *scores, float *logits) {
+    if (!e) return GNNVC_ERR_INVALID;
+    return forward_host(e, x, scores, logits, /*audited=*/false);
+}
+
+int gnnvc_forward_audited(gnnvc_engine *e, const float *x, float *scores, float *logits) {
+    if (!e) return GNNVC_ERR_INVALID;
+    return forward_host(e, x, scores, logits, /*audited=*/true);
 }
 
 int gnnvc_reduction_flags(gnnvc_engine *e, uint32_t max_degree, uint8_t *flags) {

@@ -185,6 +185,10 @@ hipError_t write_verdicts(const VerdictWords &vw, uint32_t *out_dev, hipStream_t
 // fused bits), [5] ~(row << 32 | audit bits).  repair: the audit's value is written over every mismatching one.
 constexpr int kAuditWords = 8;
 hipError_t launch_audit_stage(const StageCall &c, unsigned long long *rec, bool repair);
+// The same check of a GENERIC stage (k_audit_any, gnnvc_audit_any.hip; any shape stage_any_fits accepts): a wave per row, lane o
+// = output o, the weights read as stored — nothing shared with k_stage_any or k_audit_stage.  The same record; [0] is the exact
+// number of mismatching values, [1] counts every pair of NaNs (k_audit_stage: those whose bits differ).
+hipError_t launch_audit_any(const StageCall &c, unsigned long long *rec, bool repair);
 // the audit's test hook: out[at]'s lowest mantissa bit flipped by one lane
 hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 

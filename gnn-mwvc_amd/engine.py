@@ -25,7 +25,8 @@ ABI_SYMBOLS = [
     "gnnvc_in_width", "gnnvc_out_width", "gnnvc_upload_graph", "gnnvc_attach_graph_device", "gnnvc_attach_graph_slice",
     "gnnvc_graph_staging", "gnnvc_staged_columns_ready", "gnnvc_commit_staged_graph",
     "gnnvc_derive_graph_begin", "gnnvc_derive_graph_commit", "gnnvc_graph_row_hashes",
-    "gnnvc_forward", "gnnvc_forward_device", "gnnvc_num_stages", "gnnvc_stage_widths",
+    "gnnvc_forward", "gnnvc_forward_device", "gnnvc_forward_audited", "gnnvc_forward_audited_device", "gnnvc_audit_stage_device",
+    "gnnvc_num_stages", "gnnvc_stage_widths",
     "gnnvc_stage_forward_device", "gnnvc_stage_input_ready", "gnnvc_live_columns", "gnnvc_column_counts", "gnnvc_pack_rows", "gnnvc_unpack_rows", "gnnvc_unpack_gathered",
     "gnnvc_push_piece", "gnnvc_unpack_pieces", "gnnvc_get_stream",
     "gnnvc_reduction_flags", "gnnvc_score_keys", "gnnvc_synchronize", "gnnvc_last_forward_ms",
@@ -118,6 +119,9 @@ def load_library():
     L.gnnvc_forward.argtypes = [vp, f32p, f32p, f32p]
     L.gnnvc_forward_device.argtypes = [vp, f32p, f32p, f32p]
     L.gnnvc_stage_forward_device.argtypes = [vp, C.c_int, u32, u32, f32p, f32p, f32p]
+    L.gnnvc_forward_audited.argtypes = [vp, f32p, f32p, f32p]
+    L.gnnvc_forward_audited_device.argtypes = [vp, f32p, f32p, f32p]
+    L.gnnvc_audit_stage_device.argtypes = [vp, C.c_int, u32, u32, f32p, f32p, f32p]
     L.gnnvc_reduction_flags.argtypes = [vp, u32, vp]
     L.gnnvc_stage_input_ready.argtypes = [vp, C.c_int, f32p, u32, u32]
     L.gnnvc_score_keys.argtypes = [vp, f32p, u32, vp, vp]
@@ -309,6 +313,14 @@ class Engine:
     def forward(self, x: np.ndarray, want_logits: bool = True, out=None):
         """Host forward: returns (scores[n, out_width], logits or None).  `out` = (scores, logits) arrays to fill
         instead of new ones (a caller that times the call keeps first-touch page faults out of it that way)."""
+        return self._forward_host(self._L.gnnvc_forward, x, want_logits, out)
+
+    def forward_audited(self, x: np.ndarray, want_logits: bool = True, out=None):
+        """`forward` with every fused stage audited in this call (gnnvc_forward_audited), generic stages included, whatever
+        "audit_period" says.  A mismatch raises GnnvcError with is_audit true (code -6); audit_report() has the details."""
+        return self._forward_host(self._L.gnnvc_forward_audited, x, want_logits, out)
+
+    def _forward_host(self, entry, x, want_logits, out):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n, self.in_width)
         if out is not None:
             scores, logits = out
@@ -318,8 +330,7 @@ class Engine:
         else:
             scores = np.empty((self.n, self.out_width), dtype=np.float32)
             logits = np.empty((self.n, self.out_width), dtype=np.float32) if want_logits else None
-        self._check(self._L.gnnvc_forward(self._h, _np_ptr(x), _np_ptr(scores),
-                                          _np_ptr(logits) if want_logits else None))
+        self._check(entry(self._h, _np_ptr(x), _np_ptr(scores), _np_ptr(logits) if want_logits else None))
         return scores, logits
 
     def forward_device(self, x_ptr: int, scores_ptr: int, logits_ptr: int = 0):
@@ -329,6 +340,15 @@ class Engine:
                              logits_ptr: int = 0):
         self._check(self._L.gnnvc_stage_forward_device(self._h, stage, row_lo, row_hi, in_ptr,
                                                        out_ptr, logits_ptr or None))
+
+    def forward_audited_device(self, x_ptr: int, scores_ptr: int, logits_ptr: int = 0):
+        """`forward_device` with every fused stage audited in this call; synchronises the engine's stream."""
+        self._check(self._L.gnnvc_forward_audited_device(self._h, x_ptr, scores_ptr, logits_ptr or None))
+
+    def audit_stage_device(self, stage: int, row_lo: int, row_hi: int, in_ptr: int, out_ptr: int, logits_ptr: int = 0):
+        """Check rows [row_lo, row_hi) of out_ptr (and logits_ptr) against what `stage` computes from in_ptr; runs no stage.
+        A mismatch raises GnnvcError with is_audit true unless "audit_repair" is 1, which writes the audit's values over it."""
+        self._check(self._L.gnnvc_audit_stage_device(self._h, stage, row_lo, row_hi, in_ptr, out_ptr, logits_ptr or None))
 
     def stage_input_ready(self, stage: int, in_ptr: int, row_lo: int, row_hi: int):
         """Announce the complete, final input of `stage` before computing rows [row_lo, row_hi) of it in pieces."""

@@ -260,7 +260,11 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         stages and returns GNNVC_ERR_AUDIT, gnnvc_last_error naming the stage, its row range, the number of
  *                         mismatching values, the first row and column with both bit patterns in hex, and the plan that produced
  *                         the stage; the engine stays usable.  Unfused models and generic-stage models (option "generic_stages")
- *                         audit nothing.  Default 0 (off).
+ *                         audit nothing under the period: on a generic-stage model a call whose turn it is runs unaudited and
+ *                         counts nothing.  The explicit calls audit them: gnnvc_forward_audited and
+ *                         gnnvc_forward_audited_device audit every fused stage of one forward, whatever the period says and
+ *                         without ticking its counter, and gnnvc_audit_stage_device checks rows the caller holds — for the
+ *                         trained shapes and for generic stages alike (see "forward" below).  Default 0 (off).
  *   "audit_repair" 0|1    1 = the audit writes its own values over the mismatching ones: the call returns GNNVC_OK with correct
  *                         outputs (a repaired stage hands correct rows to the next one) and counts the repair.  Default 0.
  *   "audit_log" 0|1       1 = every audited call prints one stderr line, "gnnvc audit: audit_runs <n> audit_failures <n>
@@ -273,7 +277,8 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         mantissa bit of output value (r, 0) is flipped between the stage and its audit.  Unaudited calls are
  *                         never touched.  Default -1 (off).
  *                         gnnvc_get_info: "audit_runs" (stage checks done), "audit_failures" (checks with a mismatch),
- *                         "audit_repairs" (values repaired), "audit_nan_pairs" (NaN pairs taken as equal), and of the first
+ *                         "audit_repairs" (values repaired), "audit_nan_pairs" (NaN pairs taken as equal: with different bits
+ *                         on the trained shapes, every pair on generic stages), and of the first
  *                         failing check of the last failing call: "audit_last_stage", "audit_last_row", "audit_last_col",
  *                         "audit_last_mismatches", "audit_last_fused_bits", "audit_last_plain_bits" (-1 / 0 before any).  A
  *                         multi-device handle decides per forward whether its parts audit; it sums their counters and reports
@@ -294,8 +299,12 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         A model whose every stage is of a trained shape is planned, launched and audited as ever.
  *                         0: such a model is not fused, has 0 stages and runs layer by layer (one launch per layer), as
  *                         before this option existed.  2 (tests): the trained shape is sent through the generic kernel as well,
- *                         none of its plans used.  Generic stages have no per-graph plan and no audit ("audit_period" audits
- *                         nothing on them, as on an unfused model); gnnvc_stage_input_ready, the row codec (16-column rows) and
+ *                         none of its plans used.  Generic stages have no per-graph plan, and "audit_period" audits nothing on
+ *                         them, as on an unfused model: they are audited on demand, by gnnvc_forward_audited,
+ *                         gnnvc_forward_audited_device and gnnvc_audit_stage_device (kernel k_audit_any: a wave per row, the
+ *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
+ *                         "audit_repair", "audit_quiet", "audit_log" and "audit_flip_*" options and every "audit_*" read-out
+ *                         apply to it).  gnnvc_stage_input_ready, the row codec (16-column rows) and
  *                         gnnvc_create_multi with several devices keep returning GNNVC_ERR_UNSUPPORTED for them.  On a
  *                         multi-device handle the option is stored and changes nothing.  gnnvc_get_info: "generic_stages",
  *                         "generic_stages_model" (1 = a forward would run the generic kernel now), "generic_stages_active"
@@ -411,6 +420,19 @@ int gnnvc_forward(gnnvc_engine *e, const float *x, float *scores, float *logits)
  * the engine's stream (an audited call synchronises it: option "audit_period").  d_logits may be NULL. */
 int gnnvc_forward_device(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits);
 
+/* The same two forwards with EVERY fused stage audited in this one call, whatever "audit_period" says (the period's call counter
+ * is not ticked): each stage is recomputed right behind its launch, before the next stage is queued, and compared bit for bit
+ * with every value the fused path wrote, as described under "audit_period".  A model of the trained shapes is audited by the
+ * kernel the period uses (k_audit_stage); a generic-stage model (option "generic_stages"), which the period does not audit, by
+ * k_audit_any.  The call synchronises its stream once, at its end.  GNNVC_OK: the audit was clean.  GNNVC_ERR_AUDIT: values
+ * differ — the outputs are as the fused path wrote them, all stages have run, gnnvc_last_error carries the report and the engine
+ * stays usable; with "audit_repair" 1 the values are repaired and the call returns GNNVC_OK.  The "audit_*" counters and
+ * read-outs are updated as by any audited call, and "audit_quiet", "audit_log" and the "audit_flip_*" hooks apply.  A model that
+ * runs layer by layer (gnnvc_is_fused = 0) has no stage to audit: GNNVC_ERR_UNSUPPORTED.  A graph of no vertices: GNNVC_OK,
+ * nothing done.  A multi-device handle audits this forward on all its parts. */
+int gnnvc_forward_audited(gnnvc_engine *e, const float *x, float *scores, float *logits);
+int gnnvc_forward_audited_device(gnnvc_engine *e, const float *d_x, float *d_scores, float *d_logits);
+
 /* One fused stage (graph layer + the dense layers up to the next graph
  * layer) over the vertex range [row_lo, row_hi) — the unit a 1-D
  * vertex-partitioned multi-GPU run executes between feature exchanges.
@@ -423,6 +445,17 @@ int gnnvc_num_stages(const gnnvc_engine *e);
 int gnnvc_stage_widths(const gnnvc_engine *e, int stage, int *in_width, int *out_width);
 int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint32_t row_hi,
                                const float *d_in, float *d_out, float *d_logits);
+
+/* A pure check that runs no stage: are rows [row_lo, row_hi) of d_out what stage `stage` computes from d_in — and, on the stage
+ * that ends in the sigmoid, those rows of d_logits too, when it is not NULL?  The buffers are laid out as for
+ * gnnvc_stage_forward_device, and the same argument checks and slice rules hold (a sliced engine checks rows of its slice; an
+ * empty range is GNNVC_OK).  Any fused model: the trained shapes (k_audit_stage) and generic stages (k_audit_any).  One
+ * read-back; the call SYNCHRONISES the engine's stream.  Return codes, counters and read-outs as for gnnvc_forward_audited;
+ * with "audit_repair" 1 the audit's values are written over the mismatching ones (hence d_out and d_logits are not const).  The
+ * "audit_flip_*" hooks do not apply — the caller owns the buffers — and the period's call counter is not ticked.  A multi-device
+ * handle: GNNVC_ERR_UNSUPPORTED. */
+int gnnvc_audit_stage_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint32_t row_hi,
+                             const float *d_in, float *d_out, float *d_logits);
 
 /* ---- feature-row codec for the exchange between vertex-partitioned GPUs --------
  * No reference counterpart (the reference is single-process).  After the ReLU that ends a fused
