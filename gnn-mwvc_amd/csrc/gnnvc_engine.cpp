@@ -705,9 +705,41 @@ int forward_unfused(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
     return GNNVC_OK;
 }
 
-// Forward of a generic-stage model (option "generic_stages"): one k_stage_any launch per stage, rows ping-ponging through the
-// scratch buffers.  No plan, no pad row (the kernel reads rows of neighbours only), nothing cached between calls.  In an audited
-// call (gnnvc_forward_audited*) each stage's check (k_audit_any) is queued right behind its launch.
+// One generic stage over [lo, hi): one k_stage_any launch — or, on a graph with heavy rows (gnnvc_set_generic_heavy_rows,
+// class_heavy_rows), three: the heavy rows' sums a workgroup per row (k_any_heavy_sums), k_stage_any over the light rows, and
+// k_stage_any over the listed rows with their sums read back.  The sums kernel goes to the side queue beside the light rows
+// (fork / join as launch_side_rows) or ahead of them on the main stream (heavy_overlap()); the listed rows' launch follows both.
+int run_generic_stage(gnnvc_engine *e, const StagePlan &sp, const float *in, float *out, float *logits, uint32_t lo, uint32_t hi) {
+    {   // (lazily: option "generic_stages" set after the attach, or a threshold that has moved)
+        const int rc = class_heavy_rows(e);
+        if (rc) return rc;
+    }
+    const gnnvc::StageCall call = stage_call(e, sp, in, out, logits, lo, hi);
+    e->heavy_last_rows = e->pg.heavy_rows;
+    if (!e->pg.heavy_rows) {
+        HIP_TRY(e, gnnvc::launch_stage_any(call));
+        return GNNVC_OK;
+    }
+    const gnnvc::AnyHeavyRows hr{.list = e->heavy_list.p, .n = e->pg.heavy_rows, .from = e->pg.heavy_thresh, .hsum = e->heavy_sum.p};
+    const bool side = heavy_overlap() && e->aux_stream;
+    gnnvc::StageCall sums = call;
+    if (side) {
+        HIP_TRY(e, hipEventRecord(e->ev_fork, e->stream));
+        HIP_TRY(e, hipStreamWaitEvent(e->aux_stream, e->ev_fork, 0));
+        sums.stream = e->aux_stream;
+    }
+    HIP_TRY(e, gnnvc::launch_any_heavy_sums(sums, hr));
+    if (side) HIP_TRY(e, hipEventRecord(e->ev_join, e->aux_stream));
+    HIP_TRY(e, gnnvc::launch_stage_any(call, gnnvc::AnyRows::kLight, hr));
+    if (side) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_join, 0));
+    HIP_TRY(e, gnnvc::launch_stage_any(call, gnnvc::AnyRows::kListed, hr));
+    return GNNVC_OK;
+}
+
+// Forward of a generic-stage model (option "generic_stages"): one k_stage_any launch per stage (three on a graph with heavy rows,
+// run_generic_stage), rows ping-ponging through the scratch buffers.  No pad row (the kernels read rows of neighbours only),
+// nothing cached between calls but the list of heavy rows.  In an audited call (gnnvc_forward_audited*) each stage's check
+// (k_audit_any) is queued right behind its launches.
 int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_logits) {
     const uint32_t n = e->g.n;
     const std::vector<StagePlan> &st = e->gstages;
@@ -719,9 +751,12 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
     for (size_t s = 0; s < st.size(); ++s) {
         const bool last = s + 1 == st.size();
         float *dst = last ? d_out : e->scratch[s & 1].p;
-        HIP_TRY(e, gnnvc::launch_stage_any(stage_call(e, st[s], cur, dst, last ? d_logits : nullptr, 0, n)));
+        {
+            const int rc = run_generic_stage(e, st[s], cur, dst, last ? d_logits : nullptr, 0, n);
+            if (rc != GNNVC_OK) return rc;
+        }
         if (e->audit_now) {   // (gnnvc_forward_audited* only: "audit_period" never sets it for a generic-stage model)
-            std::string plan = "k_stage_any";
+            std::string plan = e->heavy_last_rows ? "k_stage_any (light rows, listed rows) + k_any_heavy_sums" : "k_stage_any";
             const int rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan);
             if (rc != GNNVC_OK) return rc;
         }
@@ -882,6 +917,13 @@ int gnnvc_set_option(gnnvc_engine *e, const char *key, long value) {
     return (fx & gnnvc::kFxForward) && e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
 }
 
+int gnnvc_set_generic_heavy_rows(gnnvc_engine *e, uint32_t from_degree) {
+    if (!e) return GNNVC_ERR_INVALID;
+    NOT_ON_MULTI(e, "gnnvc_set_generic_heavy_rows");
+    e->heavy_from = from_degree;   // (the attached graph is classed again by the next generic stage that runs: class_heavy_rows)
+    return GNNVC_OK;
+}
+
 int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     if (!e || !key || !value) return GNNVC_ERR_INVALID;
     const std::string k(key);
@@ -900,6 +942,10 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k == "generic_stages_model") *value = e->generic_on() ? 1 : 0;   // would a forward run k_stage_any now
     else if (k == "generic_stages_active") *value = e->generic_ran ? 1 : 0;   // did the last one
     else if (k == "generic_max_dense_layers") *value = gnnvc::kMaxDenseLayers;
+    else if (k == "generic_heavy_from") *value = (long)e->heavy_from;                 // gnnvc_set_generic_heavy_rows
+    else if (k == "generic_heavy_rows") *value = (long)e->pg.heavy_rows;              // the attached graph's last classing
+    else if (k == "generic_heavy_entries") *value = (long)e->pg.heavy_entries;
+    else if (k == "generic_heavy_last_rows") *value = (long)e->heavy_last_rows;       // 0: the last call launched one kernel a stage
     else if (k.rfind("generic_stage_layers_", 0) == 0) {   // "generic_stage_layers_<s>": dense layers of stage s of a generic model
         const char *num = k.c_str() + sizeof("generic_stage_layers_") - 1;
         char *end = nullptr;
@@ -1495,10 +1541,10 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     if (!d_in || !d_out) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
     int rc = use_device(e);
     if (rc) return rc;
-    if (e->generic_on()) {   // (k_stage_any: one launch, no plan; a generic stage audits nothing)
+    e->heavy_last_rows = 0;
+    if (e->generic_on()) {   // (k_stage_any, with k_any_heavy_sums on a graph with heavy rows; a generic stage audits nothing)
         const StagePlan &sp = e->gstages[stage];
-        HIP_TRY(e, gnnvc::launch_stage_any(stage_call(e, sp, d_in, d_out, sp.sigmoid_last ? d_logits : nullptr, row_lo, row_hi)));
-        return GNNVC_OK;
+        return run_generic_stage(e, sp, d_in, d_out, sp.sigmoid_last ? d_logits : nullptr, row_lo, row_hi);
     }
     if (!audit) return run_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits);
     e->audit_now = true;
@@ -1599,6 +1645,7 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     int rc = use_device(e);
     if (rc) return rc;
     e->generic_ran = e->generic_on();
+    e->heavy_last_rows = 0;   // (run_generic_stage sets it)
     if (e->generic_ran || e->stages.empty()) {
         rc = ensure_events(e, 2);
         if (rc) return rc;

@@ -63,6 +63,11 @@ struct gnnvc_engine {
     bool generic_ran = false;       // gnnvc_get_info "generic_stages_active": the last forward ran k_stage_any
     bool generic_on() const { return !gstages.empty() && (opt.generic == 2 || (opt.generic == 1 && stages.empty())); }
     const std::vector<StagePlan> &stage_list() const { return generic_on() ? gstages : stages; }   // what the ABI reports and runs
+    // Heavy rows of generic stages (gnnvc_set_generic_heavy_rows): rows of at least heavy_from entries (0: none) get a workgroup
+    // each for their sums (k_any_heavy_sums), beside or ahead of the light rows' k_stage_any.  The list and the sums are the
+    // engine's; what is known about the current graph is in pg.heavy_*.
+    uint32_t heavy_from = 512;      // the trained path's long-row threshold
+    uint32_t heavy_last_rows = 0;   // gnnvc_get_info "generic_heavy_last_rows": listed rows of the last forward / stage call (0 = one launch)
     int in_width = 1, out_width = 1;
     int max_width = 1;
     bool ends_in_sigmoid = false;
@@ -105,6 +110,10 @@ struct gnnvc_engine {
         uint32_t fit_calm = 0;              // verdicts in a row that changed nothing: from four on, only every eighth forward asks
         uint32_t fit_skip = 0;
         int short_from = 0;                 // the stage whose filtered call left short lists (0 = none), see short_min
+        // generic stages: the graph's heavy rows (class_heavy_rows) — known = classed, at the threshold heavy_thresh
+        bool heavy_known = false;
+        uint32_t heavy_rows = 0, heavy_thresh = 0;
+        uint64_t heavy_entries = 0;
         double plan_build_ms = 0.0;         // host wall time spent building per-graph plans for the current graph (they end in stream syncs)
         double early_ms = 0.0;              // host time the hand-off spent classing the graph and queuing builds before the commit
     };
@@ -255,6 +264,9 @@ struct gnnvc_engine {
     // long rows (degree >= long_thresh): one workgroup each, on aux_stream beside the tile kernel
     uint32_t long_thresh = 0xFFFFFFFFu, n_long = 0;
     DevBuf<uint32_t> long_list, long_count;
+    // generic stages' heavy rows (heavy_from above): find_long_rows' list and count words, and the sums — rows x the widest stage input
+    DevBuf<uint32_t> heavy_list, heavy_count;
+    DevBuf<float> heavy_sum;
     // what classify_hand_off learned about a graph in its one round trip, for the find_long that follows it
     struct PreClass {
         bool valid = false, cuts = false, waste = false, longs = false;
@@ -364,8 +376,21 @@ inline int use_device(gnnvc_engine *e) {
     return GNNVC_OK;
 }
 
+// Generic stages' heavy rows: do the sums (k_any_heavy_sums) run on the side queue beside the light rows' k_stage_any, or do the
+// three launches follow each other on the main stream?  The environment variable GNNVC_HEAVY_OVERLAP (0 | 1, read once per
+// process) overrides the default, so that both orders can be measured with one library (profiles/generic_stages/README.md).
+constexpr bool kHeavyOverlapDefault = true;
+inline bool heavy_overlap() {
+    static const bool on = [] {
+        const char *s = getenv("GNNVC_HEAVY_OVERLAP");
+        return s && *s ? atoi(s) != 0 : kHeavyOverlapDefault;
+    }();
+    return on;
+}
+
 // ---- gnnvc_plans.cpp: what is built per graph -------------------------------------------------------------------------
 int find_long(gnnvc_engine *e);                              // row classes of a new graph (long / giant rows, tile waste)
+int class_heavy_rows(gnnvc_engine *e);                       // generic stages: the heavy rows of the current graph, once per graph and threshold
 int ensure_sorted(gnnvc_engine *e, uint32_t lo, uint32_t hi);
 int build_blocked(gnnvc_engine *e);
 int build_lds_table(gnnvc_engine *e);

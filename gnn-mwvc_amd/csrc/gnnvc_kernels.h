@@ -200,7 +200,18 @@ hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 // (no plan); rows of every degree.  in: (n + 1) x f rows (the pad row is never read), out: rows [row_lo, row_hi) of an
 // (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
 bool stage_any_fits(const StagePlan &sp);
-hipError_t launch_stage_any(const StageCall &c);
+// Heavy rows of a generic stage (gnnvc_set_generic_heavy_rows): rows of at least `from` entries, listed by find_long_rows, get a
+// workgroup each for their neighbour sums (k_any_heavy_sums: hsum[i * f + c] for list position i, the same chain per column in
+// stored order) and k_stage_any is launched twice — over the rows below `from` (kLight), then over the listed ones with their
+// sums read from hsum (kListed); both skip what lies outside [row_lo, row_hi).  kAll: one launch, every row, hr unused.
+struct AnyHeavyRows {
+    const uint32_t *list = nullptr;
+    uint32_t n = 0, from = 0;
+    float *hsum = nullptr;   // n x (the stage's f) floats
+};
+enum class AnyRows { kAll, kLight, kListed };
+hipError_t launch_stage_any(const StageCall &c, AnyRows rows = AnyRows::kAll, const AnyHeavyRows &hr = AnyHeavyRows());
+hipError_t launch_any_heavy_sums(const StageCall &c, const AnyHeavyRows &hr);
 
 // a whole stage (variants 0, 1, 2) on WIDE tiles — a workgroup per 64-vertex tile, the tile's gather and each dense layer's outputs
 // split over its four waves (k_stage_w1 / k_stage_w16): graphs with fewer tiles than the chip has SIMDs, no long rows

@@ -234,6 +234,38 @@ int find_long(gnnvc_engine *e) {
     return find_giant(e);
 }
 
+// Generic stages' heavy rows (gnnvc_set_generic_heavy_rows): the rows this engine holds of at least heavy_from entries, listed
+// by find_long_rows with one 16-byte read-back.  Runs at hand-off for an engine whose generic stage list is in force
+// (prepare_plans) and otherwise the first time a generic stage runs on the graph; again after the threshold has moved.  The
+// trained model's default path never comes here.
+int class_heavy_rows(gnnvc_engine *e) {
+    gnnvc_engine::PerGraph &pg = e->pg;
+    if (pg.heavy_known && pg.heavy_thresh == e->heavy_from) return GNNVC_OK;
+    pg.heavy_known = true;
+    pg.heavy_thresh = e->heavy_from;
+    pg.heavy_rows = 0;
+    pg.heavy_entries = 0;
+    const GraphDev &g = e->g;
+    if (!e->heavy_from || e->empty_slice || g.n == 0 || g.nnz == 0 || g.hi() <= g.lo()) return GNNVC_OK;
+    HIP_TRY(e, e->heavy_list.reserve(g.hi() - g.lo()));
+    HIP_TRY(e, e->heavy_count.reserve(4));
+    uint32_t found[4] = {0, 0, 0, 0};   // {rows, -, their entries (64 bits)}
+    HIP_TRY(e, gnnvc::find_long_rows(g, e->heavy_from, e->heavy_list.p, e->heavy_count.p, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(found, e->heavy_count.p, sizeof found, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (found[0] == 0) return GNNVC_OK;
+    int fmax = 1;
+    for (const StagePlan &sp : e->gstages) fmax = std::max(fmax, sp.f);
+    HIP_TRY(e, e->heavy_sum.reserve((size_t)found[0] * (size_t)fmax));
+    if (heavy_overlap()) {   // the sums run on the side queue, beside the light rows
+        const int rc = ensure_side_streams(e);
+        if (rc) return rc;
+    }
+    pg.heavy_rows = found[0];
+    pg.heavy_entries = (uint64_t)found[2] | ((uint64_t)found[3] << 32);
+    return GNNVC_OK;
+}
+
 // The rows of [lo, hi) below the long-row threshold of the 16-wide stages, heaviest degree class first: vertex[] (+ per
 // row {first entry, end, W, NW} in meta[]); listed = how many, zero_rows = how many of them (the list's tail) have no entry.
 int sort_by_degree_async(gnnvc_engine *e, uint32_t lo, uint32_t hi, DevBuf<uint32_t> &vertex, DevBuf<uint4> &meta, uint32_t *pin_out /* [2] */,
@@ -1241,6 +1273,10 @@ int prepare_plans(gnnvc_engine *e) {
     e->handoff_build_ms = 0.0;
     {
         const int rc = prepare_table_tiles(e);
+        if (rc) return rc;
+    }
+    if (e->generic_on()) {   // (k_stage_any's heavy rows: one pass over the row pointers, one 16-byte read-back)
+        const int rc = class_heavy_rows(e);
         if (rc) return rc;
     }
     if (!e->opt.handoff || e->stages.empty() || e->g.n == 0 || e->empty_slice) return GNNVC_OK;

@@ -24,7 +24,8 @@
 //   gather   lane j owns neighbour columns j and j + 16.  The group fetches the column ids of a round (32 entries; 16 when
 //            f > 16), the next round's already on their way, issues the round's 32 row loads per lane, then adds them in
 //            order.  f = 1: every lane fetches one neighbour's value per 16 entries, 64 entries a round, and all lanes add
-//            them in the same order.  Rows of any degree take this loop.
+//            them in the same order.  Rows of any degree can take this loop; the heavy ones get their
+//            sums from k_any_heavy_sums instead (below), which changes who adds, not what is added.
 //   dense    the outputs of a layer are dealt to the lanes (o = j + 16 t); a lane runs its outputs' chains together, four
 //            k at a time: one 16-byte read of the group's input vector (same address for the group) and one per output of
 //            its transposed weight row.  The number of outputs per lane (1 .. 4) is a template argument chosen by a
@@ -241,9 +242,25 @@ __device__ __forceinline__ float any_gather1(const uint32_t *__restrict__ col, c
     return s;
 }
 
+// Which rows a launch takes (the arithmetic behind the sums is one source for all three):
+//   kAnyAll     every row of [lo, hi) — a graph without heavy rows launches this and nothing else;
+//   kAnyLight   the rows of [lo, hi) below `from` entries;
+//   kAnyListed  the rows list[0 .. nlist) that lie in [lo, hi): a group's row is list[i], its sums are hsum[i * f + c]
+//               (k_any_heavy_sums below wrote them), there is no gather.
+// MODE is a template argument, not a kernel argument: as a wave-uniform runtime value it cost the all-rows launch seven more
+// VGPRs and 2 % of a forward on an Erdős–Rényi graph, which has no heavy row (profiles/generic_stages/README.md, "Heavy rows");
+// kAnyAll is the kernel as it was.
+enum { kAnyAll = 0, kAnyLight = 1, kAnyListed = 2 };
+struct AnyRowSel {
+    uint32_t from, nlist;
+    const uint32_t *list;
+    const float *hsum;
+};
+
+template <int MODE>
 __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
                                                         float *__restrict__ out, float *__restrict__ logits, uint32_t lo, uint32_t hi,
-                                                        AnyShape S, int sig) {
+                                                        AnyShape S, int sig, AnyRowSel R) {
     extern __shared__ float4 any_lds4[];
     float *lds = reinterpret_cast<float *>(any_lds4);
     const StageAnyLayout L = stage_any_layout(S);
@@ -267,14 +284,26 @@ __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, c
     __syncthreads();
     const int lane = threadIdx.x & 63, j = lane & 15, grp = threadIdx.x >> 4, gbase = lane & 48;
     float *xs = lds + L.grp + grp * L.gs;   // the group's vector A; B follows at L.hb
-    for (uint64_t base = (uint64_t)lo + (uint64_t)blockIdx.x * kAnyRows; base < hi; base += (uint64_t)gridDim.x * kAnyRows) {
+    constexpr bool listed = MODE == kAnyListed;
+    // (the walk is over rows, or over positions of the list)
+    const uint64_t walk_lo = listed ? 0u : (uint64_t)lo, walk_hi = listed ? (uint64_t)R.nlist : (uint64_t)hi;
+    for (uint64_t base = walk_lo + (uint64_t)blockIdx.x * kAnyRows; base < walk_hi; base += (uint64_t)gridDim.x * kAnyRows) {
         const uint64_t u64 = base + (uint64_t)grp;
-        if (u64 >= hi) continue;   // (no workgroup barrier below: a group without a row just waits for the next round)
-        const uint32_t u = (uint32_t)u64;
+        if (u64 >= walk_hi) continue;   // (no workgroup barrier below: a group without a row just waits for the next round)
+        uint32_t u = (uint32_t)u64;
+        if (listed) {
+            u = R.list[u64];
+            if (u < lo || u >= hi) continue;   // listed, but not in this call's range
+        }
         // ---- graph layer
         const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
+        if (MODE == kAnyLight && re - rs >= R.from) continue;   // a heavy row: the listed-rows launch has it
         float s0 = 0.0f, s1 = 0.0f;
-        if (f == 1) {
+        if (listed) {
+            const float *hs = R.hsum + (size_t)u64 * (uint32_t)f;
+            s0 = hs[min(j, f - 1)];
+            s1 = hs[min(j + 16, f - 1)];
+        } else if (f == 1) {
             s0 = any_gather1(g.col, in, rs, re, j, gbase);
         } else if (f <= 16) {
             any_gather<false>(g.col, in, rs, re, (uint32_t)f, j, gbase, s0, s1);
@@ -317,6 +346,108 @@ __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, c
     }
 }
 
+// ---- heavy rows: the neighbour sums of ONE listed row by a whole workgroup (the structure of k_long_f1 / k_long_f16 in
+// gnnvc_kernels.hip, for any 1 <= f <= 32; nothing is shared with them or with k_audit_any).  Sums only: the row build, the dense
+// layers and the stores stay k_stage_any's (kAnyListed).
+//
+// The 256 threads form groups of G = 2^gs >= f lanes, a group per neighbour: lane c of a group fetches column c of its
+// neighbour's row (lanes c >= f have no column: they fetch column f - 1 and write nothing).  A pass covers 256 / G neighbours, a
+// chunk is R passes — R values per thread in registers — so a chunk is CH = 256 R / G neighbours: 1024 for f <= 4 (R = 4, 8, 16 for
+// G = 1, 2, 4), 512 for f <= 8, 256 for f <= 16, 128 above (R = 16).  The slab is column-major, f runs of CH + 4 floats (the pad of
+// four keeps every column 16-byte aligned and puts the adder lanes' 16-byte reads on different banks); two slabs alternate:
+// heavy_lds_bytes(f), at most 33 792 bytes (f = 32) — four workgroups a CU by LDS, and the 64 KiB limit is not raised.
+// While lane c < f of the first wave adds column c of chunk r in stored order (sixteen 16-byte LDS reads ahead of their 64
+// adds), the values of chunk r + 1 and the column ids of chunk r + 2 are in flight.  Every fetch is unconditional: entries past
+// the row's end clamp to its last entry — a real neighbour, never a pad row of `in` — and what they fetch is written to the slab
+// but never added (the adders stop at the row's length).
+typedef float any_f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kHeavyBlock = 256, kHeavyPad = 4;
+__host__ __device__ inline int heavy_shift(int f) {   // G = 1 << heavy_shift(f): the smallest power of two >= f
+    int s = 0;
+    while ((1 << s) < f) ++s;
+    return s;
+}
+__host__ __device__ inline int heavy_passes(int gs) { return gs >= 2 ? 16 : (gs == 1 ? 8 : 4); }
+__host__ __device__ inline size_t heavy_lds_bytes(int f) {
+    const int gs = heavy_shift(f), ch = (kHeavyBlock >> gs) * heavy_passes(gs);
+    return (size_t)2 * (size_t)f * (size_t)(ch + kHeavyPad) * sizeof(float);
+}
+
+template <int R>
+__global__ __launch_bounds__(kHeavyBlock) void k_any_heavy_sums(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ col,
+                                                               const float *__restrict__ in, const uint32_t *__restrict__ list,
+                                                               float *__restrict__ hsum, uint32_t f, uint32_t gs, uint32_t lo,
+                                                               uint32_t hi) {
+    extern __shared__ float4 heavy_lds4[];
+    float *slab = reinterpret_cast<float *>(heavy_lds4);
+    const uint32_t u = list[blockIdx.x];
+    if (u < lo || u >= hi) return;   // block-uniform: not in this call's range (k_stage_any skips the same rows)
+    const uint32_t tid = threadIdx.x;
+    const uint32_t rs = rowptr[u], deg = rowptr[u + 1] - rs;
+    if (deg == 0) {   // (never listed; kept so that nothing below indexes an empty row)
+        if (tid < f) hsum[(size_t)blockIdx.x * f + tid] = 0.0f;
+        return;
+    }
+    const uint32_t per = (uint32_t)kHeavyBlock >> gs, CH = per * R, stride = CH + kHeavyPad;
+    const uint32_t k0 = tid >> gs, c = tid & ((1u << gs) - 1u);
+    const bool has = c < f;
+    const uint32_t cc = has ? c : f - 1u;
+    const uint32_t nrounds = (deg + CH - 1u) / CH;
+    uint32_t idx[R];
+    float v[R];
+    // (offsets within the row: a row's degree plus three chunks stays far below 2^32 — nnz < 2^32 - GNNVC_COL_PAD)
+#define GNNVC_HEAVY_IDX(rd_)                                                  \
+    _Pragma("unroll") for (int j = 0; j < R; ++j) {                            \
+        const uint32_t o_ = (rd_) * CH + k0 + per * (uint32_t)j;              \
+        idx[j] = col[rs + (o_ < deg ? o_ : deg - 1u)];                        \
+    }
+#define GNNVC_HEAVY_VAL()                                                     \
+    _Pragma("unroll") for (int j = 0; j < R; ++j) v[j] = in[(size_t)idx[j] * f + cc];
+    float acc = 0.0f;   // threads c < f of the first wave: column c
+    GNNVC_HEAVY_IDX(0u)
+    GNNVC_HEAVY_VAL()
+    GNNVC_HEAVY_IDX(1u)
+    for (uint32_t rd = 0; rd < nrounds; ++rd) {
+        float *buf = slab + (size_t)(rd & 1u) * f * stride;
+        if (has) {
+#pragma unroll
+            for (int j = 0; j < R; ++j) buf[c * stride + k0 + per * (uint32_t)j] = v[j];
+        }
+        __syncthreads();
+        GNNVC_HEAVY_VAL()            // chunk rd + 1 (unconditional, clamped)
+        GNNVC_HEAVY_IDX(rd + 2u)
+        if (tid < f) {
+            const uint32_t left = deg - rd * CH, cnt = left < CH ? left : CH;
+            const float *colv = buf + tid * stride;
+            for (uint32_t k = 0; k < cnt; k += 64u) {   // (CH is a multiple of 64: the sixteen reads stay inside the column)
+                any_f32x4 t[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) t[j] = *reinterpret_cast<const any_f32x4 *>(&colv[k + 4 * j]);
+                if (k + 64u <= cnt) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        acc = acc + t[j][0];
+                        acc = acc + t[j][1];
+                        acc = acc + t[j][2];
+                        acc = acc + t[j][3];
+                    }
+                } else {   // the row's last entries: what lies behind them in the slab is not added
+                    const uint32_t m = cnt - k;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if ((uint32_t)(4 * j + i) < m) acc = acc + t[j][i];
+                }
+            }
+        }
+        // this slab is rewritten in round rd + 2, behind the barrier of round rd + 1, which the adders reach after these reads
+    }
+#undef GNNVC_HEAVY_IDX
+#undef GNNVC_HEAVY_VAL
+    if (tid < f) hsum[(size_t)blockIdx.x * f + tid] = acc;
+}
+
 AnyShape any_shape(const StagePlan &sp) {
     AnyShape S{};
     S.f = sp.f;
@@ -334,20 +465,56 @@ bool stage_any_fits(const StagePlan &sp) {
     return (size_t)stage_any_layout(any_shape(sp)).total * sizeof(float) <= kAnyLdsBytes;
 }
 
-hipError_t launch_stage_any(const StageCall &c) {
+hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows &hr) {
     if (c.row_hi <= c.row_lo) return hipSuccess;
     const StagePlan &sp = *c.sp;
     const GraphDev &g = *c.g;
     if (!stage_any_fits(sp) || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
+    AnyRowSel sel{0u, 0u, nullptr, nullptr};
+    if (rows == AnyRows::kLight) {
+        sel = AnyRowSel{hr.from, 0u, nullptr, nullptr};
+    } else if (rows == AnyRows::kListed) {
+        if (hr.n == 0) return hipSuccess;
+        if (!hr.list || !hr.hsum) return hipErrorInvalidValue;
+        sel = AnyRowSel{hr.from, hr.n, hr.list, hr.hsum};
+    }
     const AnyGraph plain{g.rowptr, g.col, g.w, g.nw};
     const AnyShape S = any_shape(sp);
     const size_t lds = (size_t)stage_any_layout(S).total * sizeof(float);   // <= 64 KiB (stage_any_fits)
     // a persistent grid: as many workgroups as the LDS lets a CU hold (at most 8), on 256 CUs
     const unsigned per_cu = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (160u * 1024u) / (lds + 1024u)));
-    const unsigned need = (unsigned)(((size_t)(c.row_hi - c.row_lo) + kAnyRows - 1) / kAnyRows);
+    const size_t walk = rows == AnyRows::kListed ? (size_t)hr.n : (size_t)(c.row_hi - c.row_lo);   // rows, or list positions
+    const unsigned need = (unsigned)((walk + kAnyRows - 1) / kAnyRows);
     const dim3 grid(std::min(need, 256u * per_cu)), block(kAnyBlock);
-    hipLaunchKernelGGL(k_stage_any, grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, c.out,
-                       sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0);
+#define GNNVC_ANY_LAUNCH(MODE_)                                                                                         \
+    hipLaunchKernelGGL((k_stage_any<MODE_>), grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, \
+                       c.out, sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0, sel)
+    switch (rows) {
+    case AnyRows::kAll: GNNVC_ANY_LAUNCH(kAnyAll); break;
+    case AnyRows::kLight: GNNVC_ANY_LAUNCH(kAnyLight); break;
+    case AnyRows::kListed: GNNVC_ANY_LAUNCH(kAnyListed); break;
+    }
+#undef GNNVC_ANY_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_any_heavy_sums(const StageCall &c, const AnyHeavyRows &hr) {
+    if (c.row_hi <= c.row_lo || hr.n == 0) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
+    if (sp.f < 1 || sp.f > 32 || !hr.list || !hr.hsum || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
+    const int gs = heavy_shift(sp.f);
+    const size_t lds = heavy_lds_bytes(sp.f);   // <= 33 792 bytes
+    const dim3 grid(hr.n), block(kHeavyBlock);
+#define GNNVC_HEAVY_LAUNCH(R_)                                                                                            \
+    hipLaunchKernelGGL((k_any_heavy_sums<R_>), grid, block, lds, c.stream, g.rowptr, g.col, c.in, hr.list, hr.hsum, \
+                       (uint32_t)sp.f, (uint32_t)gs, c.row_lo, c.row_hi)
+    switch (heavy_passes(gs)) {
+    case 4: GNNVC_HEAVY_LAUNCH(4); break;
+    case 8: GNNVC_HEAVY_LAUNCH(8); break;
+    default: GNNVC_HEAVY_LAUNCH(16); break;
+    }
+#undef GNNVC_HEAVY_LAUNCH
     return hipGetLastError();
 }
 

@@ -21,7 +21,8 @@ _LIB = pathlib.Path(os.environ["GNNVC_LIBRARY"]).resolve() if os.environ.get("GN
 # deliberately left out: a debugging aid outside the header (Option C), used by tests/test_gpu_lifetime.py
 ABI_SYMBOLS = [
     "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_destroy",
-    "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_num_layers", "gnnvc_is_fused",
+    "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_set_generic_heavy_rows",
+    "gnnvc_num_layers", "gnnvc_is_fused",
     "gnnvc_in_width", "gnnvc_out_width", "gnnvc_upload_graph", "gnnvc_attach_graph_device", "gnnvc_attach_graph_slice",
     "gnnvc_graph_staging", "gnnvc_staged_columns_ready", "gnnvc_commit_staged_graph",
     "gnnvc_derive_graph_begin", "gnnvc_derive_graph_commit", "gnnvc_graph_row_hashes",
@@ -103,6 +104,7 @@ def load_library():
     L.gnnvc_set_stream.argtypes = [vp, vp]
     L.gnnvc_set_option.argtypes = [vp, C.c_char_p, C.c_long]
     L.gnnvc_get_info.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
+    L.gnnvc_set_generic_heavy_rows.argtypes = [vp, u32]
     for name in ("gnnvc_num_layers", "gnnvc_is_fused", "gnnvc_in_width", "gnnvc_out_width",
                  "gnnvc_num_stages", "gnnvc_synchronize"):
         getattr(L, name).argtypes = [vp]
@@ -226,6 +228,13 @@ class Engine:
         v = C.c_long(0)
         self._check(self._L.gnnvc_get_info(self._h, key.encode(), C.byref(v)))
         return v.value
+
+    def set_generic_heavy_rows(self, from_degree: int):
+        """Rows of at least `from_degree` entries get a workgroup each for their neighbour sums in generic stages
+        (gnnvc_set_generic_heavy_rows); 0 = none, the default is 512.  Same bits for every value; takes effect at the next
+        forward or stage call.  get_info: "generic_heavy_from", "generic_heavy_rows", "generic_heavy_entries",
+        "generic_heavy_last_rows"."""
+        self._check(self._L.gnnvc_set_generic_heavy_rows(self._h, from_degree))
 
     def audit_report(self) -> dict:
         """The on-device audit's counters and its last failure (option "audit_period"), key -> value."""

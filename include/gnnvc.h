@@ -299,7 +299,9 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         A model whose every stage is of a trained shape is planned, launched and audited as ever.
  *                         0: such a model is not fused, has 0 stages and runs layer by layer (one launch per layer), as
  *                         before this option existed.  2 (tests): the trained shape is sent through the generic kernel as well,
- *                         none of its plans used.  Generic stages have no per-graph plan, and "audit_period" audits nothing on
+ *                         none of its plans used.  Generic stages have no per-graph plan but the list of their heavy rows
+ *                         (gnnvc_set_generic_heavy_rows below: rows of many entries get a workgroup each for their neighbour
+ *                         sums, with the same bits), and "audit_period" audits nothing on
  *                         them, as on an unfused model: they are audited on demand, by gnnvc_forward_audited,
  *                         gnnvc_forward_audited_device and gnnvc_audit_stage_device (kernel k_audit_any: a wave per row, the
  *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
@@ -319,6 +321,27 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  * "long_row_threshold", "giant_rows", "giant_entries", "giant_row_threshold". */
 int gnnvc_set_option(gnnvc_engine *e, const char *key, long value);
 int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value);
+
+/* Heavy rows of generic stages (option "generic_stages", kernel k_stage_any).  k_stage_any gives every row to sixteen lanes,
+ * which walk a hub of tens of thousands of entries round by round while the rest of the device runs dry.  Rows of at least
+ * from_degree entries therefore take another way: they are listed once per graph (at hand-off when the generic stage list is in
+ * force, else by the first generic stage that runs on the graph: one pass over the row pointers and one 16-byte read-back), and
+ * a stage call on a graph that has such rows is three launches — k_any_heavy_sums (a 256-thread workgroup per listed row: the
+ * row's neighbour sums, one fp32 add per neighbour in stored order, one chain per column from +0.0f, as everywhere),
+ * k_stage_any over the other rows, and k_stage_any over the listed rows with their sums read back.  Results are bit-identical
+ * for every value.  A graph without such rows launches what it always did.
+ *   from_degree 0      no row takes the heavy path: every row walks k_stage_any's loop, as before this call existed;
+ *   from_degree >= 1   any value is legal; with 1 every non-empty row is heavy.  The default is 512, the long-row threshold of the
+ *                      trained path.
+ * The value takes effect at the next forward or stage call; an attached graph is classed again then.  On a model without a
+ * generic stage list the value is stored and does nothing.  Rows of 16 384 entries and more still run one chain per column
+ * (the trained path's exact parallel sums of giant rows are not used here).  A multi-device handle: GNNVC_ERR_UNSUPPORTED; a
+ * null engine: GNNVC_ERR_INVALID.
+ * gnnvc_get_info: "generic_heavy_from" (the threshold in force), "generic_heavy_rows" and "generic_heavy_entries" (the listed
+ * rows of the attached graph or slice and their entries, from its last classing; 0 before one), "generic_heavy_last_rows" (the
+ * listed rows the last forward or stage call sent down the heavy path — rows outside a stage call's range are skipped on the
+ * device and still counted; 0 when it launched one kernel per stage). */
+int gnnvc_set_generic_heavy_rows(gnnvc_engine *e, uint32_t from_degree);
 
 /* Model introspection (what model::layers holds). */
 int gnnvc_num_layers(const gnnvc_engine *e);
