@@ -707,26 +707,53 @@ int forward_unfused(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
 
 // One generic stage over [lo, hi): one k_stage_any launch — or, on a graph with heavy rows (gnnvc_set_generic_heavy_rows,
 // class_heavy_rows), three: the heavy rows' sums a workgroup per row (k_any_heavy_sums), k_stage_any over the light rows, and
-// k_stage_any over the listed rows with their sums read back.  The sums kernel goes to the side queue beside the light rows
-// (fork / join as launch_side_rows) or ahead of them on the main stream (heavy_overlap()); the listed rows' launch follows both.
+// k_stage_any over the listed rows with their sums read back.  Where some of the listed rows are giant
+// (gnnvc_set_generic_giant_rows) their chain comes first — k_any_giant_gather, [k_giant_segsum, k_giant_segmap,] k_giant_sum,
+// k_any_giant_place, which leaves their sums where the listed rows' launch reads them — and k_any_heavy_sums skips them.  The
+// giant chain and then the heavy sums go to the side queue beside the light rows (fork / join as launch_side_rows) or ahead of
+// them on the main stream (heavy_overlap()); the listed rows' launch follows all of them.
 int run_generic_stage(gnnvc_engine *e, const StagePlan &sp, const float *in, float *out, float *logits, uint32_t lo, uint32_t hi) {
     {   // (lazily: option "generic_stages" set after the attach, or a threshold that has moved)
         const int rc = class_heavy_rows(e);
         if (rc) return rc;
     }
     const gnnvc::StageCall call = stage_call(e, sp, in, out, logits, lo, hi);
-    e->heavy_last_rows = e->pg.heavy_rows;
-    if (!e->pg.heavy_rows) {
+    const gnnvc_engine::PerGraph &pg = e->pg;
+    e->heavy_last_rows = pg.heavy_rows;
+    e->ggiant_last_rows = pg.heavy_rows ? pg.giant_rows : 0;
+    e->ggiant_last_segmented = e->ggiant_last_rows && pg.giant_maxseg > 1;
+    if (!pg.heavy_rows) {
         HIP_TRY(e, gnnvc::launch_stage_any(call));
         return GNNVC_OK;
     }
-    const gnnvc::AnyHeavyRows hr{.list = e->heavy_list.p, .n = e->pg.heavy_rows, .from = e->pg.heavy_thresh, .hsum = e->heavy_sum.p};
+    const gnnvc::AnyHeavyRows hr{.list = e->heavy_list.p, .n = pg.heavy_rows, .from = pg.heavy_thresh, .hsum = e->heavy_sum.p,
+                                 .below = pg.giant_rows ? pg.giant_min : 0xFFFFFFFFu};
     const bool side = heavy_overlap() && e->aux_stream;
     gnnvc::StageCall sums = call;
+    gnnvc::AnyGiantRows ar;
+    if (pg.giant_rows) {
+        ar.gr.n = pg.giant_rows;
+        ar.gr.blocks = pg.giant_blocks;
+        ar.gr.meta = e->ag_meta.p;
+        ar.gr.off = e->ag_off.p;
+        ar.gr.slab = e->ag_slab.p;
+        ar.gr.agg = e->ag_agg.p;
+        ar.gr.segsum = pg.giant_maxseg > 1 ? e->ag_segsum.p : nullptr;
+        ar.gr.segmap = pg.giant_maxseg > 1 ? e->ag_segmap.p : nullptr;
+        ar.gr.maxseg = pg.giant_maxseg;
+        ar.pos = e->ag_pos.p;
+    }
+    const bool gather_first = side && pg.giant_rows && giant_gather_first();   // (the gather on the main stream, ahead of the fork)
+    if (gather_first) HIP_TRY(e, gnnvc::launch_any_giant(call, ar, hr.hsum, gnnvc::AnyGiantPart::kGather));
     if (side) {
         HIP_TRY(e, hipEventRecord(e->ev_fork, e->stream));
         HIP_TRY(e, hipStreamWaitEvent(e->aux_stream, e->ev_fork, 0));
         sums.stream = e->aux_stream;
+    }
+    if (pg.giant_rows) {
+        if (!gather_first) HIP_TRY(e, gnnvc::launch_any_giant(sums, ar, hr.hsum, gnnvc::AnyGiantPart::kGather));
+        HIP_TRY(e, gnnvc::launch_giant_sums(ar.gr, (uint32_t)sp.f, lo, hi, sums.stream));
+        HIP_TRY(e, gnnvc::launch_any_giant(sums, ar, hr.hsum, gnnvc::AnyGiantPart::kPlace));
     }
     HIP_TRY(e, gnnvc::launch_any_heavy_sums(sums, hr));
     if (side) HIP_TRY(e, hipEventRecord(e->ev_join, e->aux_stream));
@@ -757,6 +784,9 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
         }
         if (e->audit_now) {   // (gnnvc_forward_audited* only: "audit_period" never sets it for a generic-stage model)
             std::string plan = e->heavy_last_rows ? "k_stage_any (light rows, listed rows) + k_any_heavy_sums" : "k_stage_any";
+            if (e->ggiant_last_rows)
+                plan += e->ggiant_last_segmented ? " + k_any_giant_gather, k_giant_segsum, k_giant_segmap, k_giant_sum, k_any_giant_place"
+                                                 : " + k_any_giant_gather, k_giant_sum, k_any_giant_place";
             const int rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan);
             if (rc != GNNVC_OK) return rc;
         }
@@ -924,6 +954,14 @@ int gnnvc_set_generic_heavy_rows(gnnvc_engine *e, uint32_t from_degree) {
     return GNNVC_OK;
 }
 
+int gnnvc_set_generic_giant_rows(gnnvc_engine *e, uint32_t from_degree, int segments) {
+    if (!e) return GNNVC_ERR_INVALID;
+    NOT_ON_MULTI(e, "gnnvc_set_generic_giant_rows");
+    e->ggiant_from = from_degree;   // (as above: class_heavy_rows classes the attached graph again when either value has moved)
+    e->ggiant_segments = segments;
+    return GNNVC_OK;
+}
+
 int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     if (!e || !key || !value) return GNNVC_ERR_INVALID;
     const std::string k(key);
@@ -946,6 +984,12 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k == "generic_heavy_rows") *value = (long)e->pg.heavy_rows;              // the attached graph's last classing
     else if (k == "generic_heavy_entries") *value = (long)e->pg.heavy_entries;
     else if (k == "generic_heavy_last_rows") *value = (long)e->heavy_last_rows;       // 0: the last call launched one kernel a stage
+    else if (k == "generic_giant_from") *value = (long)e->ggiant_from;                // gnnvc_set_generic_giant_rows
+    else if (k == "generic_giant_segments") *value = (long)e->ggiant_segments;        // as stored: -1 | 0 | 1 (or whatever was passed)
+    else if (k == "generic_giant_rows") *value = (long)e->pg.giant_rows;              // the attached graph's last classing
+    else if (k == "generic_giant_entries") *value = (long)e->pg.giant_entries;
+    else if (k == "generic_giant_last_rows") *value = (long)e->ggiant_last_rows;
+    else if (k == "generic_giant_last_segmented") *value = e->ggiant_last_segmented ? 1 : 0;
     else if (k.rfind("generic_stage_layers_", 0) == 0) {   // "generic_stage_layers_<s>": dense layers of stage s of a generic model
         const char *num = k.c_str() + sizeof("generic_stage_layers_") - 1;
         char *end = nullptr;
@@ -1542,6 +1586,8 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     int rc = use_device(e);
     if (rc) return rc;
     e->heavy_last_rows = 0;
+    e->ggiant_last_rows = 0;
+    e->ggiant_last_segmented = false;
     if (e->generic_on()) {   // (k_stage_any, with k_any_heavy_sums on a graph with heavy rows; a generic stage audits nothing)
         const StagePlan &sp = e->gstages[stage];
         return run_generic_stage(e, sp, d_in, d_out, sp.sigmoid_last ? d_logits : nullptr, row_lo, row_hi);
@@ -1645,7 +1691,9 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     int rc = use_device(e);
     if (rc) return rc;
     e->generic_ran = e->generic_on();
-    e->heavy_last_rows = 0;   // (run_generic_stage sets it)
+    e->heavy_last_rows = 0;
+    e->ggiant_last_rows = 0;
+    e->ggiant_last_segmented = false;   // (run_generic_stage sets it)
     if (e->generic_ran || e->stages.empty()) {
         rc = ensure_events(e, 2);
         if (rc) return rc;

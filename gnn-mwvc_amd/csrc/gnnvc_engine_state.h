@@ -68,6 +68,13 @@ struct gnnvc_engine {
     // engine's; what is known about the current graph is in pg.heavy_*.
     uint32_t heavy_from = 512;      // the trained path's long-row threshold
     uint32_t heavy_last_rows = 0;   // gnnvc_get_info "generic_heavy_last_rows": listed rows of the last forward / stage call (0 = one launch)
+    // Giant rows of generic stages (gnnvc_set_generic_giant_rows): the listed rows of at least max(ggiant_from, heavy_from) entries
+    // (0: none) take the trained path's exact parallel scan instead of k_any_heavy_sums' one chain per column: k_any_giant_gather
+    // into a slab of the engine's own (ag_* below), k_giant_segsum / k_giant_segmap / k_giant_sum, k_any_giant_place.
+    uint32_t ggiant_from = 16384;   // the trained path's giant_row_threshold
+    int ggiant_segments = -1;       // 1 = one stream on several waves, 0 = one wave walks each stream, -1 = by the graph (find_giant's rule)
+    uint32_t ggiant_last_rows = 0;  // "generic_giant_last_rows": giant rows of the last forward / stage call
+    bool ggiant_last_segmented = false;   // "generic_giant_last_segmented": that call used several waves per stream
     int in_width = 1, out_width = 1;
     int max_width = 1;
     bool ends_in_sigmoid = false;
@@ -114,6 +121,11 @@ struct gnnvc_engine {
         bool heavy_known = false;
         uint32_t heavy_rows = 0, heavy_thresh = 0;
         uint64_t heavy_entries = 0;
+        // ... and the giant ones among them, classed with giant_from / giant_seg as set at the time: rows, gather blocks, segments of
+        // the longest stream (0: one wave walks each stream), the degree from which a listed row is giant (0xFFFFFFFF: none)
+        uint32_t giant_from = 0, giant_rows = 0, giant_blocks = 0, giant_maxseg = 0, giant_min = 0xFFFFFFFFu;
+        int giant_seg = -1;
+        uint64_t giant_entries = 0;
         double plan_build_ms = 0.0;         // host wall time spent building per-graph plans for the current graph (they end in stream syncs)
         double early_ms = 0.0;              // host time the hand-off spent classing the graph and queuing builds before the commit
     };
@@ -267,6 +279,13 @@ struct gnnvc_engine {
     // generic stages' heavy rows (heavy_from above): find_long_rows' list and count words, and the sums — rows x the widest stage input
     DevBuf<uint32_t> heavy_list, heavy_count;
     DevBuf<float> heavy_sum;
+    // generic stages' giant rows: {row, first entry, degree, first gather block} heaviest first, each row's slab offset and position
+    // in heavy_list, the slab (per row: the widest stage input x the degree rounded up to giant_window() floats), the aggregates
+    // (rows x f of the stage at hand) and, with several waves per stream, the segments' sums and maps.  Not the trained path's gi_*.
+    DevBuf<uint4> ag_meta, ag_segmap;
+    DevBuf<unsigned long long> ag_off;
+    DevBuf<uint32_t> ag_pos;
+    DevBuf<float> ag_slab, ag_agg, ag_segsum;
     // what classify_hand_off learned about a graph in its one round trip, for the find_long that follows it
     struct PreClass {
         bool valid = false, cuts = false, waste = false, longs = false;
@@ -384,6 +403,19 @@ inline bool heavy_overlap() {
     static const bool on = [] {
         const char *s = getenv("GNNVC_HEAVY_OVERLAP");
         return s && *s ? atoi(s) != 0 : kHeavyOverlapDefault;
+    }();
+    return on;
+}
+
+// Generic stages' giant rows: does their gather (k_any_giant_gather, a throughput kernel) go to the main stream AHEAD of the fork —
+// the trained path's giant_gather_first — instead of opening the chain on the side queue?  GNNVC_GIANT_GATHER_FIRST (0 | 1, read
+// once per process) overrides the default; it means something only where the sums overlap (heavy_overlap()).  Both orders are
+// measured in profiles/generic_stages/README.md, "Giant rows".
+constexpr bool kGiantGatherFirstDefault = false;
+inline bool giant_gather_first() {
+    static const bool on = [] {
+        const char *s = getenv("GNNVC_GIANT_GATHER_FIRST");
+        return s && *s ? atoi(s) != 0 : kGiantGatherFirstDefault;
     }();
     return on;
 }

@@ -208,6 +208,7 @@ struct AnyHeavyRows {
     const uint32_t *list = nullptr;
     uint32_t n = 0, from = 0;
     float *hsum = nullptr;   // n x (the stage's f) floats
+    uint32_t below = 0xFFFFFFFFu;   // k_any_heavy_sums leaves listed rows of at least this many entries alone: the giant route has their sums
 };
 enum class AnyRows { kAll, kLight, kListed };
 hipError_t launch_stage_any(const StageCall &c, AnyRows rows = AnyRows::kAll, const AnyHeavyRows &hr = AnyHeavyRows());
@@ -285,6 +286,22 @@ hipError_t find_giant_rows(const GraphDev &g, const uint32_t *list, uint32_t n_l
 // everything behind it on another, hence the parts.
 enum class GiantPart { kAll, kGather, kAfterGather };
 hipError_t launch_giant_stage(const StageCall &c, const GiantRows &gr, uint32_t min_deg, GiantPart part);
+// the sums alone (k_giant_segsum, k_giant_segmap, k_giant_sum), F streams per row (1 <= F <= 32), agg: float[n x F]
+hipError_t launch_giant_sums(const GiantRows &gr, uint32_t F, uint32_t row_lo, uint32_t row_hi, hipStream_t stream);
+
+// Giant rows of a GENERIC stage (gnnvc_set_generic_giant_rows; gnnvc_stage_any.hip): the listed heavy rows of at least the giant
+// threshold go through a slab like the trained path's — gr as above, with fmax streams of room per row (the widest stage input of
+// the model; a stage of width f writes and sums the first f) — and their aggregates are placed where k_stage_any<kAnyListed>
+// reads a listed row's sums: hsum[pos[i] * f + c], pos[i] = the row's position in the heavy list.
+// find_any_giant_rows fills {row, first entry, degree, list position} in no particular order.
+struct AnyGiantRows {
+    GiantRows gr;
+    const uint32_t *pos = nullptr;
+};
+hipError_t find_any_giant_rows(const GraphDev &g, const uint32_t *list, uint32_t n_list, uint32_t thresh, void *meta, uint32_t *count,
+                               hipStream_t stream);
+enum class AnyGiantPart { kGather, kPlace };
+hipError_t launch_any_giant(const StageCall &c, const AnyGiantRows &ar, float *hsum, AnyGiantPart part);
 hipError_t stream_sums(const float *streams_dev, uint32_t streams, uint32_t len, void *meta, unsigned long long *off, float *agg,
                        int mode /* 0 on several waves, 2 on one wave: the same exact sum */, hipStream_t stream, float *segsum = nullptr,
                        void *segmap = nullptr);

@@ -2177,12 +2177,16 @@ __global__ __launch_bounds__(64 * kGiantSegWaves) void k_giant_segmap(const floa
     if (lane == 0) segmap[(size_t)st * maxseg + sg] = make_uint4(E, total.d0, total.d1, any_bad ? 1u : 0u);
 }
 
+// AGG16: agg holds 16 floats per row — the trained path, k_giant_dense reads agg[i * 16 + c]; false: F floats per row (generic
+// stages).  A template argument: as a kernel argument the stride cost the trained path's kernel four more spilled SGPRs (27 -> 31).
+template <bool AGG16>
 __global__ __launch_bounds__(64) void k_giant_sum(const float *__restrict__ slab, const uint4 *__restrict__ meta,
                                                   const unsigned long long *__restrict__ off, uint32_t F, float *__restrict__ agg,
                                                   uint32_t row_lo, uint32_t row_hi, const uint32_t *__restrict__ prp,
                                                   const uint32_t *__restrict__ prune_bad, const uint4 *__restrict__ segmap,
                                                   uint32_t maxseg, uint32_t min_deg) {
     const uint32_t i = blockIdx.x / F, c = blockIdx.x % F;
+    const uint32_t agg_stride = AGG16 ? 16u : F;
     const uint4 mt = meta[i];
     if (mt.x < row_lo || mt.x >= row_hi || mt.z < min_deg) return;
     const int lane = threadIdx.x;
@@ -2191,7 +2195,7 @@ __global__ __launch_bounds__(64) void k_giant_sum(const float *__restrict__ slab
     const uint32_t lpad = (len + kGiantWin - 1) / kGiantWin * kGiantWin;
     const uint32_t nwin = lpad / kGiantWin;
     if (nwin == 0) {   // nothing left of the row: a sum of no addends
-        if (lane == 0) agg[(size_t)i * 16 + c] = 0.0f;
+        if (lane == 0) agg[(size_t)i * agg_stride + c] = 0.0f;
         return;
     }
     const f32x4 *__restrict__ src = reinterpret_cast<const f32x4 *>(slab + off[i] + (size_t)c * lpad) + lane * (kGiantB / 4);
@@ -2249,7 +2253,7 @@ __global__ __launch_bounds__(64) void k_giant_sum(const float *__restrict__ slab
     }
 #undef GNNVC_GIANT_LOAD
 #undef GNNVC_GIANT_USE
-    if (lane == 0) agg[(size_t)i * 16 + c] = acc;
+    if (lane == 0) agg[(size_t)i * agg_stride + c] = acc;
 }
 
 // VARIANT as stage_variant(): 0 = F 1 -> 16 features, 1 = F 16 -> 16 features, 2 = F 16 -> sigmoid
@@ -5600,7 +5604,7 @@ hipError_t launch_giant_stage(const StageCall &c, const GiantRows &gr, uint32_t 
             GNNVC_LAUNCH(k_giant_segmap, sgrid, sblock, 0, c.stream, gr.slab, meta, gr.off, F, gr.maxseg, gr.segsum,
                          reinterpret_cast<uint4 *>(gr.segmap), c.row_lo, c.row_hi, pr, pb, min_deg);
         }
-        GNNVC_LAUNCH(k_giant_sum, dim3(gr.n * F), dim3(64), 0, c.stream, gr.slab, meta, gr.off, F, gr.agg, c.row_lo, c.row_hi, pr, pb,
+        GNNVC_LAUNCH(k_giant_sum<true>, dim3(gr.n * F), dim3(64), 0, c.stream, gr.slab, meta, gr.off, F, gr.agg, c.row_lo, c.row_hi, pr, pb,
                      seg ? reinterpret_cast<const uint4 *>(gr.segmap) : nullptr, gr.maxseg, min_deg);
     }
     const float *P = c.params + sp.param_offset;
@@ -5638,8 +5642,27 @@ hipError_t stream_sums(const float *streams_dev, uint32_t streams, uint32_t len,
         GNNVC_LAUNCH(k_giant_segmap, sgrid, sblock, 0, stream, streams_dev, mt, off, 1u, maxseg, segsum,
                      reinterpret_cast<uint4 *>(segmap), 0u, 1u, none, none, 0u);
     }
-    GNNVC_LAUNCH(k_giant_sum, dim3(streams), dim3(64), 0, stream, streams_dev, mt, off, 1u, agg, 0u, 1u, none, none,
+    GNNVC_LAUNCH(k_giant_sum<true>, dim3(streams), dim3(64), 0, stream, streams_dev, mt, off, 1u, agg, 0u, 1u, none, none,
                  seg ? reinterpret_cast<const uint4 *>(segmap) : nullptr, maxseg, 0u);
+    return hipGetLastError();
+}
+
+// the sums of launch_giant_stage alone, for streams of any width (generic stages: gnnvc_stage_any.hip gathers, k_stage_any does
+// the dense layers): F streams per row at slab + off[i] + c * lpad, agg[i * F + c]; no pruned adjacency, rows of every degree
+hipError_t launch_giant_sums(const GiantRows &gr, uint32_t F, uint32_t row_lo, uint32_t row_hi, hipStream_t stream) {
+    if (gr.n == 0 || row_hi <= row_lo) return hipSuccess;
+    if (F < 1 || F > 32 || !gr.meta || !gr.off || !gr.slab || !gr.agg) return hipErrorInvalidValue;
+    const uint4 *meta = reinterpret_cast<const uint4 *>(gr.meta);
+    const uint32_t *none = nullptr;
+    const bool seg = gr.segsum && gr.segmap && gr.maxseg > 1;
+    if (seg) {
+        const dim3 sgrid(gr.n * F * giant_seg_blocks(gr.maxseg)), sblock(64 * kGiantSegWaves);
+        GNNVC_LAUNCH(k_giant_segsum, sgrid, sblock, 0, stream, gr.slab, meta, gr.off, F, gr.maxseg, gr.segsum, row_lo, row_hi, none, none, 0u);
+        GNNVC_LAUNCH(k_giant_segmap, sgrid, sblock, 0, stream, gr.slab, meta, gr.off, F, gr.maxseg, gr.segsum,
+                     reinterpret_cast<uint4 *>(gr.segmap), row_lo, row_hi, none, none, 0u);
+    }
+    GNNVC_LAUNCH(k_giant_sum<false>, dim3(gr.n * F), dim3(64), 0, stream, gr.slab, meta, gr.off, F, gr.agg, row_lo, row_hi, none, none,
+                 seg ? reinterpret_cast<const uint4 *>(gr.segmap) : nullptr, gr.maxseg, 0u);
     return hipGetLastError();
 }
 

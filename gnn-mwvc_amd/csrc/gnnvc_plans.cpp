@@ -234,17 +234,84 @@ int find_long(gnnvc_engine *e) {
     return find_giant(e);
 }
 
+// Generic stages' giant rows (gnnvc_set_generic_giant_rows): the listed heavy rows of at least max(ggiant_from, heavy_from)
+// entries, with their position in the heavy list (hsum is indexed by it), laid out as find_giant lays out the trained path's —
+// heaviest first, lpad / giant_block() gather blocks a row, so that every float of a stream up to lpad is written in every call —
+// in buffers of the engine's own.  fmax: the widest stage input of the model.  A slab that does not fit in memory leaves the
+// graph without giant rows (the heavy path has them): not an error.
+static int class_giant_rows(gnnvc_engine *e, int fmax) {
+    gnnvc_engine::PerGraph &pg = e->pg;
+    if (!e->ggiant_from || !pg.heavy_rows) return GNNVC_OK;
+    const uint32_t gt = std::max(e->ggiant_from, pg.heavy_thresh);
+    HIP_TRY(e, e->ag_meta.reserve((size_t)pg.heavy_rows + 1));
+    HIP_TRY(e, gnnvc::find_any_giant_rows(e->g, e->heavy_list.p, pg.heavy_rows, gt, e->ag_meta.p, e->heavy_count.p, e->stream));
+    uint32_t cnt = 0;
+    HIP_TRY(e, hipMemcpyAsync(&cnt, e->heavy_count.p, sizeof cnt, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (cnt == 0 || cnt > pg.heavy_rows) return GNNVC_OK;
+    std::vector<uint4> meta((size_t)cnt + 1);
+    HIP_TRY(e, hipMemcpy(meta.data(), e->ag_meta.p, (size_t)cnt * sizeof(uint4), hipMemcpyDeviceToHost));
+    std::sort(meta.begin(), meta.begin() + cnt, [](const uint4 &a, const uint4 &b) { return a.z != b.z ? a.z > b.z : a.x < b.x; });
+    std::vector<unsigned long long> off(cnt);
+    std::vector<uint32_t> pos(cnt);
+    const uint32_t win = gnnvc::giant_window(), blk = gnnvc::giant_block();
+    uint64_t floats = 0, blocks = 0, entries = 0;
+    for (uint32_t i = 0; i < cnt; ++i) {
+        const uint64_t lpad = ((uint64_t)meta[i].z + win - 1) / win * win;
+        off[i] = floats;
+        pos[i] = meta[i].w;
+        meta[i].w = (uint32_t)blocks;
+        floats += (uint64_t)fmax * lpad;
+        blocks += lpad / blk;
+        entries += meta[i].z;
+    }
+    if (blocks >= 0x7FFFFFFFull || (uint64_t)cnt * (uint64_t)fmax >= 0x7FFFFFFFull) return GNNVC_OK;   // (more launches than a grid holds: the heavy path keeps them)
+    meta[cnt] = make_uint4(0xFFFFFFFFu, 0u, 0u, (uint32_t)blocks);
+    uint32_t maxseg = gnnvc::giant_segments(meta[0].z);   // (sorted: the first row is the longest)
+    // one stream on several waves: -1 = where the longest stream's walk is what a stage would wait for (find_giant's rule)
+    bool segments = e->ggiant_segments > 0;
+    if (e->ggiant_segments < 0) segments = (double)meta[0].z * 2.0e-9 > 0.5 * (double)e->g.nnz / 50.0e9;
+    if (!(segments && maxseg > 1 && (uint64_t)cnt * (uint64_t)fmax * maxseg < (1ull << 31))) maxseg = 0;
+    hipError_t rc = e->ag_slab.reserve(floats);
+    if (rc == hipSuccess) rc = e->ag_agg.reserve((size_t)cnt * (size_t)fmax);
+    if (rc == hipSuccess && maxseg) rc = e->ag_segsum.reserve((size_t)cnt * (size_t)fmax * maxseg);
+    if (rc == hipSuccess && maxseg) rc = e->ag_segmap.reserve((size_t)cnt * (size_t)fmax * maxseg);
+    if (rc == hipErrorOutOfMemory) {   // no room for the slab: no giant rows on this graph
+        (void)hipGetLastError();
+        e->ag_slab.release();
+        return GNNVC_OK;
+    }
+    HIP_TRY(e, rc);
+    HIP_TRY(e, e->ag_off.reserve(cnt));
+    HIP_TRY(e, e->ag_pos.reserve(cnt));
+    HIP_TRY(e, hipMemcpy(e->ag_meta.p, meta.data(), ((size_t)cnt + 1) * sizeof(uint4), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(e->ag_off.p, off.data(), (size_t)cnt * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(e->ag_pos.p, pos.data(), (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice));
+    pg.giant_rows = cnt;
+    pg.giant_blocks = (uint32_t)blocks;
+    pg.giant_maxseg = maxseg;
+    pg.giant_entries = entries;
+    pg.giant_min = gt;
+    return GNNVC_OK;
+}
+
 // Generic stages' heavy rows (gnnvc_set_generic_heavy_rows): the rows this engine holds of at least heavy_from entries, listed
 // by find_long_rows with one 16-byte read-back.  Runs at hand-off for an engine whose generic stage list is in force
-// (prepare_plans) and otherwise the first time a generic stage runs on the graph; again after the threshold has moved.  The
-// trained model's default path never comes here.
+// (prepare_plans) and otherwise the first time a generic stage runs on the graph; again after the threshold — or what
+// gnnvc_set_generic_giant_rows sets — has moved.  The trained model's default path never comes here.
 int class_heavy_rows(gnnvc_engine *e) {
     gnnvc_engine::PerGraph &pg = e->pg;
-    if (pg.heavy_known && pg.heavy_thresh == e->heavy_from) return GNNVC_OK;
+    if (pg.heavy_known && pg.heavy_thresh == e->heavy_from && pg.giant_from == e->ggiant_from && pg.giant_seg == e->ggiant_segments)
+        return GNNVC_OK;
     pg.heavy_known = true;
     pg.heavy_thresh = e->heavy_from;
     pg.heavy_rows = 0;
     pg.heavy_entries = 0;
+    pg.giant_from = e->ggiant_from;
+    pg.giant_seg = e->ggiant_segments;
+    pg.giant_rows = pg.giant_blocks = pg.giant_maxseg = 0;
+    pg.giant_entries = 0;
+    pg.giant_min = 0xFFFFFFFFu;
     const GraphDev &g = e->g;
     if (!e->heavy_from || e->empty_slice || g.n == 0 || g.nnz == 0 || g.hi() <= g.lo()) return GNNVC_OK;
     HIP_TRY(e, e->heavy_list.reserve(g.hi() - g.lo()));
@@ -263,7 +330,7 @@ int class_heavy_rows(gnnvc_engine *e) {
     }
     pg.heavy_rows = found[0];
     pg.heavy_entries = (uint64_t)found[2] | ((uint64_t)found[3] << 32);
-    return GNNVC_OK;
+    return class_giant_rows(e, fmax);
 }
 
 // The rows of [lo, hi) below the long-row threshold of the 16-wide stages, heaviest degree class first: vertex[] (+ per

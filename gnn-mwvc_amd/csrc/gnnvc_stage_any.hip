@@ -25,7 +25,8 @@
 //            f > 16), the next round's already on their way, issues the round's 32 row loads per lane, then adds them in
 //            order.  f = 1: every lane fetches one neighbour's value per 16 entries, 64 entries a round, and all lanes add
 //            them in the same order.  Rows of any degree can take this loop; the heavy ones get their
-//            sums from k_any_heavy_sums instead (below), which changes who adds, not what is added.
+//            sums from k_any_heavy_sums instead (below), and the giant ones among those from the exact parallel scan behind
+//            k_any_giant_gather (further below): that changes who adds, not what is added.
 //   dense    the outputs of a layer are dealt to the lanes (o = j + 16 t); a lane runs its outputs' chains together, four
 //            k at a time: one 16-byte read of the group's input vector (same address for the group) and one per output of
 //            its transposed weight row.  The number of outputs per lane (1 .. 4) is a template argument chosen by a
@@ -377,13 +378,14 @@ template <int R>
 __global__ __launch_bounds__(kHeavyBlock) void k_any_heavy_sums(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ col,
                                                                const float *__restrict__ in, const uint32_t *__restrict__ list,
                                                                float *__restrict__ hsum, uint32_t f, uint32_t gs, uint32_t lo,
-                                                               uint32_t hi) {
+                                                               uint32_t hi, uint32_t below) {
     extern __shared__ float4 heavy_lds4[];
     float *slab = reinterpret_cast<float *>(heavy_lds4);
     const uint32_t u = list[blockIdx.x];
     if (u < lo || u >= hi) return;   // block-uniform: not in this call's range (k_stage_any skips the same rows)
     const uint32_t tid = threadIdx.x;
     const uint32_t rs = rowptr[u], deg = rowptr[u + 1] - rs;
+    if (deg >= below) return;   // block-uniform: a giant row — k_any_giant_gather and the exact scan have its sums (0xFFFFFFFF: none)
     if (deg == 0) {   // (never listed; kept so that nothing below indexes an empty row)
         if (tid < f) hsum[(size_t)blockIdx.x * f + tid] = 0.0f;
         return;
@@ -448,6 +450,94 @@ __global__ __launch_bounds__(kHeavyBlock) void k_any_heavy_sums(const uint32_t *
     if (tid < f) hsum[(size_t)blockIdx.x * f + tid] = acc;
 }
 
+// ---- giant rows: listed rows of at least the giant threshold (gnnvc_set_generic_giant_rows) leave k_any_heavy_sums' single chain
+// per column for the trained path's exact parallel scan (exact_sum.h; k_giant_segsum / k_giant_segmap / k_giant_sum of
+// gnnvc_kernels.hip, which take the number of streams per row at run time).  What is new here is the gather for any width:
+// k_any_giant_gather writes the row's neighbour values column-major into the slab — stream c of giant row i at
+// slab + off[i] + c * lpad, lpad = the degree rounded up to the scan's window — and k_any_giant_place copies the aggregates to
+// where k_stage_any<kAnyListed> reads a listed row's sums.
+//
+// One 256-thread workgroup per 256 consecutive entries of one row (lpad / 256 workgroups a row: every float of a stream up to
+// lpad is written in every call — the segment sums rely on zero padding).  Groups of G = 2^GS >= f lanes, a group per entry, G
+// passes: lane c < f of a group fetches float c of its entry's neighbour row (4-byte loads: f need not be a multiple of 4), all G
+// fetches of a thread in flight at once.  Entries past the row's end clamp to its last entry for the fetch — a real neighbour,
+// never a pad row — and are stored as +0.0f.  The values cross an LDS tile [f][256 + 4] (at most 33 280 bytes, f = 32) and leave
+// with 16-byte stores, 1 KiB per stream and workgroup.
+constexpr int kAnyGiantBlk = 256, kAnyGiantPitch = kAnyGiantBlk + 4;
+
+// meta[i] = {row, first entry, degree, first gather block}, meta[n_giant].w = the number of gather blocks
+__device__ __forceinline__ uint32_t any_giant_of_block(const uint4 *__restrict__ meta, uint32_t n_giant, uint32_t b) {
+    uint32_t lo = 0, hi = n_giant;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (meta[mid].w <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the listed rows of at least `thresh` entries, with their position in the list: {row, first entry, degree, position}
+__global__ void k_find_any_giant(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ list, uint32_t n_list, uint32_t thresh,
+                                 uint4 *__restrict__ meta, uint32_t *__restrict__ count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_list) return;
+    const uint32_t u = list[i], rs = rowptr[u], deg = rowptr[u + 1] - rs;
+    if (deg >= thresh) meta[atomicAdd(count, 1u)] = make_uint4(u, rs, deg, i);
+}
+
+template <int GS>
+__global__ __launch_bounds__(kAnyGiantBlk) void k_any_giant_gather(const uint32_t *__restrict__ col, const float *__restrict__ in,
+                                                                  float *__restrict__ slab, const uint4 *__restrict__ meta,
+                                                                  const unsigned long long *__restrict__ off, uint32_t n_giant, uint32_t f,
+                                                                  uint32_t win, uint32_t lo, uint32_t hi) {
+    extern __shared__ float4 giant_lds4[];
+    float *tile = reinterpret_cast<float *>(giant_lds4);
+    constexpr uint32_t G = 1u << GS, per = (uint32_t)kAnyGiantBlk >> GS;
+    const uint32_t i = any_giant_of_block(meta, n_giant, blockIdx.x);
+    const uint4 mt = meta[i];
+    if (mt.x < lo || mt.x >= hi) return;   // block-uniform: not in this call's range
+    const uint32_t deg = mt.z;
+    if (deg == 0) return;                  // (never listed; k_giant_sum writes the sum of no addends)
+    const uint32_t j0 = (blockIdx.x - mt.w) * (uint32_t)kAnyGiantBlk;
+    const uint32_t lpad = (deg + win - 1u) / win * win;
+    if (j0 >= lpad) return;                // (block-uniform; the host lays out exactly lpad / 256 blocks a row)
+    const uint32_t tid = threadIdx.x, k0 = tid >> GS, c = tid & (G - 1u);
+    const bool has = c < f;
+    const uint32_t cc = has ? c : f - 1u;
+    uint32_t idx[G];
+    float v[G];
+#pragma unroll
+    for (uint32_t p = 0; p < G; ++p) {
+        const uint32_t j = j0 + k0 + per * p;
+        idx[p] = col[mt.y + (j < deg ? j : deg - 1u)];
+    }
+#pragma unroll
+    for (uint32_t p = 0; p < G; ++p) v[p] = in[(size_t)idx[p] * f + cc];
+    if (has) {
+#pragma unroll
+        for (uint32_t p = 0; p < G; ++p) {
+            const uint32_t k = k0 + per * p;
+            tile[c * (uint32_t)kAnyGiantPitch + k] = j0 + k < deg ? v[p] : 0.0f;
+        }
+    }
+    __syncthreads();
+    float *dst = slab + off[i] + j0;       // (16-byte aligned: off[i], lpad and j0 are multiples of 256 floats)
+    for (uint32_t q = tid; q < f * (uint32_t)(kAnyGiantBlk / 4); q += (uint32_t)kAnyGiantBlk) {
+        const uint32_t cq = q >> 6, k4 = (q & 63u) * 4u;
+        *reinterpret_cast<any_f32x4 *>(dst + (size_t)cq * lpad + k4) = *reinterpret_cast<const any_f32x4 *>(&tile[cq * (uint32_t)kAnyGiantPitch + k4]);
+    }
+}
+
+// aggregate (i, c) of the giant rows -> hsum[pos[i] * f + c], the listed row's sums as k_stage_any<kAnyListed> reads them
+__global__ __launch_bounds__(256) void k_any_giant_place(const uint4 *__restrict__ meta, const uint32_t *__restrict__ pos,
+                                                         const float *__restrict__ agg, float *__restrict__ hsum, uint32_t n_giant, uint32_t f,
+                                                         uint32_t lo, uint32_t hi) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)n_giant * f) return;
+    const uint32_t i = (uint32_t)(t / f), c = (uint32_t)(t % f), u = meta[i].x;
+    if (u < lo || u >= hi) return;         // (its aggregates were not computed in this call)
+    hsum[(size_t)pos[i] * f + c] = agg[t];
+}
+
 AnyShape any_shape(const StagePlan &sp) {
     AnyShape S{};
     S.f = sp.f;
@@ -508,13 +598,56 @@ hipError_t launch_any_heavy_sums(const StageCall &c, const AnyHeavyRows &hr) {
     const dim3 grid(hr.n), block(kHeavyBlock);
 #define GNNVC_HEAVY_LAUNCH(R_)                                                                                            \
     hipLaunchKernelGGL((k_any_heavy_sums<R_>), grid, block, lds, c.stream, g.rowptr, g.col, c.in, hr.list, hr.hsum, \
-                       (uint32_t)sp.f, (uint32_t)gs, c.row_lo, c.row_hi)
+                       (uint32_t)sp.f, (uint32_t)gs, c.row_lo, c.row_hi, hr.below)
     switch (heavy_passes(gs)) {
     case 4: GNNVC_HEAVY_LAUNCH(4); break;
     case 8: GNNVC_HEAVY_LAUNCH(8); break;
     default: GNNVC_HEAVY_LAUNCH(16); break;
     }
 #undef GNNVC_HEAVY_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t find_any_giant_rows(const GraphDev &g, const uint32_t *list, uint32_t n_list, uint32_t thresh, void *meta, uint32_t *count,
+                               hipStream_t stream) {
+    hipError_t rc = hipMemsetAsync(count, 0, sizeof(uint32_t), stream);
+    if (rc != hipSuccess || n_list == 0) return rc;
+    hipLaunchKernelGGL(k_find_any_giant, dim3((n_list + 255) / 256), dim3(256), 0, stream, g.rowptr, list, n_list, thresh,
+                       reinterpret_cast<uint4 *>(meta), count);
+    return hipGetLastError();
+}
+
+hipError_t launch_any_giant(const StageCall &c, const AnyGiantRows &ar, float *hsum, AnyGiantPart part) {
+    const GiantRows &gr = ar.gr;
+    if (c.row_hi <= c.row_lo || gr.n == 0) return hipSuccess;
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
+    if (sp.f < 1 || sp.f > 32 || !gr.meta || !gr.off || !gr.slab || !gr.agg || !ar.pos || !hsum || c.row_hi > g.hi() || c.row_lo < g.lo())
+        return hipErrorInvalidValue;
+    const uint4 *meta = reinterpret_cast<const uint4 *>(gr.meta);
+    const uint32_t f = (uint32_t)sp.f;
+    if (part == AnyGiantPart::kPlace) {
+        const size_t cells = (size_t)gr.n * f;
+        hipLaunchKernelGGL(k_any_giant_place, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c.stream, meta, ar.pos, gr.agg, hsum, gr.n,
+                           f, c.row_lo, c.row_hi);
+        return hipGetLastError();
+    }
+    const uint32_t win = giant_window();
+    if (giant_block() != (uint32_t)kAnyGiantBlk || win % (uint32_t)kAnyGiantBlk != 0 || gr.blocks == 0) return hipErrorInvalidValue;
+    const size_t lds = (size_t)f * kAnyGiantPitch * sizeof(float);   // <= 33 280 bytes
+    const dim3 grid(gr.blocks), block(kAnyGiantBlk);
+#define GNNVC_GIANT_GATHER(GS_)                                                                                              \
+    hipLaunchKernelGGL((k_any_giant_gather<GS_>), grid, block, lds, c.stream, g.col, c.in, gr.slab, meta, gr.off, gr.n, f, win, \
+                       c.row_lo, c.row_hi)
+    switch (heavy_shift(sp.f)) {
+    case 0: GNNVC_GIANT_GATHER(0); break;
+    case 1: GNNVC_GIANT_GATHER(1); break;
+    case 2: GNNVC_GIANT_GATHER(2); break;
+    case 3: GNNVC_GIANT_GATHER(3); break;
+    case 4: GNNVC_GIANT_GATHER(4); break;
+    default: GNNVC_GIANT_GATHER(5); break;
+    }
+#undef GNNVC_GIANT_GATHER
     return hipGetLastError();
 }
 

@@ -22,6 +22,7 @@ _LIB = pathlib.Path(os.environ["GNNVC_LIBRARY"]).resolve() if os.environ.get("GN
 ABI_SYMBOLS = [
     "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_destroy",
     "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_set_generic_heavy_rows",
+    "gnnvc_set_generic_giant_rows",
     "gnnvc_num_layers", "gnnvc_is_fused",
     "gnnvc_in_width", "gnnvc_out_width", "gnnvc_upload_graph", "gnnvc_attach_graph_device", "gnnvc_attach_graph_slice",
     "gnnvc_graph_staging", "gnnvc_staged_columns_ready", "gnnvc_commit_staged_graph",
@@ -105,6 +106,7 @@ def load_library():
     L.gnnvc_set_option.argtypes = [vp, C.c_char_p, C.c_long]
     L.gnnvc_get_info.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
     L.gnnvc_set_generic_heavy_rows.argtypes = [vp, u32]
+    L.gnnvc_set_generic_giant_rows.argtypes = [vp, u32, C.c_int]
     for name in ("gnnvc_num_layers", "gnnvc_is_fused", "gnnvc_in_width", "gnnvc_out_width",
                  "gnnvc_num_stages", "gnnvc_synchronize"):
         getattr(L, name).argtypes = [vp]
@@ -235,6 +237,14 @@ class Engine:
         forward or stage call.  get_info: "generic_heavy_from", "generic_heavy_rows", "generic_heavy_entries",
         "generic_heavy_last_rows"."""
         self._check(self._L.gnnvc_set_generic_heavy_rows(self._h, from_degree))
+
+    def set_generic_giant_rows(self, from_degree: int, segments: int = -1):
+        """Listed heavy rows of at least `from_degree` entries are summed by the exact parallel scan in generic stages
+        (gnnvc_set_generic_giant_rows); 0 = none, the default is 16384.  segments: 1 = one stream on several waves, 0 = one wave
+        walks each stream, -1 = by the graph.  Same bits for every pair of values; takes effect at the next forward or stage call.
+        get_info: "generic_giant_from", "generic_giant_segments", "generic_giant_rows", "generic_giant_entries",
+        "generic_giant_last_rows", "generic_giant_last_segmented"."""
+        self._check(self._L.gnnvc_set_generic_giant_rows(self._h, from_degree, segments))
 
     def audit_report(self) -> dict:
         """The on-device audit's counters and its last failure (option "audit_period"), key -> value."""

@@ -301,7 +301,10 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         before this option existed.  2 (tests): the trained shape is sent through the generic kernel as well,
  *                         none of its plans used.  Generic stages have no per-graph plan but the list of their heavy rows
  *                         (gnnvc_set_generic_heavy_rows below: rows of many entries get a workgroup each for their neighbour
- *                         sums, with the same bits), and "audit_period" audits nothing on
+ *                         sums, with the same bits) and, among those, of their giant rows (gnnvc_set_generic_giant_rows below:
+ *                         rows of 16 384 entries and more are summed by the exact parallel scan, with the same bits; keys
+ *                         "generic_giant_from", "generic_giant_segments", "generic_giant_rows", "generic_giant_entries",
+ *                         "generic_giant_last_rows", "generic_giant_last_segmented"), and "audit_period" audits nothing on
  *                         them, as on an unfused model: they are audited on demand, by gnnvc_forward_audited,
  *                         gnnvc_forward_audited_device and gnnvc_audit_stage_device (kernel k_audit_any: a wave per row, the
  *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
@@ -334,14 +337,39 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value);
  *   from_degree >= 1   any value is legal; with 1 every non-empty row is heavy.  The default is 512, the long-row threshold of the
  *                      trained path.
  * The value takes effect at the next forward or stage call; an attached graph is classed again then.  On a model without a
- * generic stage list the value is stored and does nothing.  Rows of 16 384 entries and more still run one chain per column
- * (the trained path's exact parallel sums of giant rows are not used here).  A multi-device handle: GNNVC_ERR_UNSUPPORTED; a
- * null engine: GNNVC_ERR_INVALID.
+ * generic stage list the value is stored and does nothing.  Listed rows of 16 384 entries and more leave k_any_heavy_sums'
+ * one chain per column for the exact parallel scan (gnnvc_set_generic_giant_rows below).  A multi-device handle:
+ * GNNVC_ERR_UNSUPPORTED; a null engine: GNNVC_ERR_INVALID.
  * gnnvc_get_info: "generic_heavy_from" (the threshold in force), "generic_heavy_rows" and "generic_heavy_entries" (the listed
  * rows of the attached graph or slice and their entries, from its last classing; 0 before one), "generic_heavy_last_rows" (the
  * listed rows the last forward or stage call sent down the heavy path — rows outside a stage call's range are skipped on the
  * device and still counted; 0 when it launched one kernel per stage). */
 int gnnvc_set_generic_heavy_rows(gnnvc_engine *e, uint32_t from_degree);
+
+/* Giant rows of generic stages.  k_any_heavy_sums adds a listed row with one fp32 chain per column, about 4 ns a neighbour: a hub
+ * of several hundred thousand entries holds every stage for milliseconds.  Listed rows of at least from_degree entries therefore
+ * take the route the trained model's giant rows take, for any stage input width 1 <= f <= 32: k_any_giant_gather (a 256-thread
+ * workgroup per 256 entries) writes the row's neighbour values column-major into a slab of the engine's own, one stream of
+ * floats per column in stored order; k_giant_sum — behind k_giant_segsum and k_giant_segmap when a stream is spread over several
+ * waves — evaluates each stream's sequential fp32 sum with the exact parallel scan (bit for bit the chain's result, for any
+ * data); k_any_giant_place puts the sums where the listed rows' k_stage_any launch reads them.  Results are bit-identical for
+ * every pair of values.
+ *   from_degree   0: no giant rows, every listed row is summed by k_any_heavy_sums.  The default is 16 384, the trained path's
+ *                 "giant_row_threshold".  Giant rows are a subset of the heavy rows: a row is giant iff the heavy threshold is not
+ *                 0 and its degree is at least max(from_degree, the heavy threshold); with heavy rows off there are none.
+ *   segments      1: one stream on several waves (segments of 4096 addends, k_giant_segsum / k_giant_segmap); 0: one wave walks
+ *                 each stream; -1 (default): by the graph, as the trained path's "giant_segments" — several waves where the longest
+ *                 stream's walk is what a stage would wait for.  Any other value is stored: positive as 1, negative as -1.
+ * Both values take effect at the next forward or stage call; an attached graph is classed again then (one more pass over the
+ * heavy list, one read-back, the slab: the widest stage input x the rows' entries rounded up to 1024, in floats).  A slab that
+ * does not fit in device memory leaves the graph without giant rows; that is not an error.  On a model without a generic stage
+ * list the values are stored and do nothing.  A multi-device handle: GNNVC_ERR_UNSUPPORTED; a null engine: GNNVC_ERR_INVALID.
+ * gnnvc_get_info: "generic_giant_from" and "generic_giant_segments" (as stored), "generic_giant_rows" and
+ * "generic_giant_entries" (the giant rows of the attached graph or slice and their entries, from its last classing),
+ * "generic_giant_last_rows" (the giant rows of the last forward or stage call; rows outside a stage call's range are skipped on
+ * the device and still counted), "generic_giant_last_segmented" (1: that call ran k_giant_segsum and k_giant_segmap).
+ * "generic_heavy_rows", "generic_heavy_entries" and "generic_heavy_last_rows" count every listed row, the giant ones included. */
+int gnnvc_set_generic_giant_rows(gnnvc_engine *e, uint32_t from_degree, int segments);
 
 /* Model introspection (what model::layers holds). */
 int gnnvc_num_layers(const gnnvc_engine *e);
