@@ -1,8 +1,8 @@
 // gnnvc_audit_any.hip — k_audit_any: the on-device audit of a GENERIC fused stage (gnnvc_forward_audited*,
 // gnnvc_audit_stage_device).  It recomputes one stage — graph layer of input width f, d = 1 .. 6 dense layers of widths
 // n[0 .. d), ReLU | sigmoid — for rows [lo, hi) from the stage's own input and compares every value the fused path wrote: the
-// n[d - 1]-wide output row, or the scores and the logits on the sigmoid stage.  Bounds: stage_any_fits (1 <= f <= 32, every
-// width but the last <= 64, the last <= 32).
+// n[d - 1]-wide output row, or the scores and the logits on the sigmoid stage.  Bounds: whatever stage_any_fits admits (1 <= f <= 32,
+// every width but the last <= 64 — <= 128 in a big stage, gnnvc_set_generic_big_stages — the last <= 32).
 //
 // What is computed is the layer-by-layer kernels' arithmetic (k_graph_layer, k_linear, k_relu, k_sigmoid):
 //   neighbour-sum column c   one fp32 add chain in stored CSR order from +0.0f;
@@ -16,11 +16,11 @@
 // the outputs o = j + 16 t, transpose the weights into LDS at a padded pitch and walk k four at a time, this one is laid out the
 // other way round:
 //   a WAVE per row (four rows per 256-thread workgroup, grid-stride, no workgroup barrier anywhere);
-//   lane o owns output o of every layer (widths are at most 64, the wave's width) and runs its whole chain, k advancing one at
-//   a time; the weight W[k][o] is read where the model put it, in the stored [k][n] layout straight from the parameter block (the
+//   lane o owns output o of every layer — and output o + 64 of a layer wider than the wave (a big stage's, at most 128), a second
+//   chain of its own behind the first — and runs its whole chain, k advancing one at a time; the weight W[k][o] is read where the model put it, in the stored [k][n] layout straight from the parameter block (the
 //   lanes of a wave read consecutive words; a stage's parameters are a few KiB that stay in the caches), nothing is transposed
 //   and nothing copied to LDS;
-//   the row's activations live in two per-wave LDS vectors of 68 floats (static LDS, 2176 bytes a workgroup) that the layers
+//   the row's activations live in two per-wave LDS vectors of 132 floats (static LDS, 4224 bytes a workgroup) that the layers
 //   ping-pong through; x[k] is one broadcast read;
 //   the graph row has K = 2 f + 3 <= 67 columns — more than a wave — so it is written by a loop over c = lane, lane + 64;
 //   lanes c < f each run their column's add chain over the neighbours: the wave fetches 64 column ids at a time (the next 64
@@ -57,7 +57,9 @@ __device__ __forceinline__ void wave_handoff() {
 }
 
 constexpr int kBlockThreads = 256, kWaves = kBlockThreads / 64;
-constexpr int kVec = 68;   // floats per activation vector: the graph row's 2 * 32 + 3 = 67 columns, hidden widths up to 64
+constexpr int kVec = 132;   // floats per activation vector: the graph row's 2 * 32 + 3 = 67 columns, hidden widths up to 128
+static_assert(kVec >= 2 * kAnyMaxF + 3 && kVec >= kAnyBigHidden && kAnyBigHidden <= 2 * 64 && kAnyMaxLast <= 32,
+              "the vectors, the two outputs a lane owns and the column code are sized for what stage_any_route admits");
 
 struct AuditGraph {   // the graph as handed over
     const uint32_t *rowptr, *col, *w, *nw;
@@ -132,6 +134,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_audit_any(AuditGraph g, float
             r = acc + W[K * N + o];
             if (l + 1 < d) {
                 if (lane < N) b[lane] = relu_ref(r);
+                if (N > 64) {   // (wave-uniform) a layer wider than the wave: output lane + 64, the same way
+                    const int o1 = min(lane + 64, N - 1);
+                    float acc1 = 0.0f;
+#pragma unroll 8
+                    for (int k = 0; k < K; ++k) acc1 = __builtin_fmaf(a[k], W[k * N + o1], acc1);
+                    const float r1 = acc1 + W[K * N + o1];
+                    if (lane + 64 < N) b[lane + 64] = relu_ref(r1);
+                }
                 wave_handoff();
                 float *t = a;
                 a = b;
@@ -198,10 +208,7 @@ hipError_t launch_audit_any(const StageCall &c, unsigned long long *rec, bool re
     S.f = sp.f;
     S.d = sp.nd;
     for (int l = 0; l < kMaxDenseLayers; ++l) S.n[l] = (l < sp.nd) ? sp.wn[l] : 0;
-    // (stage_any_fits' bounds are what the vectors and the column code are sized for)
-    if (2 * S.f + 3 > kVec || S.n[S.d - 1] > 32) return hipErrorInvalidValue;
-    for (int l = 0; l < S.d; ++l)
-        if (S.n[l] < 1 || S.n[l] > 64) return hipErrorInvalidValue;
+    // (stage_any_fits' bounds are what the vectors and the column code are sized for: the static_assert at kVec)
     // the graph as handed over and nothing else: no plan's view can reach the audit
     const AuditGraph plain{g.rowptr, g.col, g.w, g.nw};
     // a persistent grid: a wave per row, up to eight workgroups on each of 256 CUs

@@ -91,6 +91,8 @@ bool zero_terms_may_go(const Layer &l) {
     return true;
 }
 
+void plan_generic(gnnvc_engine *e);
+
 // Widths through the network; decides fused vs layer-by-layer.
 int plan_model(gnnvc_engine *e) {
     // input width: a leading graph layer accepts any width; a leading linear fixes it.
@@ -162,15 +164,21 @@ int plan_model(gnnvc_engine *e) {
         i += 7;
     }
     if (ok && !st.empty() && st.back().sigmoid_last) e->stages = std::move(st);
+    plan_generic(e);
+    return GNNVC_OK;
+}
 
-    // generic stages (k_stage_any): (Graph, (Linear, activation){d})+ with 1 <= d <= kMaxDenseLayers, d free per stage, any widths
-    // within stage_any_fits (which knows the LDS bound too); every activation a ReLU but the model's last, a sigmoid (a model that
-    // ends in a ReLU stays layer by layer, as for the trained shapes).  One stage outside the bounds leaves the whole model layer
-    // by layer.
+// generic stages (k_stage_any): (Graph, (Linear, activation){d})+ with 1 <= d <= kMaxDenseLayers, d free per stage, any widths
+// within stage_any_fits (which knows the LDS bounds too: the default one, and the opt-in one of gnnvc_set_generic_big_stages, which
+// each stage carries as big_lds); every activation a ReLU but the model's last, a sigmoid (a model that ends in a ReLU stays layer
+// by layer, as for the trained shapes).  One stage outside the bounds leaves the whole model layer by layer.  Derives e->gstages
+// anew from the layers (their parameter offsets are plan_model's): at model load, and when the opt-in's limit moves.
+void plan_generic(gnnvc_engine *e) {
+    e->gstages.clear();
     std::vector<StagePlan> gs;
     bool gok = !e->layers.empty();
-    f = e->in_width;
-    for (i = 0; gok && i < e->layers.size();) {
+    int f = e->in_width;
+    for (size_t i = 0; gok && i < e->layers.size();) {
         const Layer *L = &e->layers[i];
         const size_t left = e->layers.size() - i;
         gok = L[0].kind == kGraph;
@@ -193,13 +201,13 @@ int plan_model(gnnvc_engine *e) {
         if (!gok) break;
         sp.n3 = sp.wn[sp.nd - 1];
         if (sp.nd == 3) { sp.n1 = sp.wn[0]; sp.n2 = sp.wn[1]; }
+        sp.big_lds = e->big_lds;
         gok = gnnvc::stage_any_fits(sp);
         gs.push_back(sp);
         f = sp.n3;
         i += at;
     }
     if (gok && !gs.empty()) e->gstages = std::move(gs);
-    return GNNVC_OK;
 }
 
 int upload_params(gnnvc_engine *e) {
@@ -962,6 +970,35 @@ int gnnvc_set_generic_giant_rows(gnnvc_engine *e, uint32_t from_degree, int segm
     return GNNVC_OK;
 }
 
+int gnnvc_set_generic_big_stages(gnnvc_engine *e, uint32_t lds_bytes) {
+    if (!e) return GNNVC_ERR_INVALID;
+    NOT_ON_MULTI(e, "gnnvc_set_generic_big_stages");
+    if (lds_bytes != 0 && (lds_bytes < 65536u || lds_bytes > 163840u))
+        return fail(e, GNNVC_ERR_INVALID, "gnnvc_set_generic_big_stages: %u is neither 0 nor within 65536 .. 163840", lds_bytes);
+    if (lds_bytes == e->big_lds) return GNNVC_OK;
+    if (lds_bytes) {   // the big instantiations' LDS limit on this device: refused here, never inside a forward
+        const int rc = use_device(e);
+        if (rc) return rc;
+        if (gnnvc::allow_big_stages() != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e, GNNVC_ERR_UNSUPPORTED, "gnnvc_set_generic_big_stages: the runtime refuses k_stage_any 160 KiB of dynamic LDS on device %d", e->device);
+        }
+    }
+    e->big_lds = lds_bytes;
+    plan_generic(e);                // (at once, as option "generic_stages": the stage list and everything the ABI reports of it)
+    e->pg.heavy_known = false;      // an attached graph is classed again by the next generic stage that runs (class_heavy_rows)
+    return GNNVC_OK;
+}
+
+// "<prefix><s>" of a generic model: the stage index, or -1 (no such stage, not a number, the model is not generic)
+static long generic_stage_index(const gnnvc_engine *e, const std::string &k, size_t prefix_len) {
+    const char *num = k.c_str() + prefix_len;
+    char *end = nullptr;
+    const long s = strtol(num, &end, 10);
+    if (!e->generic_on() || *num < '0' || *num > '9' || *end != 0 || s >= (long)e->gstages.size()) return -1;
+    return s;
+}
+
 int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     if (!e || !key || !value) return GNNVC_ERR_INVALID;
     const std::string k(key);
@@ -991,11 +1028,20 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k == "generic_giant_last_rows") *value = (long)e->ggiant_last_rows;
     else if (k == "generic_giant_last_segmented") *value = e->ggiant_last_segmented ? 1 : 0;
     else if (k.rfind("generic_stage_layers_", 0) == 0) {   // "generic_stage_layers_<s>": dense layers of stage s of a generic model
-        const char *num = k.c_str() + sizeof("generic_stage_layers_") - 1;
-        char *end = nullptr;
-        const long s = strtol(num, &end, 10);
-        if (!e->generic_on() || *num < '0' || *num > '9' || *end != 0 || s >= (long)e->gstages.size()) return GNNVC_ERR_INVALID;
+        const long s = generic_stage_index(e, k, sizeof("generic_stage_layers_") - 1);
+        if (s < 0) return GNNVC_ERR_INVALID;
         *value = e->gstages[(size_t)s].nd;
+    }
+    else if (k == "generic_big_lds") *value = (long)e->big_lds;                       // gnnvc_set_generic_big_stages, as set
+    else if (k.rfind("generic_stage_lds_bytes_", 0) == 0) {   // "generic_stage_lds_bytes_<s>": the stage's LDS layout at 256 threads
+        const long s = generic_stage_index(e, k, sizeof("generic_stage_lds_bytes_") - 1);
+        if (s < 0) return GNNVC_ERR_INVALID;
+        *value = (long)gnnvc::stage_any_route(e->gstages[(size_t)s]).lds256;
+    }
+    else if (k.rfind("generic_stage_threads_", 0) == 0) {     // "generic_stage_threads_<s>": the workgroup size its launches use
+        const long s = generic_stage_index(e, k, sizeof("generic_stage_threads_") - 1);
+        if (s < 0) return GNNVC_ERR_INVALID;
+        *value = gnnvc::stage_any_route(e->gstages[(size_t)s]).threads;
     }
     else if (k == "audit_runs") *value = (long)e->audit_runs;
     else if (k == "audit_failures") *value = (long)e->audit_failures;

@@ -61,6 +61,9 @@ struct gnnvc_engine {
     // widths fit gnnvc::stage_any_fits — the trained shapes included, which only option value 2 sends there.
     std::vector<StagePlan> gstages;
     bool generic_ran = false;       // gnnvc_get_info "generic_stages_active": the last forward ran k_stage_any
+    // gnnvc_set_generic_big_stages: 0 = off, else the LDS limit (65 536 .. 163 840 bytes) under which stages outside the default
+    // bounds are admitted to gstages (gnnvc::stage_any_route; every plan in gstages carries the value it was derived under)
+    uint32_t big_lds = 0;
     bool generic_on() const { return !gstages.empty() && (opt.generic == 2 || (opt.generic == 1 && stages.empty())); }
     const std::vector<StagePlan> &stage_list() const { return generic_on() ? gstages : stages; }   // what the ABI reports and runs
     // Heavy rows of generic stages (gnnvc_set_generic_heavy_rows): rows of at least heavy_from entries (0: none) get a workgroup

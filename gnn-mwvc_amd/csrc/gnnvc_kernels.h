@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <hip/hip_vector_types.h>
 
+#include <atomic>
 #include <vector>
 
 #include "gnnvc_device_mem.h"
@@ -77,6 +78,7 @@ struct StagePlan {
     int variant = -1;         // index into the compiled instantiations, -1 = none
     int nd = 3;               // dense layers
     int wn[kMaxDenseLayers] = {0, 0, 0, 0, 0, 0};   // their widths, wn[nd - 1] == n3 (filled for generic stages)
+    uint32_t big_lds = 0;     // a generic stage: the LDS limit of gnnvc_set_generic_big_stages it was planned under (0 = off)
     uint32_t skip_ok = 0;     // bit l set: dense layer l + 1 has finite weights only and no bias with the bits of -0.0f, so terms
                               // whose input is +-0 may be left out of its chains bit for bit (set at model load)
 };
@@ -185,8 +187,8 @@ hipError_t write_verdicts(const VerdictWords &vw, uint32_t *out_dev, hipStream_t
 // fused bits), [5] ~(row << 32 | audit bits).  repair: the audit's value is written over every mismatching one.
 constexpr int kAuditWords = 8;
 hipError_t launch_audit_stage(const StageCall &c, unsigned long long *rec, bool repair);
-// The same check of a GENERIC stage (k_audit_any, gnnvc_audit_any.hip; any shape stage_any_fits accepts): a wave per row, lane o
-// = output o, the weights read as stored — nothing shared with k_stage_any or k_audit_stage.  The same record; [0] is the exact
+// The same check of a GENERIC stage (k_audit_any, gnnvc_audit_any.hip; any shape stage_any_fits accepts, big stages included): a
+// wave per row, lane o = outputs o and o + 64, the weights read as stored — nothing shared with k_stage_any or k_audit_stage.  The same record; [0] is the exact
 // number of mismatching values, [1] counts every pair of NaNs (k_audit_stage: those whose bits differ).
 hipError_t launch_audit_any(const StageCall &c, unsigned long long *rec, bool repair);
 // the audit's test hook: out[at]'s lowest mantissa bit flipped by one lane
@@ -194,12 +196,30 @@ hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 
 // A fused stage of ANY widths and depth within stage_any_fits (k_stage_any, gnnvc_stage_any.hip) — models of the pattern
 // (Graph, (Linear, ReLU){d})+ with 1 <= d <= kMaxDenseLayers per stage and a sigmoid in place of the model's last ReLU, that are
-// not of the trained shapes.  stage_any_fits: 1 <= f <= 32, every width but the last <= 64, the last <= 32, and the stage's LDS
-// layout (transposed weights, biases, sixteen pairs of vectors) within the 64 KiB a launch gets without raising the kernel's
-// limit — plan_model and the launcher both ask this one function.  One launch per call; the graph's rowptr / col / w / nw only
-// (no plan); rows of every degree.  in: (n + 1) x f rows (the pad row is never read), out: rows [row_lo, row_hi) of an
-// (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
+// not of the trained shapes.  stage_any_route decides what is admitted and where it goes; plan_model, the launchers, the engine's
+// read-outs and the audit all ask it (stage_any_fits = its `ok`):
+//   a SMALL stage    1 <= f <= 32, every width but the last <= 64, the last <= 32, and the stage's LDS layout (transposed weights,
+//                    biases, sixteen pairs of vectors) within the 64 KiB a launch gets without raising the kernel's limit: the
+//                    default instantiations at 256 threads, whatever sp.big_lds says;
+//   a BIG stage      sp.big_lds != 0 (gnnvc_set_generic_big_stages, 65 536 .. 163 840), not small, every width but the last <= 128,
+//                    the last <= 32, and the layout AT 256 THREADS within sp.big_lds: a big instantiation at 1024, 512 or 256
+//                    threads — the largest whose own layout (64 / 32 / 16 pairs of vectors) fits sp.big_lds;
+//   anything else    not admitted: the model runs layer by layer.
+// One launch per call; the graph's rowptr / col / w / nw only (no plan); rows of every degree.  in: (n + 1) x f rows (the pad row
+// is never read), out: rows [row_lo, row_hi) of an (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
+constexpr int kAnyMaxF = 32, kAnySmallHidden = 64, kAnyBigHidden = 128, kAnyMaxLast = 32;   // the widths stage_any_route admits
+struct AnyRoute {
+    bool ok = false, big = false;
+    int threads = 256;           // the workgroup size the launcher uses
+    size_t lds256 = 0, lds = 0;  // the layout's bytes at 256 threads (what admits the stage), and at `threads` (what is launched)
+};
+AnyRoute stage_any_route(const StagePlan &sp);
 bool stage_any_fits(const StagePlan &sp);
+// raises the big instantiations' dynamic-LDS limit on the current device (once per device); an error = the runtime refuses it
+hipError_t allow_big_stages();
+// kernels that need more than 64 KiB of dynamic LDS must be told so once per device (engines on several devices may live in one
+// process; `done` has one bit per device ordinal)
+hipError_t allow_dynamic_lds(const void *func, int bytes, std::atomic<uint64_t> &done);
 // Heavy rows of a generic stage (gnnvc_set_generic_heavy_rows): rows of at least `from` entries, listed by find_long_rows, get a
 // workgroup each for their neighbour sums (k_any_heavy_sums: hsum[i * f + c] for list position i, the same chain per column in
 // stored order) and k_stage_any is launched twice — over the rows below `from` (kLight), then over the listed ones with their

@@ -5174,9 +5174,8 @@ hipError_t launch_stage0_blocked(const StageCall &c, const BlockedPlan &bp, cons
 }
 
 // ---- LDS-table plan of the F = 1 stage ----------------------------------------------------
-// kernels that need more than 64 KiB of dynamic LDS must be told so once per device (engines on several devices may
-// live in one process; `done` has one bit per device ordinal)
-static hipError_t allow_dynamic_lds(const void *func, int bytes, std::atomic<uint64_t> &done) {
+// (declared in gnnvc_kernels.h: the generic stages' big instantiations share it)
+hipError_t allow_dynamic_lds(const void *func, int bytes, std::atomic<uint64_t> &done) {
     int dev = 0;
     hipError_t rc = hipGetDevice(&dev);
     if (rc != hipSuccess) return rc;

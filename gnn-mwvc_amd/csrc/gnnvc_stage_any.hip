@@ -12,8 +12,11 @@
 //   relu_ref, or sigmoid_ref on the last layer of the last stage (the logits are its input).
 // Compile with -ffp-contract=off, like the rest of the library.
 //
-// Bounds (stage_any_fits): 1 <= f <= 32, 1 <= d <= 6 dense layers, every width but the last 1 .. 64, the last 1 .. 32, and the LDS
-// layout below within 64 KiB (the dynamic LDS a launch gets without raising the kernel's limit, which nothing here does).
+// Bounds (stage_any_route, which stage_any_fits asks): 1 <= f <= 32, 1 <= d <= 6 dense layers, every width but the last 1 .. 64, the
+// last 1 .. 32, and the LDS layout below within 64 KiB (the dynamic LDS a launch gets without raising the kernel's limit).  A
+// stage within these launches the kernel's default instantiations, whatever else is set.  With gnnvc_set_generic_big_stages a
+// stage outside them is admitted when its hidden widths are at most 128 and its layout at 256 threads fits the limit given (at
+// most 160 KiB, a CU's LDS): it launches a BIG instantiation (below), whose limit allow_big_stages has raised.
 //
 // Shape of the kernel: 256-thread workgroups walk the row range 16 rows at a time (grid-stride; no workgroup barrier inside
 // the walk, so a wave that sits on a very long row holds up nobody else).  Each workgroup first transposes the stage's
@@ -34,6 +37,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#include <cstdlib>
 
 #include "expf_glibc.h"
 #include "gnnvc_kernels.h"
@@ -78,7 +83,7 @@ __host__ __device__ inline int any_round4(int v) { return (v + 3) / 4 * 4; }
 __host__ __device__ inline int any_pitch(int k) {
     return 4 * (((k + 3) / 4) | 1);   // an odd number of 16-byte slots: rows o .. o + 15 start in sixteen different slots
 }
-__host__ __device__ inline StageAnyLayout stage_any_layout(const AnyShape &S) {
+__host__ __device__ inline StageAnyLayout stage_any_layout(const AnyShape &S, int rows) {   // rows: a workgroup's rows per pass (threads / 16)
     StageAnyLayout L;
     int K = 2 * S.f + 3, wsum = 0, nsum = 0, a = K, b = 0;   // a, b: the longest vector that lands in A, in B
     for (int l = 0; l < S.d; ++l) {
@@ -95,10 +100,11 @@ __host__ __device__ inline StageAnyLayout stage_any_layout(const AnyShape &S) {
     L.grp = L.bias + any_round4(nsum);
     L.hb = any_round4(a);
     L.gs = L.hb + any_round4(b);
-    L.total = L.grp + kAnyRows * L.gs;
+    L.total = L.grp + rows * L.gs;
     return L;
 }
-constexpr size_t kAnyLdsBytes = 64u * 1024u;
+constexpr size_t kAnyLdsBytes = 64u * 1024u;         // the dynamic LDS a launch gets without raising the kernel's limit
+constexpr size_t kAnyBigLdsBytes = 160u * 1024u;     // a CU's LDS: the most gnnvc_set_generic_big_stages may allow a workgroup
 
 namespace {
 
@@ -258,13 +264,19 @@ struct AnyRowSel {
     const float *hsum;
 };
 
-template <int MODE>
-__global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
+// The BIG form (gnnvc_set_generic_big_stages; BIG = true) is the same source with two more template arguments: BLOCK = 256, 512 or
+// 1024 threads (16 / 32 / 64 rows a pass: above 80 KiB of LDS one workgroup fits a CU, and its waves are all the CU has to cover
+// the LDS reads of the dense layers with), and hidden layers of up to 128 outputs, taken 64 outputs at a time — the chains of
+// different outputs are independent, so a layer's second half is the first half's code on the next 64 transposed rows.  The
+// defaults are the kernel as it was.
+template <int MODE, int BLOCK = kAnyBlock, bool BIG = false>
+__global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
                                                         float *__restrict__ out, float *__restrict__ logits, uint32_t lo, uint32_t hi,
                                                         AnyShape S, int sig, AnyRowSel R) {
     extern __shared__ float4 any_lds4[];
     float *lds = reinterpret_cast<float *>(any_lds4);
-    const StageAnyLayout L = stage_any_layout(S);
+    constexpr int ROWS = BLOCK / 16;
+    const StageAnyLayout L = stage_any_layout(S, ROWS);
     const int f = S.f, d = S.d, k1 = 2 * f + 3;
     float *bs = lds + L.bias;
     // parameters, transposed: wt[o * pitch + k] = W[k * N + o]   (W1 b1 W2 b2 ... are contiguous from P)
@@ -274,8 +286,8 @@ __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, c
         int K = k1;
         for (int l = 0; l < d; ++l) {
             const int N = S.n[l], p = any_pitch(K);
-            for (int i = threadIdx.x; i < K * N; i += kAnyBlock) wt[(i % N) * p + i / N] = W[i];
-            for (int i = threadIdx.x; i < N; i += kAnyBlock) bl[i] = W[K * N + i];
+            for (int i = threadIdx.x; i < K * N; i += BLOCK) wt[(i % N) * p + i / N] = W[i];
+            for (int i = threadIdx.x; i < N; i += BLOCK) bl[i] = W[K * N + i];
             W += K * N + N;
             wt += N * p;
             bl += N;
@@ -288,7 +300,7 @@ __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, c
     constexpr bool listed = MODE == kAnyListed;
     // (the walk is over rows, or over positions of the list)
     const uint64_t walk_lo = listed ? 0u : (uint64_t)lo, walk_hi = listed ? (uint64_t)R.nlist : (uint64_t)hi;
-    for (uint64_t base = walk_lo + (uint64_t)blockIdx.x * kAnyRows; base < walk_hi; base += (uint64_t)gridDim.x * kAnyRows) {
+    for (uint64_t base = walk_lo + (uint64_t)blockIdx.x * ROWS; base < walk_hi; base += (uint64_t)gridDim.x * ROWS) {
         const uint64_t u64 = base + (uint64_t)grp;
         if (u64 >= walk_hi) continue;   // (no workgroup barrier below: a group without a row just waits for the next round)
         uint32_t u = (uint32_t)u64;
@@ -329,7 +341,11 @@ __global__ __launch_bounds__(kAnyBlock) void k_stage_any(AnyGraph g, float ws, c
         int K = k1;
         for (int l = 0; l + 1 < d; ++l) {
             const int N = S.n[l], p = any_pitch(K);
-            any_hidden_n(src, K, wt, p, bl, N, j, dst);
+            if (BIG) {   // (N <= 128: one or two passes; outputs ob + j + 16 t, the clamp and the k tail as in the one pass)
+                for (int ob = 0; ob < N; ob += 64) any_hidden_n(src, K, wt + ob * p, p, bl + ob, N - ob, j, dst + ob);
+            } else {
+                any_hidden_n(src, K, wt, p, bl, N, j, dst);
+            }
             wave_lds_sync();
             wt += N * p;
             bl += N;
@@ -548,18 +564,63 @@ AnyShape any_shape(const StagePlan &sp) {
 
 }  // namespace
 
-bool stage_any_fits(const StagePlan &sp) {
-    if (sp.f < 1 || sp.f > 32 || sp.nd < 1 || sp.nd > kMaxDenseLayers) return false;
-    for (int l = 0; l < sp.nd; ++l)
-        if (sp.wn[l] < 1 || sp.wn[l] > (l + 1 < sp.nd ? 64 : 32)) return false;
-    return (size_t)stage_any_layout(any_shape(sp)).total * sizeof(float) <= kAnyLdsBytes;
+// GNNVC_BIG_THREADS (256 | 512 | 1024, read once per process) forces the big form's workgroup size where that size's layout fits
+// the limit, so that one library can be measured three ways (profiles/generic_stages/README.md, "Big stages"); anything else, or
+// a size that does not fit, leaves the rule in force.
+static int forced_big_threads() {
+    static const int v = [] {
+        const char *s = getenv("GNNVC_BIG_THREADS");
+        const int t = s && *s ? atoi(s) : 0;
+        return t == 256 || t == 512 || t == 1024 ? t : 0;
+    }();
+    return v;
 }
+
+// THE function that decides what is admitted and where it goes (plan_model, the launchers here, the engine's read-outs and the
+// audit's launcher all ask it, through stage_any_fits where a yes / no is enough).
+AnyRoute stage_any_route(const StagePlan &sp) {
+    AnyRoute r;
+    if (sp.f < 1 || sp.f > kAnyMaxF || sp.nd < 1 || sp.nd > kMaxDenseLayers) return r;
+    bool small = true;   // the default bounds: the kernel as it always was
+    for (int l = 0; l < sp.nd; ++l) {
+        const bool last = l + 1 == sp.nd;
+        if (sp.wn[l] < 1 || sp.wn[l] > (last ? kAnyMaxLast : kAnyBigHidden)) return r;
+        if (!last && sp.wn[l] > kAnySmallHidden) small = false;
+    }
+    const AnyShape S = any_shape(sp);
+    r.lds256 = (size_t)stage_any_layout(S, kAnyRows).total * sizeof(float);
+    if (small && r.lds256 <= kAnyLdsBytes) {
+        r.ok = true;
+        r.lds = r.lds256;
+        return r;
+    }
+    // the opt-in (gnnvc_set_generic_big_stages): admitted by the layout at 256 threads
+    if (sp.big_lds < kAnyLdsBytes || sp.big_lds > kAnyBigLdsBytes || r.lds256 > sp.big_lds) return r;
+    r.ok = r.big = true;
+    r.lds = r.lds256;
+    // the workgroup size: the largest whose layout fits the limit (the weights are in LDS once per workgroup, and above 80 KiB a
+    // CU holds one workgroup: its waves are all there is to cover the dense layers' LDS reads; measured, 1024 against 512 against
+    // 256 threads: profiles/generic_stages/README.md, "Big stages")
+    const auto bytes_at = [&](int t) { return (size_t)stage_any_layout(S, t / 16).total * sizeof(float); };
+    const int forced = forced_big_threads();
+    const int cap = forced && bytes_at(forced) <= sp.big_lds ? forced : 1024;   // (a forced size that does not fit: the rule)
+    for (int t : {1024, 512}) {
+        if (t > cap || bytes_at(t) > sp.big_lds) continue;
+        r.threads = t;
+        r.lds = bytes_at(t);
+        break;
+    }
+    return r;
+}
+
+bool stage_any_fits(const StagePlan &sp) { return stage_any_route(sp).ok; }
 
 hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows &hr) {
     if (c.row_hi <= c.row_lo) return hipSuccess;
     const StagePlan &sp = *c.sp;
     const GraphDev &g = *c.g;
-    if (!stage_any_fits(sp) || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
+    const AnyRoute route = stage_any_route(sp);
+    if (!route.ok || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
     AnyRowSel sel{0u, 0u, nullptr, nullptr};
     if (rows == AnyRows::kLight) {
         sel = AnyRowSel{hr.from, 0u, nullptr, nullptr};
@@ -570,22 +631,51 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
     }
     const AnyGraph plain{g.rowptr, g.col, g.w, g.nw};
     const AnyShape S = any_shape(sp);
-    const size_t lds = (size_t)stage_any_layout(S).total * sizeof(float);   // <= 64 KiB (stage_any_fits)
-    // a persistent grid: as many workgroups as the LDS lets a CU hold (at most 8), on 256 CUs
-    const unsigned per_cu = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (160u * 1024u) / (lds + 1024u)));
+    const size_t lds = route.lds;   // <= 64 KiB, or (a big stage) <= the limit gnnvc_set_generic_big_stages was given
+    // a persistent grid: as many workgroups as the LDS lets a CU hold (at most 8, and 2048 threads), on 256 CUs
+    const unsigned per_cu = (unsigned)std::min<size_t>(std::min<size_t>(8, 2048u / (unsigned)route.threads),
+                                                       std::max<size_t>(1, (160u * 1024u) / (lds + 1024u)));
     const size_t walk = rows == AnyRows::kListed ? (size_t)hr.n : (size_t)(c.row_hi - c.row_lo);   // rows, or list positions
-    const unsigned need = (unsigned)((walk + kAnyRows - 1) / kAnyRows);
-    const dim3 grid(std::min(need, 256u * per_cu)), block(kAnyBlock);
-#define GNNVC_ANY_LAUNCH(MODE_)                                                                                         \
-    hipLaunchKernelGGL((k_stage_any<MODE_>), grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, \
-                       c.out, sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0, sel)
+    const unsigned rows_wg = (unsigned)route.threads / 16u;
+    const unsigned need = (unsigned)((walk + rows_wg - 1) / rows_wg);
+    const dim3 grid(std::min(need, 256u * per_cu)), block((unsigned)route.threads);
+#define GNNVC_ANY_ARGS                                                                                                        \
+    grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, c.out, sp.sigmoid_last ? c.logits : nullptr, \
+        c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0, sel
+#define GNNVC_ANY_LAUNCH(MODE_)                                                             \
+    do {                                                                                    \
+        if (!route.big) hipLaunchKernelGGL((k_stage_any<MODE_>), GNNVC_ANY_ARGS);           \
+        else if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true>), GNNVC_ANY_ARGS); \
+        else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true>), GNNVC_ANY_ARGS);   \
+        else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true>), GNNVC_ANY_ARGS);           \
+    } while (0)
     switch (rows) {
     case AnyRows::kAll: GNNVC_ANY_LAUNCH(kAnyAll); break;
     case AnyRows::kLight: GNNVC_ANY_LAUNCH(kAnyLight); break;
     case AnyRows::kListed: GNNVC_ANY_LAUNCH(kAnyListed); break;
     }
 #undef GNNVC_ANY_LAUNCH
+#undef GNNVC_ANY_ARGS
     return hipGetLastError();
+}
+
+// the big instantiations take more than 64 KiB of dynamic LDS: told to the runtime once per device and instantiation
+// (allow_dynamic_lds of gnnvc_kernels.hip), by gnnvc_set_generic_big_stages — a refusal surfaces there, never inside a forward
+hipError_t allow_big_stages() {
+    static std::atomic<uint64_t> done[9];
+    hipError_t rc = hipSuccess;
+    int i = 0;
+#define GNNVC_ANY_ALLOW(MODE_, BLOCK_)                                                                                                  \
+    if (rc == hipSuccess)                                                                                                               \
+        rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_stage_any<MODE_, BLOCK_, true>), (int)kAnyBigLdsBytes, done[i]);        \
+    ++i
+#define GNNVC_ANY_ALLOW3(MODE_) GNNVC_ANY_ALLOW(MODE_, 256); GNNVC_ANY_ALLOW(MODE_, 512); GNNVC_ANY_ALLOW(MODE_, 1024)
+    GNNVC_ANY_ALLOW3(kAnyAll);
+    GNNVC_ANY_ALLOW3(kAnyLight);
+    GNNVC_ANY_ALLOW3(kAnyListed);
+#undef GNNVC_ANY_ALLOW3
+#undef GNNVC_ANY_ALLOW
+    return rc;
 }
 
 hipError_t launch_any_heavy_sums(const StageCall &c, const AnyHeavyRows &hr) {

@@ -22,7 +22,7 @@ _LIB = pathlib.Path(os.environ["GNNVC_LIBRARY"]).resolve() if os.environ.get("GN
 ABI_SYMBOLS = [
     "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_destroy",
     "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_set_generic_heavy_rows",
-    "gnnvc_set_generic_giant_rows",
+    "gnnvc_set_generic_giant_rows", "gnnvc_set_generic_big_stages",
     "gnnvc_num_layers", "gnnvc_is_fused",
     "gnnvc_in_width", "gnnvc_out_width", "gnnvc_upload_graph", "gnnvc_attach_graph_device", "gnnvc_attach_graph_slice",
     "gnnvc_graph_staging", "gnnvc_staged_columns_ready", "gnnvc_commit_staged_graph",
@@ -107,6 +107,7 @@ def load_library():
     L.gnnvc_get_info.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
     L.gnnvc_set_generic_heavy_rows.argtypes = [vp, u32]
     L.gnnvc_set_generic_giant_rows.argtypes = [vp, u32, C.c_int]
+    L.gnnvc_set_generic_big_stages.argtypes = [vp, u32]
     for name in ("gnnvc_num_layers", "gnnvc_is_fused", "gnnvc_in_width", "gnnvc_out_width",
                  "gnnvc_num_stages", "gnnvc_synchronize"):
         getattr(L, name).argtypes = [vp]
@@ -245,6 +246,14 @@ class Engine:
         get_info: "generic_giant_from", "generic_giant_segments", "generic_giant_rows", "generic_giant_entries",
         "generic_giant_last_rows", "generic_giant_last_segmented"."""
         self._check(self._L.gnnvc_set_generic_giant_rows(self._h, from_degree, segments))
+
+    def set_generic_big_stages(self, lds_bytes: int):
+        """Opt-in: generic stages with hidden widths up to 128 whose LDS layout at 256 threads fits `lds_bytes` (65536 .. 163840)
+        are fused too (gnnvc_set_generic_big_stages); 0 = off, the default.  Takes effect at once: fused, num_stages and
+        stage_widths follow.  Same bits for every value.  Raises GnnvcError -5 if the runtime refuses the kernels' raised LDS
+        limit, -1 for any other value.  get_info: "generic_big_lds", "generic_stage_lds_bytes_<s>",
+        "generic_stage_threads_<s>"."""
+        self._check(self._L.gnnvc_set_generic_big_stages(self._h, lds_bytes))
 
     def audit_report(self) -> dict:
         """The on-device audit's counters and its last failure (option "audit_period"), key -> value."""

@@ -304,7 +304,10 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         sums, with the same bits) and, among those, of their giant rows (gnnvc_set_generic_giant_rows below:
  *                         rows of 16 384 entries and more are summed by the exact parallel scan, with the same bits; keys
  *                         "generic_giant_from", "generic_giant_segments", "generic_giant_rows", "generic_giant_entries",
- *                         "generic_giant_last_rows", "generic_giant_last_segmented"), and "audit_period" audits nothing on
+ *                         "generic_giant_last_rows", "generic_giant_last_segmented").  The bounds above are the default ones:
+ *                         gnnvc_set_generic_big_stages (below) admits, on request, stages with hidden widths up to 128 and
+ *                         up to 160 KiB of LDS (keys "generic_big_lds", "generic_stage_lds_bytes_<s>",
+ *                         "generic_stage_threads_<s>").  "audit_period" audits nothing on
  *                         them, as on an unfused model: they are audited on demand, by gnnvc_forward_audited,
  *                         gnnvc_forward_audited_device and gnnvc_audit_stage_device (kernel k_audit_any: a wave per row, the
  *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
@@ -370,6 +373,31 @@ int gnnvc_set_generic_heavy_rows(gnnvc_engine *e, uint32_t from_degree);
  * the device and still counted), "generic_giant_last_segmented" (1: that call ran k_giant_segsum and k_giant_segmap).
  * "generic_heavy_rows", "generic_heavy_entries" and "generic_heavy_last_rows" count every listed row, the giant ones included. */
 int gnnvc_set_generic_giant_rows(gnnvc_engine *e, uint32_t from_degree, int segments);
+
+/* Big stages of generic models (opt-in).  By default a generic stage is fused only within 64 KiB of LDS and hidden widths of at
+ * most 64, and one stage outside these bounds sends the whole model back to one launch per layer.  gfx950 has 160 KiB of LDS per
+ * CU and one workgroup may take all of it; this call lets k_stage_any use it.
+ *   lds_bytes 0                    off (the default): the engine behaves exactly as if this call did not exist;
+ *   lds_bytes 65 536 .. 163 840    on, with that LDS limit in bytes.  A generic stage is then admitted if 1 <= f <= 32, it has 1 .. 6
+ *                                  dense layers, every hidden width is <= 128, its last width is <= 32, and its LDS layout AT 256
+ *                                  THREADS (transposed weights, biases, sixteen pairs of row vectors) is <= lds_bytes;
+ *   anything else                  GNNVC_ERR_INVALID.
+ * A stage within the default bounds launches exactly the kernels it always did, at 256 threads.  Every other admitted stage
+ * launches a "big" instantiation of the same kernel source — a hidden layer of more than 64 outputs is taken 64 outputs at a
+ * time, with the same bits — at 1024, 512 or 256 threads a workgroup (64 / 32 / 16 rows a pass): the largest size whose own
+ * layout fits lds_bytes.  Heavy and giant rows, gnnvc_stage_forward_device and the explicit audit calls (k_audit_any) serve a big
+ * stage as they serve any generic stage.  Results are bit-identical to the layer-by-layer forward for every value.
+ * The call takes effect at once, as option "generic_stages" does: the generic stage list is derived anew, and with it
+ * gnnvc_is_fused, gnnvc_num_stages, gnnvc_stage_widths and "generic_stage_layers_<s>"; an attached graph's heavy and giant rows
+ * are classed again by the next generic stage that runs.  A model that is still not admitted (a wider layer, a larger layout,
+ * f or a last width above 32) keeps running layer by layer.  The kernels' raised LDS limit is set here, once per device: if the
+ * runtime refuses it the call returns GNNVC_ERR_UNSUPPORTED and the engine stays as it was — never a forward.  A multi-device
+ * handle: GNNVC_ERR_UNSUPPORTED; a null engine: GNNVC_ERR_INVALID.
+ * gnnvc_get_info: "generic_big_lds" (the value as set, 0 when off), "generic_stage_lds_bytes_<s>" (the LDS layout of stage s at 256
+ * threads, in bytes) and "generic_stage_threads_<s>" (the workgroup size its launches use: 256, 512 or 1024 — 256 for every stage
+ * within the default bounds); both per-stage keys follow "generic_stage_layers_<s>": GNNVC_ERR_INVALID for a stage that does
+ * not exist or while the model is not generic. */
+int gnnvc_set_generic_big_stages(gnnvc_engine *e, uint32_t lds_bytes);
 
 /* Model introspection (what model::layers holds). */
 int gnnvc_num_layers(const gnnvc_engine *e);

@@ -91,14 +91,19 @@ def model_text(layers, depths, name: str) -> str:
     return "\n".join(out) + "\n"
 
 
-def layers_of(name: str, seed: int | None = None):
-    seed = SEEDS[name] if seed is None else seed
-    rng = np.random.default_rng([13, list(SPECS).index(name), seed])
+def draw(rng, shapes):
+    """The family's weight draw: per (k, n), W[k, n] then bias[n], uniform in [-s, s), s = min(0.5, 1.1 / sqrt(k)).
+    (tools/modelgen_big.py draws its members with this function too.)"""
     out = []
-    for (k, n) in linear_shapes(name):
+    for (k, n) in shapes:
         scale = min(0.5, 1.1 / np.sqrt(k))
         out.append((rng.uniform(-scale, scale, (k, n)).astype(np.float32), rng.uniform(-scale, scale, n).astype(np.float32)))
     return out
+
+
+def layers_of(name: str, seed: int | None = None):
+    seed = SEEDS[name] if seed is None else seed
+    return draw(np.random.default_rng([13, list(SPECS).index(name), seed]), linear_shapes(name))
 
 
 def build(name: str, seed: int | None = None) -> str:
