@@ -1,5 +1,5 @@
 """The graph and the crafted inputs of tests/test_gpu_giant_rows.py (tools/giant_rows_inputs.py, and crafted_input of
-tests/test_gpu_heavy_rows.py) are what that test needs — proven here on the CPU: the hubs' degrees, that the oracle adds a row in
+tests/generic_harness.py) are what that test needs — proven here on the CPU: the hubs' degrees, that the oracle adds a row in
 stored order, and that the input made for the integer route of the exact scan really walks it: many binades, exact ties, one
 large jump per hub, and a sum that tells the stored order from the reversed one."""
 import numpy as np
@@ -7,8 +7,7 @@ import pytest
 
 from oracle import oracle_py
 from tools import giant_rows_inputs as gi
-from tests.test_gpu_heavy_rows import crafted_input
-from tests.test_gpu_models import bits
+from tests.generic_harness import bits, crafted_input
 
 WIDTHS = (3, 32)       # stages 0 and 1 of the model in3_f32
 

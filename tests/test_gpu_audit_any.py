@@ -13,94 +13,23 @@ trained model, slices and the refusals; "audit_period" keeps auditing nothing on
 import numpy as np
 import pytest
 
-from oracle import oracle_py
 from tools import graphgen as gg
 from tools import modelgen_depths as md
 from tools import modelgen_shapes as ms
+from tests import generic_harness as gh
+from tests.generic_harness import bits, check_scores, graph_of
 from tests.test_expf_restatement import shim, _run   # noqa: F401  (the fixture that builds tests/support/libexpf_shim.so)
-from tests.test_gpu_models import bits, check_scores
-from tests.test_modelgen_depths import stage_outputs as stage_outputs_depths
-from tests.test_modelgen_shapes import stage_outputs as stage_outputs_shapes
 
 pytestmark = pytest.mark.gpu
 
 ERR_INVALID, ERR_UNSUPPORTED, ERR_AUDIT = -1, -5, -6
 
-# name -> (generator module, its stage_outputs)
-FAMILY = {name: (ms, stage_outputs_shapes) for name in ("narrow", "wide", "odd", "out4", "in3", "first_trained")}
-FAMILY.update({name: (md, stage_outputs_depths) for name in ("logit", "six_deep", "late_wide", "in3_f32", "too_big")})
+# name -> family
+FAMILY = {name: "shapes" for name in ("narrow", "wide", "odd", "out4", "in3", "first_trained")}
+FAMILY.update({name: "depths" for name in ("logit", "six_deep", "late_wide", "in3_f32", "too_big")})
 MODELS = [name for name in FAMILY if name != "too_big"]
-GRAPHS = {
-    "er3000": lambda: gg.erdos_renyi(3000, 15000, 15),
-    "sparse": lambda: gg.erdos_renyi(5000, 3000, 23),                     # many empty rows
-    "er1933": lambda: gg.erdos_renyi(1933, 7000, 61),                     # n = 30 * 64 + 13
-    "one": lambda: gg.from_edge_list(1, [], [57]),                        # n = 1
-    "hub8k": lambda: gg.hub_graph(8000, 24000, 2, 5000, seed=9),          # rows 0 and 1: about 5000 entries, 78 fetch batches
-}
+GRAPHS = ["er3000", "sparse", "er1933", "one", "hub8k"]   # (tests/generic_harness.py has what each is)
 FETCH_BATCH = 64   # column ids k_audit_any fetches at a time
-
-_cache = {}
-
-
-def mod_of(name):
-    return FAMILY[name][0]
-
-
-def text_of(name):
-    if ("text", name) not in _cache:
-        _cache["text", name] = mod_of(name).FAMILY[name]()
-    return _cache["text", name]
-
-
-def graph_of(gname):
-    if ("graph", gname) not in _cache:
-        _cache["graph", gname] = GRAPHS[gname]()
-    return _cache["graph", gname]
-
-
-def want_of(name, gname):
-    """[(stage input, stage output, pre-activation of the stage's last linear layer)] from the oracle's layers, computed once."""
-    if ("want", name, gname) not in _cache:
-        g = graph_of(gname)
-        om = oracle_py.OracleModel(text_of(name))
-        om.set_weight_scale(g.ws)
-        _cache["want", name, gname] = FAMILY[name][1](om, name, g)
-    return _cache["want", name, gname]
-
-
-def flat_logits(name, gname):
-    key = ("flat", name, gname)
-    if key not in _cache:
-        _cache[key] = np.ascontiguousarray(want_of(name, gname)[-1][2].reshape(-1))
-    return _cache[key]
-
-
-def open_engine(name, g, opts=()):
-    import gnn_mwvc_amd as G
-    e = G.Engine(text_of(name), device=0)
-    try:
-        for k, v in dict(opts).items():
-            e.set_option(k, v)
-        e.set_weight_scale(g.ws)
-        e.upload_graph(g)
-    except BaseException:
-        e.close()
-        raise
-    return e
-
-
-def stage_buffers(torch, name, gname, s, fill=float("nan")):
-    """(device input of stage s from the oracle with a zero pad row, output and logits buffers filled with `fill`, f, n_out)"""
-    g = graph_of(gname)
-    hin = want_of(name, gname)[s][0]
-    f, n_out = mod_of(name).stage_widths(name)[s]
-    dev = torch.device("cuda:0")
-    tin = torch.zeros((g.n + 1, f), dtype=torch.float32, device=dev)
-    tin[: g.n] = torch.from_numpy(np.ascontiguousarray(hin, dtype=np.float32).reshape(g.n, f)).to(dev)
-    out = torch.full((g.n + 1, n_out), fill, dtype=torch.float32, device=dev)
-    lgt = torch.full((g.n + 1, n_out), fill, dtype=torch.float32, device=dev)
-    torch.cuda.synchronize()
-    return tin, out, lgt, f, n_out
 
 
 def expect_audit_error(call):
@@ -128,12 +57,13 @@ CLEAN += [(name, gname) for name in ("narrow", "in3_f32") for gname in ("one", "
 
 @pytest.mark.parametrize("name,gname", CLEAN)
 def test_forward_audited_is_clean_and_changes_nothing(name, gname):
+    fam = FAMILY[name]
     g = graph_of(gname)
-    x = mod_of(name).model_input(name, g)
-    e = open_engine(name, g)
+    x = gh.FAMILIES[fam].model_input(name, g)
+    e = gh.open_engine(fam, name, g)
     try:
         ns = e.num_stages
-        assert e.fused and ns == len(want_of(name, gname))
+        assert e.fused and ns == len(gh.want_of(fam, name, gname))
         sc0, lg0 = e.forward(x)
         assert e.get_info("audit_runs") == 0
         sc1, lg1 = e.forward_audited(x)
@@ -141,7 +71,7 @@ def test_forward_audited_is_clean_and_changes_nothing(name, gname):
         print(name, gname, rep)
         assert rep["audit_runs"] == ns and rep["audit_failures"] == 0 and rep["audit_repairs"] == 0 and rep["audit_nan_pairs"] == 0, rep
         assert np.array_equal(bits(sc1), bits(sc0)) and np.array_equal(bits(lg1), bits(lg0)), (name, gname)
-        assert np.array_equal(bits(lg1), bits(want_of(name, gname)[-1][2])), (name, gname)
+        assert np.array_equal(bits(lg1), bits(gh.want_of(fam, name, gname)[-1][2])), (name, gname)
         assert e.get_info("generic_stages_active") == 1
         e.forward_audited(x, want_logits=False)   # (without logits: the scores alone are checked)
         assert e.get_info("audit_runs") == 2 * ns and e.get_info("audit_failures") == 0
@@ -154,7 +84,7 @@ def test_forward_audited_device_is_clean():
     name, gname = "odd", "er1933"
     g = graph_of(gname)
     dev = torch.device("cuda:0")
-    e = open_engine(name, g)
+    e = gh.open_engine("shapes", name, g)
     try:
         x = torch.from_numpy(ms.model_input(name, g)).to(dev)
         sc = torch.zeros(g.n, dtype=torch.float32, device=dev)
@@ -162,7 +92,7 @@ def test_forward_audited_device_is_clean():
         torch.cuda.synchronize()
         e.forward_audited_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())   # (synchronises the stream itself)
         assert e.get_info("audit_runs") == e.num_stages and e.get_info("audit_failures") == 0
-        assert np.array_equal(bits(lg.cpu().numpy()), bits(flat_logits(name, gname)))
+        assert np.array_equal(bits(lg.cpu().numpy()), bits(gh.flat_logits("shapes", name, gname)))
     finally:
         e.close()
 
@@ -176,18 +106,19 @@ WRITES += [(name, gname) for name in ("narrow", "in3_f32") for gname in ("er3000
 @pytest.mark.parametrize("name,gname", WRITES)
 def test_repairing_zeros_writes_the_oracles_stage(shim, name, gname):
     import torch
+    fam = FAMILY[name]
     g = graph_of(gname)
     n = g.n
-    want = want_of(name, gname)
-    restated = _run(shim.sigmoid_restated, flat_logits(name, gname)).reshape(n, -1)   # the device's scores, bit for bit
-    e = open_engine(name, g, {"audit_repair": 1})
+    want = gh.want_of(fam, name, gname)
+    restated = _run(shim.sigmoid_restated, gh.flat_logits(fam, name, gname)).reshape(n, -1)   # the device's scores, bit for bit
+    e = gh.open_engine(fam, name, g, {"audit_repair": 1})
     try:
         cuts = sorted({0, n // 5, n // 3, (2 * n) // 3, n})
         ranges = list(zip(cuts[:-1], cuts[1:]))
         order = ranges[0::2] + ranges[1::2]   # with gaps first, then the gaps
         for s, (hin, hout, pre) in enumerate(want):
             last = s + 1 == len(want)
-            tin, out, lgt, f, n_out = stage_buffers(torch, name, gname, s)
+            tin, out, lgt, f, n_out = gh.stage_buffers(fam, name, gname, s)
             w_out = restated if last else np.ascontiguousarray(hout, dtype=np.float32).reshape(n, n_out)
             w_pre = np.ascontiguousarray(pre, dtype=np.float32).reshape(n, n_out)
             done = np.zeros(n + 1, dtype=bool)
@@ -215,7 +146,7 @@ def test_repairing_zeros_writes_the_oracles_stage(shim, name, gname):
                 assert np.isnan(gotl[~done]).all() if last else np.isnan(gotl).all(), (name, gname, s, "logits rows")
             assert done[:n].all() and not done[n]
             if last:   # the suite's score rule, over the whole stage
-                check_scores(shim, got[:n].reshape(-1), gotl[:n].reshape(-1), flat_logits(name, gname), (name, gname))
+                check_scores(shim, got[:n].reshape(-1), gotl[:n].reshape(-1), gh.flat_logits(fam, name, gname), (name, gname))
     finally:
         e.close()
 
@@ -242,10 +173,10 @@ def test_one_flipped_bit_is_found_and_named(where):
     g = graph_of(gname)
     n = g.n
     s, lo, hi, r, c, in_logits = _positions(n)[where]
-    last = s + 1 == len(want_of(name, gname))
-    e = open_engine(name, g)
+    last = s + 1 == len(gh.want_of("shapes", name, gname))
+    e = gh.open_engine("shapes", name, g)
     try:
-        tin, out, lgt, f, n_out = stage_buffers(torch, name, gname, s)
+        tin, out, lgt, f, n_out = gh.stage_buffers("shapes", name, gname, s)
         assert c < n_out and (last or not in_logits)
         e.stage_forward_device(s, 0, n, tin.data_ptr(), out.data_ptr(), lgt.data_ptr() if last else 0)
         e.synchronize()
@@ -279,11 +210,12 @@ def test_one_flipped_bit_is_found_and_named(where):
 
 @pytest.mark.parametrize("name", ["narrow", "six_deep"])
 def test_flip_inside_a_forward_is_found_and_repaired(name):
+    fam = FAMILY[name]
     gname = "er3000"
     g = graph_of(gname)
-    x = mod_of(name).model_input(name, g)
-    wl = want_of(name, gname)[-1][2]
-    e = open_engine(name, g)
+    x = gh.FAMILIES[fam].model_input(name, g)
+    wl = gh.want_of(fam, name, gname)[-1][2]
+    e = gh.open_engine(fam, name, g)
     try:
         ns = e.num_stages
         for s in range(ns):
@@ -322,7 +254,7 @@ def test_nan_input_is_no_alarm():
     g = graph_of(gname)
     x = ms.model_input(name, g).copy()
     x.reshape(-1)[g.n // 2] = np.nan
-    e = open_engine(name, g)
+    e = gh.open_engine("shapes", name, g)
     try:
         sc, lg = e.forward_audited(x)
         rep = e.audit_report()
@@ -365,7 +297,7 @@ def test_refusals_and_empty_calls(model_text):
     t = torch.zeros((g.n + 1, 32), dtype=torch.float32, device="cuda:0")
     torch.cuda.synchronize()
     # a model that runs layer by layer has no stage to audit
-    e = open_engine("too_big", g)
+    e = gh.open_engine("depths", "too_big", g)
     try:
         assert not e.fused
         with pytest.raises(G.GnnvcError) as err:
@@ -386,7 +318,7 @@ def test_refusals_and_empty_calls(model_text):
         assert err.value.code == ERR_UNSUPPORTED
     finally:
         e.close()
-    e = open_engine("narrow", g)
+    e = gh.open_engine("shapes", "narrow", g)
     try:
         for stage in (e.num_stages, -1):
             with pytest.raises(G.GnnvcError) as err:
@@ -418,20 +350,20 @@ def test_a_slice_checks_rows_of_its_slice():
     t = lambda v: torch.from_numpy(v.astype(np.int64)).to(torch.int32).to(dev)
     lo, hi = g.n // 2, g.n
     sl = D.slice_csr(g.n, t(g.rowptr), t(g.col), t(g.w), t(g.nw), lo, hi)
-    e = G.Engine(text_of(name), device=0)
+    e = G.Engine(gh.text_of("shapes", name), device=0)
     try:
         e.set_weight_scale(g.ws)
         torch.cuda.synchronize()
         e.attach_graph_slice(g.n, lo, hi, sl.nnz, sl.rowptr.data_ptr(), sl.col.data_ptr(), sl.w.data_ptr(), sl.nw.data_ptr(), keepalive=sl)
         s = 1
-        tin, out, lgt, f, n_out = stage_buffers(torch, name, gname, s)
+        tin, out, lgt, f, n_out = gh.stage_buffers("shapes", name, gname, s)
         e.stage_forward_device(s, lo, hi, tin.data_ptr(), out.data_ptr(), 0)
         e.synchronize()
         a, b = lo + 37, hi - 5
         e.audit_stage_device(s, a, b, tin.data_ptr(), out.data_ptr(), 0)
         e.audit_stage_device(s, lo, hi, tin.data_ptr(), out.data_ptr(), 0)
         assert e.get_info("audit_runs") == 2 and e.get_info("audit_failures") == 0
-        assert np.array_equal(bits(out[lo:hi].cpu().numpy()), bits(want_of(name, gname)[s][1][lo:hi]))
+        assert np.array_equal(bits(out[lo:hi].cpu().numpy()), bits(gh.want_of("shapes", name, gname)[s][1][lo:hi]))
         out.view(torch.int32)[hi - 1, n_out - 1] ^= 1
         torch.cuda.synchronize()
         e.audit_stage_device(s, a, b, tin.data_ptr(), out.data_ptr(), 0)       # (the flipped row is outside this range)
@@ -451,7 +383,7 @@ def test_the_period_still_audits_nothing_on_a_generic_model():
     name, gname = "narrow", "er3000"
     g = graph_of(gname)
     x = ms.model_input(name, g)
-    e = open_engine(name, g, {"audit_period": 1})
+    e = gh.open_engine("shapes", name, g, {"audit_period": 1})
     try:
         _, lg0 = e.forward(x)
         assert e.get_info("audit_runs") == 0

@@ -7,63 +7,24 @@ Bars, as in tests/test_gpu_depths.py and no wider: logits and every stage's outp
 call's range and the row behind the end untouched.  The graphs are that file's.
 
 The speed guard at the end is that file's too: big stages on against off (layer by layer) on one engine, ER 1 M / 10 M."""
-import time
+import functools
 
 import numpy as np
 import pytest
 
-from oracle import oracle_py
 from tools import modelgen_big as mb
+from tests import generic_harness as gh
+from tests.generic_harness import LDS_BYTES, bits, check_scores, graph_of
 from tests.test_expf_restatement import shim, _run   # noqa: F401  (the fixture that builds tests/support/libexpf_shim.so)
-from tests.test_gpu_depths import GRAPHS, graph_of
-from tests.test_gpu_models import bits, check_scores, ulp
-from tests.test_modelgen_big import LDS_BYTES, stage_outputs
 
 pytestmark = pytest.mark.gpu
 
+# the accessors of tests/generic_harness.py, for the family of this file
+text_of, want_of, flat_logits, open_engine = (functools.partial(f, "big")
+                                              for f in (gh.text_of, gh.want_of, gh.flat_logits, gh.open_engine))
+GRAPHS = ["er3000", "sparse", "er1933", "one", "hub6k"]   # tests/test_gpu_depths.py's (tests/generic_harness.py has what each is)
 ERR_INVALID, ERR_UNSUPPORTED = -1, -5
 FULL = 163840
-
-_cache = {}
-
-
-def text_of(name):
-    if ("text", name) not in _cache:
-        _cache["text", name] = mb.FAMILY[name]()
-    return _cache["text", name]
-
-
-def want_of(name, gname):
-    """[(stage input, stage output, pre-activation of the stage's last linear layer)] from the oracle's layers, computed once."""
-    if ("want", name, gname) not in _cache:
-        g = graph_of(gname)
-        om = oracle_py.OracleModel(text_of(name))
-        om.set_weight_scale(g.ws)
-        _cache["want", name, gname] = stage_outputs(om, name, g)
-    return _cache["want", name, gname]
-
-
-def flat_logits(name, gname):
-    key = ("flat", name, gname)
-    if key not in _cache:
-        _cache[key] = np.ascontiguousarray(want_of(name, gname)[-1][2].reshape(-1))
-    return _cache[key]
-
-
-def open_engine(name, g, big=0, opts=()):
-    import gnn_mwvc_amd as G
-    e = G.Engine(text_of(name), device=0)
-    try:
-        for k, v in dict(opts).items():
-            e.set_option(k, v)
-        if big is not None:
-            e.set_generic_big_stages(big)
-        e.set_weight_scale(g.ws)
-        e.upload_graph(g)
-    except BaseException:
-        e.close()
-        raise
-    return e
 
 
 def assert_layer_by_layer(e):
@@ -155,37 +116,11 @@ def test_forward_and_stage_entry(shim, name, gname):
             assert e.get_info("generic_stages_active") == 1
         # the stage entry over split row ranges, each stage fed the oracle's input: first two ranges with a gap between them
         # (the gap, the rows behind and the row behind the end stay as they were), then the gap
-        dev = torch.device("cuda:0")
         n = g.n
-        cuts = sorted({0, n // 5, n // 3, (2 * n) // 3, n})
-        ranges = list(zip(cuts[:-1], cuts[1:]))
-        first, gap = (ranges[0::2], ranges[1::2]) if len(ranges) > 1 else (ranges, [])
+        first, gap = gh.split_ranges(n)
         assert len(want) == e.num_stages
         for s, (hin, hout, pre) in enumerate(want):
-            f, n_out = mb.stage_widths(name)[s]
-            last = s + 1 == len(want)
-            tin = torch.zeros((n + 1, f), dtype=torch.float32, device=dev)
-            tin[:n] = torch.from_numpy(np.ascontiguousarray(hin)).to(dev)
-            out = torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev)
-            lgt = torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev)
-            torch.cuda.synchronize()
-            for part, todo in enumerate((first, gap)):
-                for lo, hi in todo:
-                    e.stage_forward_device(s, lo, hi, tin.data_ptr(), out.data_ptr(), lgt.data_ptr() if last else 0)
-                e.synchronize()
-                got, gotl = out.cpu().numpy(), lgt.cpu().numpy()
-                done = np.zeros(n + 1, dtype=bool)
-                for lo, hi in (first if part == 0 else first + gap):
-                    done[lo:hi] = True
-                assert np.isnan(got[~done]).all(), (name, gname, s, part, "rows outside the ranges were written")
-                assert np.isnan(gotl[~done]).all() if last else np.isnan(gotl).all(), (name, gname, s, part, "logits rows")
-                w_out = hout[done[:n]]
-                if last:
-                    assert np.array_equal(bits(gotl[:n][done[:n]]), bits(pre[done[:n]])), (name, gname, s, part, "stage logits")
-                    assert ulp(got[:n][done[:n]], w_out).max(initial=0) <= 1, (name, gname, s, part, "stage scores")
-                else:
-                    bad = np.argwhere(bits(got[:n][done[:n]]) != bits(w_out))
-                    assert bad.size == 0, (name, gname, s, part, f"{len(bad)} values differ, first (row, column)", bad[:6].tolist())
+            done = gh.run_stage_ranges(e, "big", name, g, s, hin, [first, gap], hout, pre, (name, gname))
             assert done[:n].all() and not done[n]
     finally:
         e.close()
@@ -293,7 +228,6 @@ def test_repairing_zeros_writes_the_oracles_stage(shim, name):
     n = g.n
     want = want_of(name, gname)
     restated = _run(shim.sigmoid_restated, flat_logits(name, gname)).reshape(n, -1)   # the device's scores, bit for bit
-    dev = torch.device("cuda:0")
     e = open_engine(name, g, big=FULL, opts={"audit_repair": 1})
     try:
         cuts = sorted({0, n // 5, n // 3, (2 * n) // 3, n})
@@ -301,11 +235,7 @@ def test_repairing_zeros_writes_the_oracles_stage(shim, name):
         order = ranges[0::2] + ranges[1::2]   # with gaps first, then the gaps
         for s, (hin, hout, pre) in enumerate(want):
             last = s + 1 == len(want)
-            f, n_out = mb.stage_widths(name)[s]
-            tin = torch.zeros((n + 1, f), dtype=torch.float32, device=dev)
-            tin[:n] = torch.from_numpy(np.ascontiguousarray(hin, dtype=np.float32).reshape(n, f)).to(dev)
-            out = torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev)
-            lgt = torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev)
+            tin, out, lgt, f, n_out = gh.stage_buffers("big", name, gname, s)
             w_out = restated if last else np.ascontiguousarray(hout, dtype=np.float32).reshape(n, n_out)
             w_pre = np.ascontiguousarray(pre, dtype=np.float32).reshape(n, n_out)
             done = np.zeros(n + 1, dtype=bool)
@@ -395,21 +325,6 @@ def test_a_multi_device_handle_refuses_the_call(model_text):
 GUARDED = ["too_big", "h128"]   # what the measurement left admitted (profiles/generic_stages/README.md, "Big stages")
 
 
-def _best_ms(torch, e, x, sc, lg):
-    for _ in range(2):
-        e.forward_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())
-    e.synchronize()
-    best = 1e9
-    for _ in range(3):                       # the best of three batches of five, as tests/test_gpu_depths.py
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(5):
-            e.forward_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())
-        e.synchronize()
-        best = min(best, (time.perf_counter() - t) * 200.0)
-    return best, lg.clone()
-
-
 def test_big_stages_are_not_slower_than_layer_by_layer():
     import torch
     import gnn_mwvc_amd as G
@@ -425,10 +340,10 @@ def test_big_stages_are_not_slower_than_layer_by_layer():
             sc = torch.zeros(g.n, device=dev)
             lg = torch.zeros(g.n, device=dev)
             torch.cuda.synchronize()
-            ms_off, lg0 = _best_ms(torch, e, x, sc, lg)
+            ms_off, lg0 = gh.steady_ms(e, x, sc, lg)
             assert e.get_info("generic_stages_active") == 0
             e.set_generic_big_stages(FULL)
-            ms_on, lg1 = _best_ms(torch, e, x, sc, lg)
+            ms_on, lg1 = gh.steady_ms(e, x, sc, lg)
             assert e.get_info("generic_stages_active") == 1
             print(f"er1m {name}: big stages on {ms_on:.3f} ms, off {ms_off:.3f} ms, {ms_off / ms_on:.2f}x")
             assert torch.equal(lg0.view(torch.int32), lg1.view(torch.int32)), name

@@ -17,24 +17,19 @@ import numpy as np
 import pytest
 
 from tools import giant_rows_inputs as gi
-from tools import graphgen as gg
 from tools import modelgen_depths as md
-from tests import test_gpu_heavy_rows as hv
+from tests import generic_harness as gh
+from tests.generic_harness import bits, check_scores, crafted_input, degrees, graph_of, ulp
 from tests.test_expf_restatement import shim, _run   # noqa: F401  (the fixture that builds tests/support/libexpf_shim.so)
-from tests.test_gpu_heavy_rows import MODELS, crafted_input, degrees, gen_of, oracle_stage, run_stage_ranges, text_of
-from tests.test_gpu_models import bits, check_scores, ulp
 
 pytestmark = pytest.mark.gpu
 
+# model -> family (the models of tests/test_gpu_heavy_rows.py)
+MODELS = {"narrow": "shapes", "odd": "shapes", "wide": "shapes", "logit": "depths", "two_deep": "depths", "in3_f32": "depths"}
 HEAVY_FROM = 512
 GIANT_DEFAULT = 16384
 GIANT_THRESHOLDS = [0, 1024, 1025, 4097, 16384]
 SEGMENT_ADDENDS = 4096       # one segment of the scan: a stream is spread over several waves only when it is longer
-
-# the graphs of this file, under names of their own in the helpers' cache of graphs and oracle results
-hv.GRAPHS.setdefault("giant_hubs", gi.hub_graph)
-hv.GRAPHS.setdefault("giant_er600", lambda: gg.erdos_renyi(600, 1800, 31))
-graph_of, want_of, flat_logits = hv.graph_of, hv.want_of, hv.flat_logits
 
 
 def giant_counts(deg, heavy, thr):
@@ -48,13 +43,6 @@ def giant_counts(deg, heavy, thr):
 def segmented(deg, heavy, thr, seg):
     rows, _ = giant_counts(deg, heavy, thr)
     return int(seg == 1 and rows > 0 and int(deg.max()) > SEGMENT_ADDENDS)
-
-
-def open_engine(name, g, giant=None, heavy=None, opts=()):
-    e = hv.open_engine(name, g, heavy_from=heavy, opts=opts)
-    if giant is not None:
-        e.set_generic_giant_rows(*giant)
-    return e
 
 
 def check_info(e, deg, heavy, thr, seg, label):
@@ -73,7 +61,7 @@ def test_the_graph_is_what_the_name_says_and_the_defaults_are_the_trained_paths(
     assert deg[:8].tolist() == gi.HUB_DEGREES and deg[8:].max() < 64
     assert [giant_counts(deg, HEAVY_FROM, t)[0] for t in GIANT_THRESHOLDS] == [0, 6, 5, 2, 0]
     assert int((deg >= HEAVY_FROM).sum()) == 7
-    e = G.Engine(text_of("narrow"), device=0)
+    e = G.Engine(gh.text_of("shapes", "narrow"), device=0)
     try:
         assert e.get_info("generic_giant_from") == GIANT_DEFAULT and e.get_info("generic_giant_segments") == -1
         for key in ("generic_giant_rows", "generic_giant_entries", "generic_giant_last_rows", "generic_giant_last_segmented"):
@@ -88,11 +76,12 @@ def test_the_graph_is_what_the_name_says_and_the_defaults_are_the_trained_paths(
 
 @pytest.mark.parametrize("name", list(MODELS))
 def test_every_setting_gives_the_oracles_bits(shim, name):
+    fam = MODELS[name]
     g = graph_of("giant_hubs")
     deg = degrees(g)
-    wl = want_of(name, "giant_hubs")[-1][2]
-    x = gen_of(name).model_input(name, g)
-    e = open_engine(name, g, heavy=HEAVY_FROM)
+    wl = gh.want_of(fam, name, "giant_hubs")[-1][2]
+    x = gh.FAMILIES[fam].model_input(name, g)
+    e = gh.open_engine(fam, name, g, heavy=HEAVY_FROM)
     try:
         first = None
         for thr in GIANT_THRESHOLDS:
@@ -102,7 +91,7 @@ def test_every_setting_gives_the_oracles_bits(shim, name):
                 sc, lg = e.forward(x)
                 mism = int((bits(lg) != bits(wl)).sum())
                 assert mism == 0, (label, f"{mism}/{lg.size} logits differ", np.argwhere(bits(lg) != bits(wl))[:6].tolist())
-                check_scores(shim, sc.reshape(-1), lg.reshape(-1), flat_logits(name, "giant_hubs"), label)
+                check_scores(shim, sc.reshape(-1), lg.reshape(-1), gh.flat_logits(fam, name, "giant_hubs"), label)
                 if first is None:
                     first = (sc.copy(), lg.copy())
                 assert np.array_equal(bits(sc), bits(first[0])) and np.array_equal(bits(lg), bits(first[1])), label
@@ -114,18 +103,19 @@ def test_every_setting_gives_the_oracles_bits(shim, name):
 
 @pytest.mark.parametrize("name", list(MODELS))
 def test_thresholds_1_send_every_non_empty_row_the_giant_way(shim, name):
+    fam = MODELS[name]
     g = graph_of("giant_er600")
     deg = degrees(g)
-    wl = want_of(name, "giant_er600")[-1][2]
-    e = open_engine(name, g, giant=(1, -1), heavy=1)
+    wl = gh.want_of(fam, name, "giant_er600")[-1][2]
+    e = gh.open_engine(fam, name, g, giant=(1, -1), heavy=1)
     try:
-        sc, lg = e.forward(gen_of(name).model_input(name, g))
+        sc, lg = e.forward(gh.FAMILIES[fam].model_input(name, g))
         assert e.get_info("generic_giant_last_rows") == int((deg > 0).sum()) <= g.n
         assert e.get_info("generic_giant_rows") == int((deg > 0).sum())
         assert e.get_info("generic_giant_entries") == g.nnz
         assert e.get_info("generic_giant_last_segmented") == 0
         assert np.array_equal(bits(lg), bits(wl)), name
-        check_scores(shim, sc.reshape(-1), lg.reshape(-1), flat_logits(name, "giant_er600"), name)
+        check_scores(shim, sc.reshape(-1), lg.reshape(-1), gh.flat_logits(fam, name, "giant_er600"), name)
     finally:
         e.close()
 
@@ -141,7 +131,7 @@ def crafted(which, stage):
         g = graph_of("giant_hubs")
         f, _ = md.stage_widths("in3_f32")[stage]
         hin = crafted_input(g.n, f, 300 + f) if which == "a" else gi.scan_input(g, f, 200 + f)   # (as tests/test_giant_rows_inputs.py)
-        out, pre = oracle_stage("in3_f32", g, stage, hin)
+        out, pre = gh.oracle_stage("depths", "in3_f32", g, stage, hin)
         _stage_want[which, stage] = (hin, out, pre)
     return _stage_want[which, stage]
 
@@ -155,9 +145,9 @@ def test_the_sums_are_added_in_stored_order(stage, seg, which):
     deg = degrees(g)
     assert md.stage_widths(name)[stage][0] == (3, 32)[stage]
     hin, want_out, want_pre = crafted(which, stage)
-    e = open_engine(name, g, giant=(1024, seg), heavy=HEAVY_FROM)
+    e = gh.open_engine("depths", name, g, giant=(1024, seg), heavy=HEAVY_FROM)
     try:
-        run_stage_ranges(e, name, g, stage, hin, [[(0, g.n)]], want_out, want_pre, (name, which, seg))
+        gh.run_stage_ranges(e, "depths", name, g, stage, hin, [[(0, g.n)]], want_out, want_pre, (name, which, seg))
         check_info(e, deg, HEAVY_FROM, 1024, seg, (name, which, stage, seg))
         assert e.get_info("generic_giant_last_rows") == 6
     finally:
@@ -168,17 +158,18 @@ def test_the_sums_are_added_in_stored_order(stage, seg, which):
 
 @pytest.mark.parametrize("name", list(MODELS))
 def test_stage_entry_over_split_ranges(name):
+    fam = MODELS[name]
     g = graph_of("giant_hubs")
     n = g.n
-    want = want_of(name, "giant_hubs")
+    want = gh.want_of(fam, name, "giant_hubs")
     # hubs 0 .. 2 and 5 .. 7 in the first two ranges, hubs 3 and 4 in the gap between them: giant rows on both sides of every cut
     first, gap = [(0, 3), (5, n // 2)], [(3, 5), (n // 2, n)]
     for seg in (0, 1):
-        e = open_engine(name, g, giant=(1024, seg), heavy=HEAVY_FROM)
+        e = gh.open_engine(fam, name, g, giant=(1024, seg), heavy=HEAVY_FROM)
         try:
             assert len(want) == e.num_stages
             for s, (hin, hout, pre) in enumerate(want):
-                done = run_stage_ranges(e, name, g, s, hin, [first, gap], hout, pre, (name, "giant_hubs", seg))
+                done = gh.run_stage_ranges(e, fam, name, g, s, hin, [first, gap], hout, pre, (name, "giant_hubs", seg))
                 assert done[:n].all() and not done[n]
                 assert e.get_info("generic_giant_last_rows") == 6 and e.get_info("generic_heavy_last_rows") == 7
                 assert e.get_info("generic_giant_last_segmented") == seg
@@ -193,19 +184,20 @@ def test_two_slices_compute_the_whole_graph(name):
     import torch
     import gnn_mwvc_amd as G
     from gnn_mwvc_amd import distributed as D
+    fam = MODELS[name]
     g = graph_of("giant_hubs")
     n = g.n
     deg = degrees(g)
-    want = want_of(name, "giant_hubs")
+    want = gh.want_of(fam, name, "giant_hubs")
     dev = torch.device("cuda:0")
     t = lambda a: torch.from_numpy(a.astype(np.int64)).to(torch.int32).to(dev)
     rp, col, w, nw = t(g.rowptr), t(g.col), t(g.w), t(g.nw)
-    widths = gen_of(name).stage_widths(name)
+    widths = gh.FAMILIES[fam].stage_widths(name)
     outs = [torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev) for _, n_out in widths]
     lgt = torch.full((n + 1, widths[-1][1]), float("nan"), dtype=torch.float32, device=dev)
     for lo, hi in ((0, 4), (4, n)):   # hubs 0 .. 3 in one slice, 4 .. 7 in the other
         sl = D.slice_csr(n, rp, col, w, nw, lo, hi)
-        e = G.Engine(text_of(name), device=0)
+        e = G.Engine(gh.text_of(fam, name), device=0)
         try:
             e.set_weight_scale(g.ws)
             e.set_generic_giant_rows(1024, 1)
@@ -241,14 +233,15 @@ def test_two_slices_compute_the_whole_graph(name):
 
 @pytest.mark.parametrize("name", ["odd", "in3_f32"])
 def test_the_explicit_audit_is_clean(name):
+    fam = MODELS[name]
     g = graph_of("giant_hubs")
-    wl = want_of(name, "giant_hubs")[-1][2]
-    e = open_engine(name, g, heavy=HEAVY_FROM)
+    wl = gh.want_of(fam, name, "giant_hubs")[-1][2]
+    e = gh.open_engine(fam, name, g, heavy=HEAVY_FROM)
     try:
         runs = 0
         for seg in (0, 1):
             e.set_generic_giant_rows(1024, seg)
-            _, lg = e.forward_audited(gen_of(name).model_input(name, g))   # (raises on a mismatch)
+            _, lg = e.forward_audited(gh.FAMILIES[fam].model_input(name, g))   # (raises on a mismatch)
             runs += e.num_stages
             assert e.get_info("generic_giant_last_rows") == 6 and e.get_info("generic_giant_last_segmented") == seg
             assert e.get_info("audit_runs") == runs and e.get_info("audit_failures") == 0
@@ -279,7 +272,7 @@ def test_a_graph_attached_before_the_option_is_classed_by_the_first_generic_stag
     name = "two_deep"
     g = graph_of("giant_hubs")
     x = md.model_input(name, g)
-    e = open_engine(name, g, giant=(1024, 1), opts={"generic_stages": 0})
+    e = gh.open_engine("depths", name, g, giant=(1024, 1), opts={"generic_stages": 0})
     try:
         assert not e.fused
         sc0, lg0 = e.forward(x)
@@ -291,7 +284,7 @@ def test_a_graph_attached_before_the_option_is_classed_by_the_first_generic_stag
         assert e.get_info("generic_giant_last_rows") == 6 and e.get_info("generic_giant_rows") == 6
         assert e.get_info("generic_giant_last_segmented") == 1
         assert np.array_equal(bits(lg0), bits(lg1)) and np.array_equal(bits(sc0), bits(sc1))
-        assert np.array_equal(bits(lg1), bits(want_of(name, "giant_hubs")[-1][2]))
+        assert np.array_equal(bits(lg1), bits(gh.want_of("depths", name, "giant_hubs")[-1][2]))
         # the next graphs: their own counts
         for gname, rows, heavy in (("er3000", 0, 0), ("giant_hubs", 6, 7)):
             g2 = graph_of(gname)
@@ -301,7 +294,7 @@ def test_a_graph_attached_before_the_option_is_classed_by_the_first_generic_stag
             _, lg = e.forward(md.model_input(name, g2))
             assert e.get_info("generic_giant_last_rows") == rows and e.get_info("generic_heavy_last_rows") == heavy, gname
             assert e.get_info("generic_giant_entries") == giant_counts(degrees(g2), HEAVY_FROM, 1024)[1], gname
-            assert np.array_equal(bits(lg), bits(want_of(name, gname)[-1][2])), gname
+            assert np.array_equal(bits(lg), bits(gh.want_of("depths", name, gname)[-1][2])), gname
     finally:
         e.close()
 
@@ -317,7 +310,7 @@ def test_the_giant_route_is_not_slower_than_without_it_on_four_giant_hubs():
     x1 = g.x().contiguous()
     inputs = {"narrow": x1, "in3_f32": torch.stack([x1, x1 * 0.37, 1.0 - x1], dim=1).contiguous()}
     for name, x in inputs.items():
-        e = G.Engine(text_of(name), device=0)
+        e = G.Engine(gh.text_of(MODELS[name], name), device=0)
         try:
             e.set_weight_scale(g.ws)
             e.attach_graph_device(g.n, g.nnz, g.rowptr.data_ptr(), g.col.data_ptr(), g.w.data_ptr(), g.nw.data_ptr(), keepalive=g)
@@ -325,10 +318,10 @@ def test_the_giant_route_is_not_slower_than_without_it_on_four_giant_hubs():
             lg = torch.zeros(g.n, device=dev)
             torch.cuda.synchronize()
             assert e.get_info("generic_giant_from") == GIANT_DEFAULT and e.get_info("generic_giant_segments") == -1
-            ms_default, lg_on = hv._steady_ms(torch, e, x, sc, lg)   # best of three batches of five
+            ms_default, lg_on = gh.steady_ms(e, x, sc, lg)   # best of three batches of five
             rows = e.get_info("generic_giant_last_rows")
             e.set_generic_giant_rows(0, -1)
-            ms_off, lg_off = hv._steady_ms(torch, e, x, sc, lg)
+            ms_off, lg_off = gh.steady_ms(e, x, sc, lg)
             assert e.get_info("generic_giant_last_rows") == 0 and e.get_info("generic_heavy_last_rows") >= 4
             print(f"power-law 262144 / four hubs of 65536, {name}: giant rows from 16384 ({rows} rows) {ms_default:.3f} ms, "
                   f"none {ms_off:.3f} ms, {ms_off / ms_default:.2f}x")

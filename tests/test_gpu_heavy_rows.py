@@ -7,165 +7,28 @@ ranges and the pad row untouched — for EVERY threshold, 0 (no heavy path) incl
 each other.  Models: narrow, odd, wide (tools/modelgen_shapes.py) and logit, two_deep, in3_f32 (tools/modelgen_depths.py):
 stage input widths 1, 3, 4, 5, 9, 12 and 32, one to four dense layers a stage.
 
-The hub graph is built here: 6 000 vertices, hubs 0 .. 8 of exactly 511, 512, 513, 767, 768, 769, 1 025, 3 000 and 0 entries
-(around the default threshold, around the chunk sizes of the sums kernel, several chunks, and an empty row), neighbours and a
-sparse background drawn among the other vertices only.
+The hub graph ("hubs", heavy_hub_graph of tests/generic_harness.py): 6 000 vertices, hubs 0 .. 8 of exactly 511, 512, 513, 767,
+768, 769, 1 025, 3 000 and 0 entries (around the default threshold, around the chunk sizes of the sums kernel, several chunks,
+and an empty row), neighbours and a sparse background drawn among the other vertices only.
 
 The last test is a speed guard: on a power-law graph with four hubs of 65 536 entries the default threshold must not be slower
 than threshold 0, which is the code as it was before the heavy path existed."""
-import time
-
 import numpy as np
 import pytest
 
 from oracle import oracle_py
-from tools import graphgen as gg
 from tools import modelgen_depths as md
-from tools import modelgen_shapes as ms
+from tests import generic_harness as gh
+from tests.generic_harness import HUB_DEGREES, HUB_N, bits, check_scores, crafted_input, degrees, graph_of, ulp
 from tests.test_expf_restatement import shim, _run   # noqa: F401  (the fixture that builds tests/support/libexpf_shim.so)
-from tests.test_gpu_models import bits, check_scores, ulp
-from tests import test_modelgen_depths as tmd
-from tests import test_modelgen_shapes as tms
 
 pytestmark = pytest.mark.gpu
 
-# model -> (its generator, the stage_outputs that goes with it)
-MODELS = {"narrow": (ms, tms), "odd": (ms, tms), "wide": (ms, tms), "logit": (md, tmd), "two_deep": (md, tmd), "in3_f32": (md, tmd)}
-HUB_DEGREES = [511, 512, 513, 767, 768, 769, 1025, 3000, 0]
-HUB_N = 6000
+# model -> family
+MODELS = {"narrow": "shapes", "odd": "shapes", "wide": "shapes", "logit": "depths", "two_deep": "depths", "in3_f32": "depths"}
 THRESHOLDS = [1, 2, 16, 33, 64, 65, 257, 512, 0]
 DEFAULT_FROM = 512
-
-
-def hub_graph():
-    rng = np.random.default_rng(77)
-    nh = len(HUB_DEGREES)
-    others = np.arange(nh, HUB_N)
-    edges = []
-    for h, d in enumerate(HUB_DEGREES):
-        for v in rng.choice(others, size=d, replace=False):
-            edges.append((h, int(v)))
-    a = rng.integers(nh, HUB_N, size=9000)
-    b = rng.integers(nh, HUB_N, size=9000)
-    edges += list(zip(a.tolist(), b.tolist()))
-    return gg.from_edge_list(HUB_N, edges, rng.integers(20, 121, size=HUB_N))
-
-
-GRAPHS = {
-    "hubs": hub_graph,
-    "er3000": lambda: gg.erdos_renyi(3000, 15000, 15),
-    "sparse": lambda: gg.erdos_renyi(5000, 3000, 23),                     # about three rows in ten are empty
-    "hub6k": lambda: gg.hub_graph(6000, 18000, 2, 3000, seed=9),          # another graph, two heavy rows (lazy classing)
-}
-
-_cache = {}
-
-
-def gen_of(name):
-    return MODELS[name][0]
-
-
-def text_of(name):
-    if ("text", name) not in _cache:
-        _cache["text", name] = gen_of(name).FAMILY[name]()
-    return _cache["text", name]
-
-
-def graph_of(gname):
-    if ("graph", gname) not in _cache:
-        _cache["graph", gname] = GRAPHS[gname]()
-    return _cache["graph", gname]
-
-
-def degrees(g):
-    return np.diff(g.rowptr.astype(np.int64))
-
-
-def oracle_of(name, g):
-    om = oracle_py.OracleModel(text_of(name))
-    om.set_weight_scale(g.ws)
-    return om
-
-
-def want_of(name, gname):
-    """[(stage input, stage output, pre-activation of the stage's last linear layer)] from the oracle's layers."""
-    if ("want", name, gname) not in _cache:
-        g = graph_of(gname)
-        _cache["want", name, gname] = MODELS[name][1].stage_outputs(oracle_of(name, g), name, g)
-    return _cache["want", name, gname]
-
-
-def flat_logits(name, gname):
-    key = ("flat", name, gname)
-    if key not in _cache:
-        _cache[key] = np.ascontiguousarray(want_of(name, gname)[-1][2].reshape(-1))
-    return _cache[key]
-
-
-def stage_depths(name):
-    return md.stage_depths(name) if gen_of(name) is md else [3] * len(ms.SPECS[name][1])
-
-
-def oracle_stage(name, g, s, hin):
-    """(output rows, pre-activation of the last linear layer) of stage s alone, from the input rows hin, through the oracle's layers."""
-    P = oracle_of(name, g).linear_params()
-    depths = stage_depths(name)
-    i = sum(depths[:s])
-    h = oracle_py.graph_layer(g, g.ws, np.ascontiguousarray(hin, dtype=np.float32))
-    pre = None
-    for _ in range(depths[s]):
-        pre = oracle_py.linear_layer(h, *P[i])
-        i += 1
-        h = oracle_py.sigmoid(pre) if i == len(P) else oracle_py.relu(pre)
-    return h, pre
-
-
-def open_engine(name, g, heavy_from=None, opts=()):
-    import gnn_mwvc_amd as G
-    e = G.Engine(text_of(name), device=0)
-    try:
-        for k, v in dict(opts).items():
-            e.set_option(k, v)
-        if heavy_from is not None:
-            e.set_generic_heavy_rows(heavy_from)
-        e.set_weight_scale(g.ws)
-        e.upload_graph(g)
-    except BaseException:
-        e.close()
-        raise
-    return e
-
-
-def run_stage_ranges(e, name, g, s, hin, ranges_by_part, want_out, want_pre, label):
-    """The stage entry over the ranges of each part in turn, on NaN-filled outputs: after every part the rows done so far are the
-    oracle's and every other row (the pad row included) is still NaN."""
-    import torch
-    dev = torch.device("cuda:0")
-    n = g.n
-    f, n_out = gen_of(name).stage_widths(name)[s]
-    last = s + 1 == len(gen_of(name).stage_widths(name))
-    tin = torch.zeros((n + 1, f), dtype=torch.float32, device=dev)
-    tin[:n] = torch.from_numpy(np.ascontiguousarray(hin, dtype=np.float32).reshape(n, f)).to(dev)
-    out = torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev)
-    lgt = torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev)
-    torch.cuda.synchronize()
-    done = np.zeros(n + 1, dtype=bool)
-    for part, todo in enumerate(ranges_by_part):
-        for lo, hi in todo:
-            e.stage_forward_device(s, lo, hi, tin.data_ptr(), out.data_ptr(), lgt.data_ptr() if last else 0)
-            done[lo:hi] = True
-        e.synchronize()
-        got, gotl = out.cpu().numpy(), lgt.cpu().numpy()
-        assert np.isnan(got[~done]).all(), (label, s, part, "rows outside the ranges were written")
-        assert np.isnan(gotl[~done]).all() if last else np.isnan(gotl).all(), (label, s, part, "logits rows")
-        d = done[:n]
-        if last:
-            assert np.array_equal(bits(gotl[:n][d]), bits(want_pre[d])), (label, s, part, "stage logits")
-            assert ulp(got[:n][d], want_out[d]).max(initial=0) <= 1, (label, s, part, "stage scores")
-        else:
-            bad = np.argwhere(bits(got[:n][d]) != bits(want_out[d]))
-            assert bad.size == 0, (label, s, part, f"{len(bad)} values differ, first (row, column)", bad[:6].tolist())
-    return done
+GRAPHS = ["hubs", "er3000", "sparse", "hub6k"]   # (tests/generic_harness.py has what each is)
 
 
 def test_graphs_are_what_the_names_say():
@@ -181,7 +44,7 @@ def test_graphs_are_what_the_names_say():
 
 def test_the_default_threshold_is_512():
     import gnn_mwvc_amd as G
-    e = G.Engine(text_of("narrow"), device=0)
+    e = G.Engine(gh.text_of("shapes", "narrow"), device=0)
     try:
         assert e.get_info("generic_heavy_from") == DEFAULT_FROM
         assert e.get_info("generic_heavy_rows") == 0 and e.get_info("generic_heavy_last_rows") == 0
@@ -206,12 +69,13 @@ def test_the_default_threshold_is_512():
 
 @pytest.mark.parametrize("name", list(MODELS))
 def test_every_threshold_gives_the_oracles_bits(shim, name):
+    fam = MODELS[name]
     for gname in ("er3000", "hubs"):
         g = graph_of(gname)
         deg = degrees(g)
-        wl = want_of(name, gname)[-1][2]
-        x = gen_of(name).model_input(name, g)
-        e = open_engine(name, g)
+        wl = gh.want_of(fam, name, gname)[-1][2]
+        x = gh.FAMILIES[fam].model_input(name, g)
+        e = gh.open_engine(fam, name, g)
         try:
             first = None
             for thr in THRESHOLDS:
@@ -219,7 +83,7 @@ def test_every_threshold_gives_the_oracles_bits(shim, name):
                 sc, lg = e.forward(x)
                 mism = int((bits(lg) != bits(wl)).sum())
                 assert mism == 0, (name, gname, thr, f"{mism}/{lg.size} logits differ", np.argwhere(bits(lg) != bits(wl))[:6].tolist())
-                check_scores(shim, sc.reshape(-1), lg.reshape(-1), flat_logits(name, gname), (name, gname, thr))
+                check_scores(shim, sc.reshape(-1), lg.reshape(-1), gh.flat_logits(fam, name, gname), (name, gname, thr))
                 if first is None:
                     first = (sc.copy(), lg.copy())
                 assert np.array_equal(bits(sc), bits(first[0])) and np.array_equal(bits(lg), bits(first[1])), (name, gname, thr)
@@ -239,30 +103,22 @@ def test_every_threshold_gives_the_oracles_bits(shim, name):
 
 @pytest.mark.parametrize("name", list(MODELS))
 def test_threshold_1_sends_every_non_empty_row_the_heavy_way(shim, name):
+    fam = MODELS[name]
     g = graph_of("sparse")
     deg = degrees(g)
-    wl = want_of(name, "sparse")[-1][2]
-    e = open_engine(name, g, heavy_from=1)
+    wl = gh.want_of(fam, name, "sparse")[-1][2]
+    e = gh.open_engine(fam, name, g, heavy=1)
     try:
-        sc, lg = e.forward(gen_of(name).model_input(name, g))
+        sc, lg = e.forward(gh.FAMILIES[fam].model_input(name, g))
         assert e.get_info("generic_heavy_last_rows") == int((deg > 0).sum()) < g.n
         assert e.get_info("generic_heavy_entries") == g.nnz
         assert np.array_equal(bits(lg), bits(wl)), name
-        check_scores(shim, sc.reshape(-1), lg.reshape(-1), flat_logits(name, "sparse"), name)
+        check_scores(shim, sc.reshape(-1), lg.reshape(-1), gh.flat_logits(fam, name, "sparse"), name)
     finally:
         e.close()
 
 
 # ---------------------------------------------------------------- the order of a row's additions
-
-def crafted_input(n, f, seed):
-    """Magnitudes from 2^-20 to 2^20, both signs, some -0.0f: sums whose bits depend on the order of their terms."""
-    rng = np.random.default_rng(seed)
-    v = np.ldexp(rng.uniform(1.0, 2.0, (n, f)), rng.integers(-20, 21, (n, f))).astype(np.float32)
-    v = np.where(rng.random((n, f)) < 0.5, -v, v).astype(np.float32)
-    v[rng.random((n, f)) < 0.05] = np.float32(-0.0)
-    return np.ascontiguousarray(v, dtype=np.float32)
-
 
 @pytest.mark.parametrize("stage", [0, 1])
 @pytest.mark.parametrize("thr", [DEFAULT_FROM, 1])
@@ -286,10 +142,10 @@ def test_the_sums_are_added_in_stored_order(stage, thr):
     assert (bits(fwd) != bits(rev)).any(), "the crafted input does not tell the two orders apart"
     agg = oracle_py.graph_layer(g, g.ws, hin)
     assert np.array_equal(bits(agg[hub, :f]), bits(fwd)), "the oracle adds a row in stored order"
-    want_out, want_pre = oracle_stage(name, g, stage, hin)
-    e = open_engine(name, g, heavy_from=thr)
+    want_out, want_pre = gh.oracle_stage("depths", name, g, stage, hin)
+    e = gh.open_engine("depths", name, g, heavy=thr)
     try:
-        run_stage_ranges(e, name, g, stage, hin, [[(0, g.n)]], want_out, want_pre, (name, "crafted", thr))
+        gh.run_stage_ranges(e, "depths", name, g, stage, hin, [[(0, g.n)]], want_out, want_pre, (name, "crafted", thr))
         assert e.get_info("generic_heavy_last_rows") == int((degrees(g) >= thr).sum())
     finally:
         e.close()
@@ -299,17 +155,18 @@ def test_the_sums_are_added_in_stored_order(stage, thr):
 
 @pytest.mark.parametrize("name", list(MODELS))
 def test_stage_entry_over_split_ranges(name):
+    fam = MODELS[name]
     g = graph_of("hubs")
     n = g.n
-    want = want_of(name, "hubs")
+    want = gh.want_of(fam, name, "hubs")
     # hubs 0 .. 2 and 6 .. 8 in the first two ranges, hubs 3 .. 5 in the gap between them: heavy rows on both sides of every cut
     first, gap = [(0, 3), (6, n // 2)], [(3, 6), (n // 2, n)]
     for thr in (DEFAULT_FROM, 1):
-        e = open_engine(name, g, heavy_from=thr)
+        e = gh.open_engine(fam, name, g, heavy=thr)
         try:
             assert len(want) == e.num_stages
             for s, (hin, hout, pre) in enumerate(want):
-                done = run_stage_ranges(e, name, g, s, hin, [first, gap], hout, pre, (name, "hubs", thr))
+                done = gh.run_stage_ranges(e, fam, name, g, s, hin, [first, gap], hout, pre, (name, "hubs", thr))
                 assert done[:n].all() and not done[n]
                 assert e.get_info("generic_heavy_last_rows") == int((degrees(g) >= thr).sum())
         finally:
@@ -323,19 +180,20 @@ def test_two_slices_compute_the_whole_graph(name):
     import torch
     import gnn_mwvc_amd as G
     from gnn_mwvc_amd import distributed as D
+    fam = MODELS[name]
     g = graph_of("hubs")
     n = g.n
     deg = degrees(g)
-    want = want_of(name, "hubs")
+    want = gh.want_of(fam, name, "hubs")
     dev = torch.device("cuda:0")
     t = lambda a: torch.from_numpy(a.astype(np.int64)).to(torch.int32).to(dev)
     rp, col, w, nw = t(g.rowptr), t(g.col), t(g.w), t(g.nw)
-    widths = gen_of(name).stage_widths(name)
+    widths = gh.FAMILIES[fam].stage_widths(name)
     outs = [torch.full((n + 1, n_out), float("nan"), dtype=torch.float32, device=dev) for _, n_out in widths]
     lgt = torch.full((n + 1, widths[-1][1]), float("nan"), dtype=torch.float32, device=dev)
     for lo, hi in ((0, 5), (5, n)):   # hubs 0 .. 4 in one slice, 5 .. 8 in the other
         sl = D.slice_csr(n, rp, col, w, nw, lo, hi)
-        e = G.Engine(text_of(name), device=0)
+        e = G.Engine(gh.text_of(fam, name), device=0)
         try:
             e.set_weight_scale(g.ws)
             torch.cuda.synchronize()
@@ -366,14 +224,15 @@ def test_two_slices_compute_the_whole_graph(name):
 
 @pytest.mark.parametrize("name", ["odd", "in3_f32"])
 def test_the_explicit_audit_is_clean(name):
+    fam = MODELS[name]
     g = graph_of("hubs")
-    wl = want_of(name, "hubs")[-1][2]
-    e = open_engine(name, g)
+    wl = gh.want_of(fam, name, "hubs")[-1][2]
+    e = gh.open_engine(fam, name, g)
     try:
         runs = 0
         for thr in (1, DEFAULT_FROM):
             e.set_generic_heavy_rows(thr)
-            _, lg = e.forward_audited(gen_of(name).model_input(name, g))   # (raises on a mismatch)
+            _, lg = e.forward_audited(gh.FAMILIES[fam].model_input(name, g))   # (raises on a mismatch)
             runs += e.num_stages
             assert e.get_info("generic_heavy_last_rows") == int((degrees(g) >= thr).sum())
             assert e.get_info("audit_runs") == runs and e.get_info("audit_failures") == 0
@@ -388,7 +247,7 @@ def test_a_graph_attached_before_the_option_is_classed_by_the_first_generic_stag
     name = "two_deep"
     g = graph_of("hubs")
     x = md.model_input(name, g)
-    e = open_engine(name, g, opts={"generic_stages": 0})
+    e = gh.open_engine("depths", name, g, opts={"generic_stages": 0})
     try:
         assert not e.fused
         sc0, lg0 = e.forward(x)
@@ -399,7 +258,7 @@ def test_a_graph_attached_before_the_option_is_classed_by_the_first_generic_stag
         assert e.get_info("generic_stages_active") == 1
         assert e.get_info("generic_heavy_last_rows") == 7 and e.get_info("generic_heavy_rows") == 7
         assert np.array_equal(bits(lg0), bits(lg1)) and np.array_equal(bits(sc0), bits(sc1))
-        assert np.array_equal(bits(lg1), bits(want_of(name, "hubs")[-1][2]))
+        assert np.array_equal(bits(lg1), bits(gh.want_of("depths", name, "hubs")[-1][2]))
         # the next graphs: their own counts
         for gname, rows in (("hub6k", 2), ("er3000", 0), ("hubs", 7)):
             g2 = graph_of(gname)
@@ -409,27 +268,12 @@ def test_a_graph_attached_before_the_option_is_classed_by_the_first_generic_stag
             _, lg = e.forward(md.model_input(name, g2))
             assert e.get_info("generic_heavy_last_rows") == rows, gname
             assert e.get_info("generic_heavy_entries") == int(degrees(g2)[degrees(g2) >= DEFAULT_FROM].sum()), gname
-            assert np.array_equal(bits(lg), bits(want_of(name, gname)[-1][2])), gname
+            assert np.array_equal(bits(lg), bits(gh.want_of("depths", name, gname)[-1][2])), gname
     finally:
         e.close()
 
 
 # ---------------------------------------------------------------- on <= off
-
-def _steady_ms(torch, e, x, sc, lg):
-    for _ in range(2):
-        e.forward_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())
-    e.synchronize()
-    best = 1e9
-    for _ in range(3):                       # the best of three batches of five, as tests/test_gpu_depths.py
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(5):
-            e.forward_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())
-        e.synchronize()
-        best = min(best, (time.perf_counter() - t) * 200.0)
-    return best, lg.clone()
-
 
 def test_the_heavy_path_is_not_slower_than_without_it_on_four_giant_hubs():
     import torch
@@ -440,7 +284,7 @@ def test_the_heavy_path_is_not_slower_than_without_it_on_four_giant_hubs():
     x1 = g.x().contiguous()
     inputs = {"narrow": x1, "in3_f32": torch.stack([x1, x1 * 0.37, 1.0 - x1], dim=1).contiguous()}
     for name, x in inputs.items():
-        e = G.Engine(text_of(name), device=0)
+        e = G.Engine(gh.text_of(MODELS[name], name), device=0)
         try:
             e.set_weight_scale(g.ws)
             e.attach_graph_device(g.n, g.nnz, g.rowptr.data_ptr(), g.col.data_ptr(), g.w.data_ptr(), g.nw.data_ptr(), keepalive=g)
@@ -448,10 +292,10 @@ def test_the_heavy_path_is_not_slower_than_without_it_on_four_giant_hubs():
             lg = torch.zeros(g.n, device=dev)
             torch.cuda.synchronize()
             assert e.get_info("generic_heavy_from") == DEFAULT_FROM
-            ms_default, lg_on = _steady_ms(torch, e, x, sc, lg)
+            ms_default, lg_on = gh.steady_ms(e, x, sc, lg)
             assert e.get_info("generic_stages_active") == 1 and e.get_info("generic_heavy_last_rows") >= 4
             e.set_generic_heavy_rows(0)
-            ms_off, lg_off = _steady_ms(torch, e, x, sc, lg)
+            ms_off, lg_off = gh.steady_ms(e, x, sc, lg)
             assert e.get_info("generic_heavy_last_rows") == 0
             print(f"power-law 262144 / four hubs of 65536, {name}: heavy rows from 512 {ms_default:.3f} ms, off {ms_off:.3f} ms, "
                   f"{ms_off / ms_default:.2f}x")

@@ -13,6 +13,7 @@ from oracle import oracle_py
 from tools import graphgen as gg
 from tools import modelgen as mg
 from tests.test_expf_restatement import shim, _run   # noqa: F401  (the fixture that builds tests/support/libexpf_shim.so)
+from tests.generic_harness import bits, check_scores, ulp   # noqa: F401  (defined there; the trained-shape tests read them here)
 from tests.test_gpu_fuzz import _graph, _options
 from tests.test_modelgen import GRAPHS, _predicted, layer_outputs
 
@@ -25,14 +26,6 @@ PLANNED = {"blocked_min_n": 0, "compact_min_n": 0, "plans_at_handoff": 2}
 # the zero-row prediction at hand-off, as test_predicted_pruned_adjacency_is_bit_identical engages it
 PREDICT = {"blocked_min_n": 0, "long_row_threshold": 256, "sorted_long_row_threshold": 512, "giant_row_threshold": 4096,
            "prune_min_entries": 0, "prune_predict_min_entries": 0, "filter_min_long_percent": 0, "prune_min_drop_percent": 1}
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def ulp(a, b):
-    return np.abs(bits(a).view(np.int32).astype(np.int64) - bits(b).view(np.int32).astype(np.int64))
 
 
 _cache = {}
@@ -88,19 +81,6 @@ def open_engine(name, g, opts=(), devices=None):
         e.close()
         raise
     return e
-
-
-def check_scores(shim, scores, logits, want_logits, label):
-    """<= 1 ulp from the oracle's scores (the host libm's sigmoid of the oracle's logits), and the restated sigmoid's bits."""
-    assert np.array_equal(bits(logits), bits(want_logits)), label
-    key = ("sigmoid", id(want_logits))   # (equal logits: one host sigmoid of each kind per reference array, which the entry keeps alive)
-    if key not in _cache:
-        w = np.ascontiguousarray(want_logits, dtype=np.float32)
-        _cache[key] = (want_logits, oracle_py.sigmoid(w), _run(shim.sigmoid_restated, w))
-    _, host, restated = _cache[key]
-    assert ulp(scores, host).max() <= 1, label
-    diff = int((bits(scores) != bits(restated)).sum())
-    assert diff == 0, f"{label}: {diff} scores differ from sigmoid_restated(logits)"
 
 
 def forwards(e, shim, name, gname, reps=5, label=()):

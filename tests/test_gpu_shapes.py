@@ -10,8 +10,8 @@ reproduces tests/golden/ and the default engine.
 The speed guard at the end is in the style of tests/test_gpu_perf_guard.py: steady forwards with the option at 1 are not slower
 than with it at 0 (which stands for the engine before the option: forward_unfused and the layer-by-layer kernels are
 untouched by it)."""
+import functools
 import json
-import time
 
 import numpy as np
 import pytest
@@ -19,67 +19,19 @@ import pytest
 from oracle import oracle_py
 from tools import graphgen as gg
 from tools import modelgen_shapes as ms
+from tests import generic_harness as gh
+from tests.generic_harness import bits, check_scores, graph_of, ulp
 from tests.test_expf_restatement import shim, _run   # noqa: F401  (the fixture that builds tests/support/libexpf_shim.so)
-from tests.test_gpu_models import bits, check_scores, ulp
-from tests.test_modelgen_shapes import stage_outputs
 
 pytestmark = pytest.mark.gpu
 
 MODELS = list(ms.SPECS)
-GRAPHS = {
-    "er3000": lambda: gg.erdos_renyi(3000, 15000, 15),
-    "er100k": lambda: gg.erdos_renyi(100000, 1000000, 1),
-    "hub20k": lambda: gg.hub_graph(40000, 120000, 2, 20000, seed=9),     # two rows of 20000 entries (beyond 16384)
-    "sparse": lambda: gg.erdos_renyi(5000, 3000, 23),                     # about three rows in ten are empty
-    "er1933": lambda: gg.erdos_renyi(1933, 7000, 61),                     # n = 30 * 64 + 13
-    "one": lambda: gg.from_edge_list(1, [], [57]),                        # n = 1
-}
+# the accessors of tests/generic_harness.py, for the family of this file
+text_of, want_of, flat_logits, open_engine = (functools.partial(f, "shapes")
+                                              for f in (gh.text_of, gh.want_of, gh.flat_logits, gh.open_engine))
+GRAPHS = ["er3000", "er100k", "hub20k", "sparse", "er1933", "one"]   # (tests/generic_harness.py has what each is)
 ERR_UNSUPPORTED = -5
 ERR_INVALID = -1
-
-_cache = {}
-
-
-def text_of(name):
-    if ("text", name) not in _cache:
-        _cache["text", name] = ms.FAMILY[name]()
-    return _cache["text", name]
-
-
-def graph_of(gname):
-    if ("graph", gname) not in _cache:
-        _cache["graph", gname] = GRAPHS[gname]()
-    return _cache["graph", gname]
-
-
-def want_of(name, gname):
-    """[(stage input, stage output, pre-activation of the stage's last linear layer)] from the oracle's layers."""
-    if ("want", name, gname) not in _cache:
-        g = graph_of(gname)
-        om = oracle_py.OracleModel(text_of(name))
-        om.set_weight_scale(g.ws)
-        _cache["want", name, gname] = stage_outputs(om, name, g)
-    return _cache["want", name, gname]
-
-
-def open_engine(name, g, opts=(), expect_fused=True):
-    import gnn_mwvc_amd as G
-    e = G.Engine(text_of(name), device=0)
-    try:
-        for k, v in dict(opts).items():
-            e.set_option(k, v)
-        assert e.num_layers == ms.num_layers(name) and e.in_width == ms.in_width(name) and e.out_width == ms.out_width(name), name
-        if expect_fused:
-            assert e.fused, name
-            assert e.num_stages == len(ms.SPECS[name][1]), name
-            assert [e.stage_widths(s) for s in range(e.num_stages)] == ms.stage_widths(name), name
-            assert e.get_info("generic_stages_model") == 1
-        e.set_weight_scale(g.ws)
-        e.upload_graph(g)
-    except BaseException:
-        e.close()
-        raise
-    return e
 
 
 def test_graphs_are_what_the_names_say():
@@ -95,12 +47,11 @@ def test_graphs_are_what_the_names_say():
 @pytest.mark.parametrize("gname", list(GRAPHS))
 @pytest.mark.parametrize("name", MODELS)
 def test_forward_and_stage_entry(shim, name, gname):
-    import torch
     g = graph_of(gname)
     want = want_of(name, gname)
     wl = want[-1][2]
     x = ms.model_input(name, g)
-    e = open_engine(name, g)
+    e = open_engine(name, g, expect_fused=True)
     try:
         # ---- whole forwards (twice: nothing may depend on what an earlier forward left)
         for rep in range(2):
@@ -109,43 +60,13 @@ def test_forward_and_stage_entry(shim, name, gname):
             mism = int((bits(lg) != bits(wl)).sum())
             assert mism == 0, (name, gname, rep, f"{mism}/{lg.size} logits differ", np.argwhere(bits(lg) != bits(wl))[:6].tolist())
             assert e.get_info("generic_stages_active") == 1
-        key = ("flat", name, gname)
-        if key not in _cache:
-            _cache[key] = np.ascontiguousarray(wl.reshape(-1))
-        check_scores(shim, sc.reshape(-1), lg.reshape(-1), _cache[key], (name, gname))
+        check_scores(shim, sc.reshape(-1), lg.reshape(-1), flat_logits(name, gname), (name, gname))
         # ---- the stage entry over split row ranges, each stage fed the oracle's input: first two ranges with a gap between
         # them (the gap, the rows behind and the pad row stay as they were), then the gap
-        dev = torch.device("cuda:0")
-        n = g.n
-        cuts = sorted({0, n // 5, n // 3, (2 * n) // 3, n})
-        ranges = list(zip(cuts[:-1], cuts[1:]))
-        first, gap = (ranges[0::2], ranges[1::2]) if len(ranges) > 1 else (ranges, [])
+        first, gap = gh.split_ranges(g.n)
         for s, (hin, hout, pre) in enumerate(want):
-            f, n3 = ms.stage_widths(name)[s]
-            last = s + 1 == len(want)
-            tin = torch.zeros((n + 1, f), dtype=torch.float32, device=dev)
-            tin[:n] = torch.from_numpy(np.ascontiguousarray(hin)).to(dev)
-            out = torch.full((n + 1, n3), float("nan"), dtype=torch.float32, device=dev)
-            lgt = torch.full((n + 1, n3), float("nan"), dtype=torch.float32, device=dev)
-            torch.cuda.synchronize()
-            for part, todo in enumerate((first, gap)):
-                for lo, hi in todo:
-                    e.stage_forward_device(s, lo, hi, tin.data_ptr(), out.data_ptr(), lgt.data_ptr() if last else 0)
-                e.synchronize()
-                got, gotl = out.cpu().numpy(), lgt.cpu().numpy()
-                done = np.zeros(n + 1, dtype=bool)
-                for lo, hi in (first if part == 0 else first + gap):
-                    done[lo:hi] = True
-                assert np.isnan(got[~done]).all(), (name, gname, s, part, "rows outside the ranges were written")
-                assert np.isnan(gotl[~done]).all() if last else np.isnan(gotl).all(), (name, gname, s, part, "logits rows")
-                w_out = hout[done[:n]]
-                if last:
-                    assert np.array_equal(bits(gotl[:n][done[:n]]), bits(pre[done[:n]])), (name, gname, s, part, "stage logits")
-                    assert ulp(got[:n][done[:n]], w_out).max(initial=0) <= 1, (name, gname, s, part, "stage scores")
-                else:
-                    bad = np.argwhere(bits(got[:n][done[:n]]) != bits(w_out))
-                    assert bad.size == 0, (name, gname, s, part, f"{len(bad)} values differ, first (row, column)", bad[:6].tolist())
-            assert done[:n].all() and not done[n]
+            done = gh.run_stage_ranges(e, "shapes", name, g, s, hin, [first, gap], hout, pre, (name, gname))
+            assert done[:g.n].all() and not done[g.n]
     finally:
         e.close()
 
@@ -158,7 +79,7 @@ def test_option_0_is_the_engine_before_the_option(name):
     for gname in ("er3000", "hub20k"):
         g = graph_of(gname)
         x = ms.model_input(name, g)
-        e = open_engine(name, g)
+        e = open_engine(name, g, expect_fused=True)
         try:
             sc1, lg1 = e.forward(x)
             assert e.get_info("generic_stages_active") == 1
@@ -178,7 +99,7 @@ def test_option_0_is_the_engine_before_the_option(name):
         finally:
             e.close()
         # an engine that has the option at 0 from the start
-        e = open_engine(name, g, {"generic_stages": 0}, expect_fused=False)
+        e = open_engine(name, g, {"generic_stages": 0})
         try:
             assert not e.fused and e.num_stages == 0
             _, lg = e.forward(x)
@@ -295,7 +216,7 @@ def test_stage_input_ready_and_the_codec_keep_their_errors(name):
     import torch
     import gnn_mwvc_amd as G
     g = graph_of("er3000")
-    e = open_engine(name, g)
+    e = open_engine(name, g, expect_fused=True)
     try:
         f, _ = ms.stage_widths(name)[1]
         t = torch.zeros((g.n + 1, f), dtype=torch.float32, device="cuda:0")
@@ -319,32 +240,6 @@ def test_stage_input_ready_and_the_codec_keep_their_errors(name):
 
 # ---------------------------------------------------------------- speed guard
 
-def _steady_ms(G, torch, name, g, x, generic, dev):
-    e = G.Engine(text_of(name), device=0)
-    try:
-        e.set_option("generic_stages", generic)
-        e.set_weight_scale(g.ws)
-        e.attach_graph_device(g.n, g.nnz, g.rowptr.data_ptr(), g.col.data_ptr(), g.w.data_ptr(), g.nw.data_ptr(), keepalive=g)
-        sc = torch.zeros(g.n, device=dev)
-        lg = torch.zeros(g.n, device=dev)
-        torch.cuda.synchronize()
-        for _ in range(2):
-            e.forward_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())
-        e.synchronize()
-        assert e.get_info("generic_stages_active") == (1 if generic else 0)
-        best = 1e9
-        for _ in range(3):                       # the best of three batches of five, as tests/test_gpu_perf_guard.py
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            for _ in range(5):
-                e.forward_device(x.data_ptr(), sc.data_ptr(), lg.data_ptr())
-            e.synchronize()
-            best = min(best, (time.perf_counter() - t) * 200.0)
-        return best, lg.clone()
-    finally:
-        e.close()
-
-
 @pytest.mark.parametrize("gkind", ["er1m", "rmat20"])
 def test_generic_stages_are_not_slower_than_layer_by_layer(gkind):
     import torch
@@ -354,8 +249,8 @@ def test_generic_stages_are_not_slower_than_layer_by_layer(gkind):
     g = ggt.erdos_renyi(1_000_000, 10_000_000, 2, dev) if gkind == "er1m" else ggt.rmat(20, 8, 5, dev)
     x = g.x().contiguous()
     for name in ("wide", "narrow", "first_trained"):
-        ms_layers, lg0 = _steady_ms(G, torch, name, g, x, 0, dev)
-        ms_fused, lg1 = _steady_ms(G, torch, name, g, x, 1, dev)
+        ms_layers, lg0 = gh.steady_ms_under_option("shapes", name, g, x, 0)
+        ms_fused, lg1 = gh.steady_ms_under_option("shapes", name, g, x, 1)
         print(f"{gkind} {name}: generic_stages=1 {ms_fused:.3f} ms, =0 {ms_layers:.3f} ms, {ms_layers / ms_fused:.2f}x")
         assert torch.equal(lg0.view(torch.int32), lg1.view(torch.int32)), (gkind, name)
         assert ms_fused <= ms_layers + 0.025, f"{gkind} {name}: generic stages {ms_fused:.3f} ms vs layer by layer {ms_layers:.3f} ms"

@@ -1,8 +1,9 @@
 """tools/modelgen_big.py: models whose stages lie outside the generic fused stage's default bounds (what
 gnnvc_set_generic_big_stages admits, and one member it does not).  The specs and the byte figures of the kernel's LDS layout —
-restated in Python by the generator — are pinned here; on the ORACLE, on erdos_renyi(3000, 15000, 15), every text parses with the
-named shapes, the stage-by-stage walk that tests/test_gpu_big_stages.py takes its per-stage references from equals predict bit
-for bit, and every member's logits are finite and take more than one value."""
+restated in Python by the generator — are pinned here (LDS_BYTES of tests/generic_harness.py, which the GPU test holds the engine
+to as well); on the ORACLE, on erdos_renyi(3000, 15000, 15), every text parses with the named shapes, the stage-by-stage walk that
+tests/test_gpu_big_stages.py takes its per-stage references from equals predict bit for bit, and every member's logits are finite
+and take more than one value."""
 import numpy as np
 import pytest
 
@@ -10,40 +11,9 @@ from oracle import oracle_py
 from tools import graphgen as gg
 from tools import modelgen_big as mb
 from tools import modelgen_depths as md
+from tests.generic_harness import LDS_BYTES, bits, stage_outputs
 
 LINEAR, GRAPH, RELU, SIGMOID = 0, 1, 2, 3
-
-# name -> bytes per stage of stage_any_layout at 16 rows a workgroup (256 threads)
-LDS_BYTES = {
-    "too_big": [91008, 97056],
-    "h128": [99648, 65568],
-    "odd_wide": [50896, 83616],
-    "edge": [161488, 4640],
-    "over": [176256, 48416],
-}
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def stage_outputs(om, name, g, x=None):
-    """Per stage: (input rows, output rows after the stage's last activation, pre-activation of its last linear layer), through
-    the oracle's own layer functions (ws = g.ws).  The last stage's output is the scores, its pre-activation the logits."""
-    h = mb.model_input(name, g) if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(g.n, -1)
-    P = om.linear_params()
-    out = []
-    i = 0
-    for d in mb.stage_depths(name):
-        hin = h
-        h = oracle_py.graph_layer(g, g.ws, h)
-        for _ in range(d):
-            pre = oracle_py.linear_layer(h, *P[i])
-            i += 1
-            h = oracle_py.sigmoid(pre) if i == len(P) else oracle_py.relu(pre)
-        out.append((hin, h, pre))
-    assert i == len(P)
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -121,7 +91,7 @@ def test_walk_equals_predict_and_logits_are_alive(graph, name):
     om.set_weight_scale(g.ws)
     x = mb.model_input(name, g)
     assert x.shape == (g.n, mb.in_width(name))
-    st = stage_outputs(om, name, g)
+    st = stage_outputs(om, "big", name, g)
     assert [(a.shape[1], b.shape[1]) for a, b, _ in st] == mb.stage_widths(name)
     logits = om.predict(g, x, stop_after=om.n_layers - 2)
     scores = om.predict(g, x)

@@ -9,31 +9,9 @@ import pytest
 from oracle import oracle_py
 from tools import graphgen as gg
 from tools import modelgen_depths as md
+from tests.generic_harness import bits, stage_outputs
 
 LINEAR, GRAPH, RELU, SIGMOID = 0, 1, 2, 3
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def stage_outputs(om, name, g, x=None):
-    """Per stage: (input rows, output rows after the stage's last activation, pre-activation of its last linear layer), through
-    the oracle's own layer functions (ws = g.ws).  The last stage's output is the scores, its pre-activation the logits."""
-    h = md.model_input(name, g) if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(g.n, -1)
-    P = om.linear_params()
-    out = []
-    i = 0
-    for d in md.stage_depths(name):
-        hin = h
-        h = oracle_py.graph_layer(g, g.ws, h)
-        for _ in range(d):
-            pre = oracle_py.linear_layer(h, *P[i])
-            i += 1
-            h = oracle_py.sigmoid(pre) if i == len(P) else oracle_py.relu(pre)
-        out.append((hin, h, pre))
-    assert i == len(P)
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -82,7 +60,7 @@ def test_walk_equals_predict_and_logits_are_alive(graph, name):
     om.set_weight_scale(g.ws)
     x = md.model_input(name, g)
     assert x.shape == (g.n, md.in_width(name))
-    st = stage_outputs(om, name, g)
+    st = stage_outputs(om, "depths", name, g)
     assert [(a.shape[1], b.shape[1]) for a, b, _ in st] == md.stage_widths(name)
     logits = om.predict(g, x, stop_after=om.n_layers - 2)
     scores = om.predict(g, x)

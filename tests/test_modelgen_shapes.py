@@ -18,33 +18,13 @@ import pytest
 from oracle import oracle_py
 from tools import graphgen as gg
 from tools import modelgen_shapes as ms
+from tests.generic_harness import bits, stage_outputs
 from tests.test_openblas_seam import _find_openblas
 
 GRAPHS = {
     "er3000": lambda: gg.erdos_renyi(3000, 15000, 15),
     "hub2k": lambda: gg.hub_graph(2000, 6000, 2, 700, seed=5),
 }
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def stage_outputs(om, name, g, x=None):
-    """Per stage: (input rows, output rows after the stage's last activation, pre-activation of its last linear layer), through
-    the oracle's own layer functions (ws = g.ws).  The last stage's output is the scores, its pre-activation the logits."""
-    h = ms.model_input(name, g) if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(g.n, -1)
-    P = om.linear_params()
-    out = []
-    for s in range(len(P) // 3):
-        hin = h
-        h = oracle_py.graph_layer(g, g.ws, h)
-        for i in range(3):
-            pre = oracle_py.linear_layer(h, *P[3 * s + i])
-            last = 3 * s + i + 1 == len(P)
-            h = oracle_py.sigmoid(pre) if last else oracle_py.relu(pre)
-        out.append((hin, h, pre))
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -88,7 +68,7 @@ def test_walk_equals_predict_and_logits_are_alive(graphs, name):
         om.set_weight_scale(g.ws)
         x = ms.model_input(name, g)
         assert x.shape == (g.n, ms.in_width(name))
-        st = stage_outputs(om, name, g)
+        st = stage_outputs(om, "shapes", name, g)
         assert [(a.shape[1], b.shape[1]) for a, b, _ in st] == ms.stage_widths(name)
         logits = om.predict(g, x, stop_after=om.n_layers - 2)
         scores = om.predict(g, x)
