@@ -1,6 +1,6 @@
 """What the tests of the generic fused stage (k_stage_any) share: the comparison rules, the oracle's stage-by-stage walk that every
-GPU test takes its expected values from, one cache of texts, graphs and oracle results, the engine opener, the stage-entry loop
-and the timing loop.  A plain module: tests/test_modelgen_{shapes,depths,big}.py show that the walk here equals the oracle's
+GPU test takes its expected values from, one cache of texts, graphs and oracle results, the engine opener, the hand-off routes
+onto a live engine, the stage-entry loop and the timing loop.  A plain module: tests/test_modelgen_{shapes,depths,big}.py show that the walk here equals the oracle's
 predict bit for bit, and so vouch for it in every file that imports it.
 
 A model is named by (family, member): family is "shapes", "depths" or "big" (tools/modelgen_shapes.py, _depths.py, _big.py), and
@@ -88,6 +88,21 @@ def oracle_of(family, name, g):
     return om
 
 
+def oracle_at(family, name, ws):
+    """The oracle's model of the member's text at the weight scale ws (oracle_of: at a graph's own)."""
+    om = oracle_py.OracleModel(text_of(family, name))
+    om.set_weight_scale(ws)
+    return om
+
+
+def logits_at(family, name, g, ws=None, x=None):
+    """The oracle's logits (n x out_width) for g from the member's model_input (or x) at the weight scale ws (default: g.ws): the
+    oracle's own predict up to the last linear layer — which tests/test_modelgen_{shapes,depths,big}.py show equal to the walk."""
+    om = oracle_at(family, name, g.ws if ws is None else ws)
+    x = FAMILIES[family].model_input(name, g) if x is None else x
+    return om.predict(g, x, stop_after=om.n_layers - 2)
+
+
 def oracle_stage(family, name, g, s, hin):
     """(output rows, pre-activation of the last linear layer) of stage s alone, from the input rows hin: the walk from stage s."""
     (_, h, pre), = _walk(oracle_of(family, name, g), family, name, g, np.ascontiguousarray(hin, dtype=np.float32), s, 1)
@@ -121,6 +136,7 @@ GRAPHS = {
     "sparse": lambda: gg.erdos_renyi(5000, 3000, 23),                     # about three rows in ten are empty
     "er1933": lambda: gg.erdos_renyi(1933, 7000, 61),                     # n = 30 * 64 + 13: no multiple of 64 or of 16
     "one": lambda: gg.from_edge_list(1, [], [57]),                        # n = 1
+    "empty": lambda: gg.from_edge_list(0, [], []),                        # n = 0: what the reference's driver hands over last
     "hub6k": lambda: gg.hub_graph(6000, 18000, 2, 3000, seed=9),          # two rows of 3000 entries: many gather rounds a row
     "hub8k": lambda: gg.hub_graph(8000, 24000, 2, 5000, seed=9),          # rows 0 and 1: about 5000 entries, 78 fetch batches of the audit
     "hub20k": lambda: gg.hub_graph(40000, 120000, 2, 20000, seed=9),      # two rows of 20000 entries (beyond 16384)
@@ -132,6 +148,15 @@ GRAPHS = {
 
 def degrees(g):
     return np.diff(g.rowptr.astype(np.int64))
+
+
+def heavy_counts(g, thr):
+    """(rows, their entries) of g with at least thr entries — what "generic_heavy_rows" / "generic_heavy_entries" read at the
+    threshold thr, and "generic_giant_rows" / "generic_giant_entries" at max(heavy, giant) — or (0, 0) for thr = 0 (none)."""
+    if not thr or g.n == 0:
+        return 0, 0
+    deg = degrees(g)
+    return int((deg >= thr).sum()), int(deg[deg >= thr].sum())
 
 
 def crafted_input(n, f, seed):
@@ -155,6 +180,30 @@ def graph_of(gname):
     if ("graph", gname) not in _cache:
         _cache["graph", gname] = GRAPHS[gname]()
     return _cache["graph", gname]
+
+
+# tests/test_gpu_generic_lifecycle.py's models and graphs, which tests/test_generic_lifecycle_inputs.py pins on the CPU: the members
+# handed every route (f = 1, 3, 5, 9 and 32, depths 1 to 5), the graphs one live engine is handed in turn (7 heavy rows, none,
+# 7, none ...), and the members whose graph is derived on the device
+LIFECYCLE_MEMBERS = [("shapes", "odd"), ("shapes", "in3"), ("depths", "mixed"), ("depths", "in3_f32")]
+LIFECYCLE_SEQUENCE = ["hubs", "er1933", "hubs", "one", "empty", "sparse", "hubs"]
+DERIVE_MEMBERS = [("shapes", "odd"), ("depths", "mixed")]
+DERIVE_STEPS = ((0.7, 50, 40), (0.5, 7, 300), (1.0, 0, 0))   # (share of vertices kept, new fold vertices, their fan)
+
+
+def derive_chain():
+    """[(g1, old_row)] per step of DERIVE_STEPS: "hubs" shrunk three times as the reference's driver shrinks its graph, by
+    tests/test_gpu_parity.py's own _shrunk_graph, rng and steps (test_graph_derived_on_the_device_equals_an_upload)."""
+    if "chain" not in _cache:
+        from tests.test_gpu_parity import _shrunk_graph
+        rng = np.random.default_rng(17)
+        g, out = graph_of("hubs"), []
+        for frac, nv, fan in DERIVE_STEPS:
+            g1, old_row = _shrunk_graph(g, rng, frac, nv, fan)
+            out.append((g1, old_row))
+            g = g1
+        _cache["chain"] = out
+    return _cache["chain"]
 
 
 def want_of(family, name, gname):
@@ -202,6 +251,33 @@ def open_engine(family, name, g, opts=(), heavy=None, giant=None, big=None, expe
         e.close()
         raise
     return e
+
+
+ROUTES = ["upload", "staged1", "staged7", "attach"]
+
+
+def hand_over(e, g, route):
+    """Make g the graph of the live engine e, with g's weight scale, by one of ROUTES: gnnvc_upload_graph, the staged hand-off
+    with the column array in 1 or 7 pieces, or gnnvc_attach_graph_device on device tensors (which the engine keeps alive).  The
+    attached column array carries its GNNVC_COL_PAD tail filled with the valid id n - 1 (0 where the graph has no vertex)."""
+    e.set_weight_scale(g.ws)
+    if route == "upload":
+        e.upload_graph(g)
+    elif route in ("staged1", "staged7"):
+        e.upload_graph_staged(g, pieces=int(route[len("staged"):]))
+    elif route == "attach":
+        import torch
+        from gnn_mwvc_amd.engine import COL_PAD
+        dev = torch.device("cuda:0")
+        col = np.full(g.nnz + COL_PAD, max(g.n - 1, 0), dtype=np.int64)
+        col[: g.nnz] = g.col
+        one = np.zeros(1, dtype=np.int64)   # (no vertex: one word each, never a null pointer)
+        arrays = (g.rowptr, col, g.w, g.nw) if g.n else (one, col, one, one)
+        t = [torch.from_numpy(np.asarray(a).astype(np.int64)).to(torch.int32).to(dev) for a in arrays]
+        torch.cuda.synchronize()
+        e.attach_graph_device(g.n, g.nnz, *[x.data_ptr() for x in t], keepalive=t)
+    else:
+        raise ValueError(route)
 
 
 def stage_buffers(family, name, gname, s, fill=float("nan")):
