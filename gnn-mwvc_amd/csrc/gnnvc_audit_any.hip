@@ -2,7 +2,8 @@
 // gnnvc_audit_stage_device).  It recomputes one stage — graph layer of input width f, d = 1 .. 6 dense layers of widths
 // n[0 .. d), ReLU | sigmoid — for rows [lo, hi) from the stage's own input and compares every value the fused path wrote: the
 // n[d - 1]-wide output row, or the scores and the logits on the sigmoid stage.  Bounds: whatever stage_any_fits admits (1 <= f <= 32,
-// every width but the last <= 64 — <= 128 in a big stage, gnnvc_set_generic_big_stages — the last <= 32).
+// every width but the last <= 64 — <= 128 in a big stage, gnnvc_set_generic_big_stages — the last <= 32; f and the last width up to
+// 64 under gnnvc_set_generic_feature_width).
 //
 // What is computed is the layer-by-layer kernels' arithmetic (k_graph_layer, k_linear, k_relu, k_sigmoid):
 //   neighbour-sum column c   one fp32 add chain in stored CSR order from +0.0f;
@@ -22,7 +23,7 @@
 //   and nothing copied to LDS;
 //   the row's activations live in two per-wave LDS vectors of 132 floats (static LDS, 4224 bytes a workgroup) that the layers
 //   ping-pong through; x[k] is one broadcast read;
-//   the graph row has K = 2 f + 3 <= 67 columns — more than a wave — so it is written by a loop over c = lane, lane + 64;
+//   the graph row has K = 2 f + 3 <= 131 columns — more than a wave — so it is written by a loop over c = lane, lane + 64, lane + 128;
 //   lanes c < f each run their column's add chain over the neighbours: the wave fetches 64 column ids at a time (the next 64
 //   already on their way), takes eight neighbours' rows per lane into registers, then adds them in order.  f = 1 has one
 //   column and so one chain: every lane fetches one neighbour's value, and the values are added in stored order through lane
@@ -34,7 +35,7 @@
 // one k_audit_stage writes): [0] the exact number of mismatching values, [1] NaN pairs, [2] repairs, and of the first
 // mismatching row its first mismatching value: [3] ~(row << 32 | column code), [4] ~(row << 32 | fused bits), [5] ~(row << 32 |
 // audit bits) — atomicMax of the complements; a row is checked by exactly one wave, which submits one triple, so the three
-// minima belong together.  Column code: the output column, + 64 for a logit (widths are at most 32).
+// minima belong together.  Column code: the output column, + 64 for a logit (widths are at most 64: the codes stay below 128).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,9 +58,11 @@ __device__ __forceinline__ void wave_handoff() {
 }
 
 constexpr int kBlockThreads = 256, kWaves = kBlockThreads / 64;
-constexpr int kVec = 132;   // floats per activation vector: the graph row's 2 * 32 + 3 = 67 columns, hidden widths up to 128
-static_assert(kVec >= 2 * kAnyMaxF + 3 && kVec >= kAnyBigHidden && kAnyBigHidden <= 2 * 64 && kAnyMaxLast <= 32,
-              "the vectors, the two outputs a lane owns and the column code are sized for what stage_any_route admits");
+constexpr int kVec = 132;   // floats per activation vector: the graph row's 2 * 64 + 3 = 131 columns, hidden widths up to 128
+// (f <= 64: a lane has at most ONE sum column, c == lane; a last layer of at most 64 outputs: one per lane, and a column code
+// below 64 with 64 left for the logits' flag)
+static_assert(kVec >= 2 * kAnyFeatMax + 3 && kVec >= kAnyBigHidden && kAnyBigHidden <= 2 * 64 && kAnyMaxLast <= kAnyFeatMax && kAnyFeatMax <= 64,
+              "the vectors, the one sum column and the two outputs a lane owns, and the column code are sized for what stage_any_route admits");
 
 struct AuditGraph {   // the graph as handed over
     const uint32_t *rowptr, *col, *w, *nw;
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_audit_any(AuditGraph g, float
         const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
         for (int c = lane; c < k1; c += 64) {
             float v = 0.0f;
-            if (c < (int)f) v = s;   // (f <= 32: c == lane here)
+            if (c < (int)f) v = s;   // (f <= 64: c == lane here)
             else if (c < 2 * (int)f) v = in[(size_t)u * f + (uint32_t)(c - (int)f)];
             if (c == (int)f + 1) v = deg;
             if (c == (int)f + 2) v = wv;

@@ -170,7 +170,7 @@ int plan_model(gnnvc_engine *e) {
 
 // generic stages (k_stage_any): (Graph, (Linear, activation){d})+ with 1 <= d <= kMaxDenseLayers, d free per stage, any widths
 // within stage_any_fits (which knows the LDS bounds too: the default one, and the opt-in one of gnnvc_set_generic_big_stages, which
-// each stage carries as big_lds); every activation a ReLU but the model's last, a sigmoid (a model that ends in a ReLU stays layer
+// each stage carries as big_lds, and the feature width of gnnvc_set_generic_feature_width, carried as feat_width); every activation a ReLU but the model's last, a sigmoid (a model that ends in a ReLU stays layer
 // by layer, as for the trained shapes).  One stage outside the bounds leaves the whole model layer by layer.  Derives e->gstages
 // anew from the layers (their parameter offsets are plan_model's): at model load, and when the opt-in's limit moves.
 void plan_generic(gnnvc_engine *e) {
@@ -202,6 +202,7 @@ void plan_generic(gnnvc_engine *e) {
         sp.n3 = sp.wn[sp.nd - 1];
         if (sp.nd == 3) { sp.n1 = sp.wn[0]; sp.n2 = sp.wn[1]; }
         sp.big_lds = e->big_lds;
+        sp.feat_width = e->feat_width;
         gok = gnnvc::stage_any_fits(sp);
         gs.push_back(sp);
         f = sp.n3;
@@ -990,6 +991,27 @@ int gnnvc_set_generic_big_stages(gnnvc_engine *e, uint32_t lds_bytes) {
     return GNNVC_OK;
 }
 
+int gnnvc_set_generic_feature_width(gnnvc_engine *e, uint32_t max_width) {
+    if (!e) return GNNVC_ERR_INVALID;
+    NOT_ON_MULTI(e, "gnnvc_set_generic_feature_width");
+    if (max_width != 0 && (max_width <= (uint32_t)gnnvc::kAnyMaxF || max_width > (uint32_t)gnnvc::kAnyFeatMax))
+        return fail(e, GNNVC_ERR_INVALID, "gnnvc_set_generic_feature_width: %u is neither 0 nor within %d .. %d", max_width,
+                    gnnvc::kAnyMaxF + 1, gnnvc::kAnyFeatMax);
+    if (max_width == e->feat_width) return GNNVC_OK;
+    if (max_width) {   // the feat instantiations' LDS limit on this device (a wide stage may be a big one too): refused here, never inside a forward
+        const int rc = use_device(e);
+        if (rc) return rc;
+        if (gnnvc::allow_feat_stages() != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e, GNNVC_ERR_UNSUPPORTED, "gnnvc_set_generic_feature_width: the runtime refuses k_stage_any 160 KiB of dynamic LDS on device %d", e->device);
+        }
+    }
+    e->feat_width = max_width;
+    plan_generic(e);                // (at once, as gnnvc_set_generic_big_stages)
+    e->pg.heavy_known = false;      // an attached graph is classed again by the next generic stage that runs (class_heavy_rows): hsum and the giant slab follow the widest f
+    return GNNVC_OK;
+}
+
 // "<prefix><s>" of a generic model: the stage index, or -1 (no such stage, not a number, the model is not generic)
 static long generic_stage_index(const gnnvc_engine *e, const std::string &k, size_t prefix_len) {
     const char *num = k.c_str() + prefix_len;
@@ -1033,6 +1055,7 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
         *value = e->gstages[(size_t)s].nd;
     }
     else if (k == "generic_big_lds") *value = (long)e->big_lds;                       // gnnvc_set_generic_big_stages, as set
+    else if (k == "generic_feature_width") *value = (long)e->feat_width;              // gnnvc_set_generic_feature_width, as set
     else if (k.rfind("generic_stage_lds_bytes_", 0) == 0) {   // "generic_stage_lds_bytes_<s>": the stage's LDS layout at 256 threads
         const long s = generic_stage_index(e, k, sizeof("generic_stage_lds_bytes_") - 1);
         if (s < 0) return GNNVC_ERR_INVALID;

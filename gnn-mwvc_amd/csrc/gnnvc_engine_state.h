@@ -64,6 +64,9 @@ struct gnnvc_engine {
     // gnnvc_set_generic_big_stages: 0 = off, else the LDS limit (65 536 .. 163 840 bytes) under which stages outside the default
     // bounds are admitted to gstages (gnnvc::stage_any_route; every plan in gstages carries the value it was derived under)
     uint32_t big_lds = 0;
+    // gnnvc_set_generic_feature_width: 0 = off, else what f and a stage's last width may be (33 .. 64) instead of 32; carried by
+    // every plan in gstages like big_lds
+    uint32_t feat_width = 0;
     bool generic_on() const { return !gstages.empty() && (opt.generic == 2 || (opt.generic == 1 && stages.empty())); }
     const std::vector<StagePlan> &stage_list() const { return generic_on() ? gstages : stages; }   // what the ABI reports and runs
     // Heavy rows of generic stages (gnnvc_set_generic_heavy_rows): rows of at least heavy_from entries (0: none) get a workgroup

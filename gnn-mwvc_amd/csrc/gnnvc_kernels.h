@@ -70,7 +70,7 @@ struct GraphDev {
 //   W1[K1 x N1] b1[N1] W2[N1 x N2] b2[N2] ... ,  K1 = 2F + 3.
 constexpr int kMaxDenseLayers = 6;
 struct StagePlan {
-    int f = 0;                // graph-layer input width: 1 or 16 (a generic stage: 1 .. 32)
+    int f = 0;                // graph-layer input width: 1 or 16 (a generic stage: 1 .. 32, on request up to 64)
     int n1 = 0, n2 = 0, n3 = 0;   // n3: the stage's output width (of its last dense layer, whatever their number); n1, n2: the
                                   // first two widths of a three-deep stage, 0 otherwise
     int sigmoid_last = 0;     // last activation is a sigmoid (else ReLU)
@@ -79,6 +79,7 @@ struct StagePlan {
     int nd = 3;               // dense layers
     int wn[kMaxDenseLayers] = {0, 0, 0, 0, 0, 0};   // their widths, wn[nd - 1] == n3 (filled for generic stages)
     uint32_t big_lds = 0;     // a generic stage: the LDS limit of gnnvc_set_generic_big_stages it was planned under (0 = off)
+    uint32_t feat_width = 0;  // a generic stage: the feature width of gnnvc_set_generic_feature_width it was planned under (0 = off)
     uint32_t skip_ok = 0;     // bit l set: dense layer l + 1 has finite weights only and no bias with the bits of -0.0f, so terms
                               // whose input is +-0 may be left out of its chains bit for bit (set at model load)
 };
@@ -204,12 +205,16 @@ hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 //   a BIG stage      sp.big_lds != 0 (gnnvc_set_generic_big_stages, 65 536 .. 163 840), not small, every width but the last <= 128,
 //                    the last <= 32, and the layout AT 256 THREADS within sp.big_lds: a big instantiation at 1024, 512 or 256
 //                    threads — the largest whose own layout (64 / 32 / 16 pairs of vectors) fits sp.big_lds;
+//   a FEAT stage     sp.feat_width in 33 .. 64 (gnnvc_set_generic_feature_width) raises the 32 of f and of the last width, in both
+//                    rules above, to that value; a stage that uses the allowance (f or its last width above 32) launches a FEAT
+//                    instantiation: at 256 threads when it is otherwise small, by the big rule when it is otherwise big;
 //   anything else    not admitted: the model runs layer by layer.
 // One launch per call; the graph's rowptr / col / w / nw only (no plan); rows of every degree.  in: (n + 1) x f rows (the pad row
 // is never read), out: rows [row_lo, row_hi) of an (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
 constexpr int kAnyMaxF = 32, kAnySmallHidden = 64, kAnyBigHidden = 128, kAnyMaxLast = 32;   // the widths stage_any_route admits
+constexpr int kAnyFeatMax = 64;   // ... and the most that f and the last width may be raised to (gnnvc_set_generic_feature_width)
 struct AnyRoute {
-    bool ok = false, big = false;
+    bool ok = false, big = false, feat = false;   // feat: f or the last width above 32 (a FEAT instantiation)
     int threads = 256;           // the workgroup size the launcher uses
     size_t lds256 = 0, lds = 0;  // the layout's bytes at 256 threads (what admits the stage), and at `threads` (what is launched)
 };
@@ -217,6 +222,7 @@ AnyRoute stage_any_route(const StagePlan &sp);
 bool stage_any_fits(const StagePlan &sp);
 // raises the big instantiations' dynamic-LDS limit on the current device (once per device); an error = the runtime refuses it
 hipError_t allow_big_stages();
+hipError_t allow_feat_stages();   // the same for the FEAT instantiations
 // kernels that need more than 64 KiB of dynamic LDS must be told so once per device (engines on several devices may live in one
 // process; `done` has one bit per device ordinal)
 hipError_t allow_dynamic_lds(const void *func, int bytes, std::atomic<uint64_t> &done);
@@ -306,7 +312,7 @@ hipError_t find_giant_rows(const GraphDev &g, const uint32_t *list, uint32_t n_l
 // everything behind it on another, hence the parts.
 enum class GiantPart { kAll, kGather, kAfterGather };
 hipError_t launch_giant_stage(const StageCall &c, const GiantRows &gr, uint32_t min_deg, GiantPart part);
-// the sums alone (k_giant_segsum, k_giant_segmap, k_giant_sum), F streams per row (1 <= F <= 32), agg: float[n x F]
+// the sums alone (k_giant_segsum, k_giant_segmap, k_giant_sum), F streams per row (1 <= F <= 64), agg: float[n x F]
 hipError_t launch_giant_sums(const GiantRows &gr, uint32_t F, uint32_t row_lo, uint32_t row_hi, hipStream_t stream);
 
 // Giant rows of a GENERIC stage (gnnvc_set_generic_giant_rows; gnnvc_stage_any.hip): the listed heavy rows of at least the giant

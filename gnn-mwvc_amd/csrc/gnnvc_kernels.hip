@@ -5650,7 +5650,7 @@ hipError_t stream_sums(const float *streams_dev, uint32_t streams, uint32_t len,
 // the dense layers): F streams per row at slab + off[i] + c * lpad, agg[i * F + c]; no pruned adjacency, rows of every degree
 hipError_t launch_giant_sums(const GiantRows &gr, uint32_t F, uint32_t row_lo, uint32_t row_hi, hipStream_t stream) {
     if (gr.n == 0 || row_hi <= row_lo) return hipSuccess;
-    if (F < 1 || F > 32 || !gr.meta || !gr.off || !gr.slab || !gr.agg) return hipErrorInvalidValue;
+    if (F < 1 || F > (uint32_t)kAnyFeatMax || !gr.meta || !gr.off || !gr.slab || !gr.agg) return hipErrorInvalidValue;   // (F: index arithmetic only)
     const uint4 *meta = reinterpret_cast<const uint4 *>(gr.meta);
     const uint32_t *none = nullptr;
     const bool seg = gr.segsum && gr.segmap && gr.maxseg > 1;

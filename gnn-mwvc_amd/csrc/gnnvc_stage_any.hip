@@ -12,11 +12,13 @@
 //   relu_ref, or sigmoid_ref on the last layer of the last stage (the logits are its input).
 // Compile with -ffp-contract=off, like the rest of the library.
 //
-// Bounds (stage_any_route, which stage_any_fits asks): 1 <= f <= 32, 1 <= d <= 6 dense layers, every width but the last 1 .. 64, the
+// Bounds (stage_any_route, which stage_any_fits asks), by default: 1 <= f <= 32, 1 <= d <= 6 dense layers, every width but the last 1 .. 64, the
 // last 1 .. 32, and the LDS layout below within 64 KiB (the dynamic LDS a launch gets without raising the kernel's limit).  A
 // stage within these launches the kernel's default instantiations, whatever else is set.  With gnnvc_set_generic_big_stages a
 // stage outside them is admitted when its hidden widths are at most 128 and its layout at 256 threads fits the limit given (at
-// most 160 KiB, a CU's LDS): it launches a BIG instantiation (below), whose limit allow_big_stages has raised.
+// most 160 KiB, a CU's LDS): it launches a BIG instantiation (below), whose limit allow_big_stages has raised.  With
+// gnnvc_set_generic_feature_width f and the last width may be up to the width given (33 .. 64): a stage that uses the allowance
+// launches a FEAT instantiation (below), and must still fit the LDS and hidden-width bounds, default or big, like any other.
 //
 // Shape of the kernel: 256-thread workgroups walk the row range 16 rows at a time (grid-stride; no workgroup barrier inside
 // the walk, so a wave that sits on a very long row holds up nobody else).  Each workgroup first transposes the stage's
@@ -221,6 +223,41 @@ __device__ __forceinline__ void any_gather(const uint32_t *__restrict__ col, con
     }
 }
 
+// The same sums for 32 < f <= 64 (the FEAT instantiations): lane j owns columns j + 16 t, t < NC = ceil(f / 16) = 3 or 4, one chain
+// each in s[t].  The group fetches 16 column ids at a time, the next 16 already on their way, and takes them in two rounds of 8
+// entries: 8 NC row loads per lane in flight (24 or 32), then their adds in stored order.  A round behind the row's end is not
+// issued; within a round, slots behind the end load row 0 and lanes without a column their last one, and neither is added.
+template <int NC>
+__device__ __forceinline__ void any_gather_n(const uint32_t *__restrict__ col, const float *__restrict__ in, uint32_t rs, uint32_t re,
+                                             uint32_t f, int j, int gbase, float (&s)[4]) {
+    uint32_t ct[NC];
+#pragma unroll
+    for (int t = 0; t < NC; ++t) ct[t] = min((uint32_t)j + 16u * t, f - 1u);
+    uint32_t cn = (rs + j < re) ? col[rs + j] : 0u;
+    for (uint32_t e = rs; e < re; e += 16u) {
+        const uint32_t m = min(16u, re - e);
+        const uint32_t cc = cn;
+        cn = (e + 16u + j < re) ? col[e + 16u + j] : 0u;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if ((uint32_t)(8 * h) >= m) break;   // (uniform over the group, whose lanes are all the shuffles below read)
+            float v[8][NC];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const size_t row = (size_t)(uint32_t)__shfl((int)cc, gbase + 8 * h + i) * f;
+#pragma unroll
+                for (int t = 0; t < NC; ++t) v[i][t] = in[row + ct[t]];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if ((uint32_t)(8 * h + i) < m) {
+#pragma unroll
+                    for (int t = 0; t < NC; ++t) s[t] = s[t] + v[i][t];
+                }
+        }
+    }
+}
+
 // f = 1: every lane fetches one neighbour's value per chunk of 16 (four chunks a round), and all lanes of the group add the
 // values in the same — stored — order
 __device__ __forceinline__ float any_gather1(const uint32_t *__restrict__ col, const float *__restrict__ in, uint32_t rs, uint32_t re,
@@ -269,7 +306,13 @@ struct AnyRowSel {
 // the LDS reads of the dense layers with), and hidden layers of up to 128 outputs, taken 64 outputs at a time — the chains of
 // different outputs are independent, so a layer's second half is the first half's code on the next 64 transposed rows.  The
 // defaults are the kernel as it was.
-template <int MODE, int BLOCK = kAnyBlock, bool BIG = false>
+//
+// The FEAT form (gnnvc_set_generic_feature_width; FEAT = true, on top of BIG = true) is the same source again for stages whose f
+// or last width lies in 33 .. 64: a lane owns up to four sum columns (any_gather_n above; the listed rows read four sums from
+// hsum) and up to four outputs of the last layer.  Everything it adds sits behind `if constexpr (FEAT)`, so the other twelve
+// instantiations compile to what they compiled to.  A FEAT stage within the default LDS and hidden-width bounds launches the
+// 256-thread form; one outside them needs big stages too and follows their rule for 1024 / 512 / 256 threads.
+template <int MODE, int BLOCK = kAnyBlock, bool BIG = false, bool FEAT = false>
 __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
                                                         float *__restrict__ out, float *__restrict__ logits, uint32_t lo, uint32_t hi,
                                                         AnyShape S, int sig, AnyRowSel R) {
@@ -312,10 +355,25 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
         const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
         if (MODE == kAnyLight && re - rs >= R.from) continue;   // a heavy row: the listed-rows launch has it
         float s0 = 0.0f, s1 = 0.0f;
+        [[maybe_unused]] float s2 = 0.0f, s3 = 0.0f;   // (FEAT: columns j + 32, j + 48)
         if (listed) {
             const float *hs = R.hsum + (size_t)u64 * (uint32_t)f;
             s0 = hs[min(j, f - 1)];
             s1 = hs[min(j + 16, f - 1)];
+            if constexpr (FEAT) {
+                s2 = hs[min(j + 32, f - 1)];
+                s3 = hs[min(j + 48, f - 1)];
+            }
+        } else if (FEAT && f > 32) {
+            if constexpr (FEAT) {
+                float sn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (f <= 48) any_gather_n<3>(g.col, in, rs, re, (uint32_t)f, j, gbase, sn);
+                else any_gather_n<4>(g.col, in, rs, re, (uint32_t)f, j, gbase, sn);
+                s0 = sn[0];
+                s1 = sn[1];
+                s2 = sn[2];
+                s3 = sn[3];
+            }
         } else if (f == 1) {
             s0 = any_gather1(g.col, in, rs, re, j, gbase);
         } else if (f <= 16) {
@@ -326,7 +384,7 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
         const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
         for (int c = j; c < k1; c += 16) {
             float v = 0.0f;
-            if (c < f) v = c < 16 ? s0 : s1;
+            if (c < f) v = c < 16 ? s0 : (!FEAT || c < 32) ? s1 : (c < 48 ? s2 : s3);
             else if (c < 2 * f) v = in[(size_t)u * (uint32_t)f + (uint32_t)(c - f)];
             if (c == f + 1) v = deg;
             if (c == f + 2) v = wv;
@@ -358,21 +416,25 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
         float *out_row = out + (size_t)u * (uint32_t)n_out;
         float *logit_row = logits ? logits + (size_t)u * (uint32_t)n_out : nullptr;   // (null unless this is the sigmoid stage)
         if (n_out <= 16) any_last<1>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
-        else any_last<2>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        else if (!FEAT || n_out <= 32) any_last<2>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        else if (n_out <= 48) any_last<3>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        else any_last<4>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
         wave_lds_sync();   // (the group's LDS is rewritten by its next row)
     }
 }
 
 // ---- heavy rows: the neighbour sums of ONE listed row by a whole workgroup (the structure of k_long_f1 / k_long_f16 in
-// gnnvc_kernels.hip, for any 1 <= f <= 32; nothing is shared with them or with k_audit_any).  Sums only: the row build, the dense
+// gnnvc_kernels.hip, for any 1 <= f <= 64; nothing is shared with them or with k_audit_any).  Sums only: the row build, the dense
 // layers and the stores stay k_stage_any's (kAnyListed).
 //
 // The 256 threads form groups of G = 2^gs >= f lanes, a group per neighbour: lane c of a group fetches column c of its
 // neighbour's row (lanes c >= f have no column: they fetch column f - 1 and write nothing).  A pass covers 256 / G neighbours, a
 // chunk is R passes — R values per thread in registers — so a chunk is CH = 256 R / G neighbours: 1024 for f <= 4 (R = 4, 8, 16 for
-// G = 1, 2, 4), 512 for f <= 8, 256 for f <= 16, 128 above (R = 16).  The slab is column-major, f runs of CH + 4 floats (the pad of
+// G = 1, 2, 4), 512 for f <= 8, 256 for f <= 16, 128 for f <= 32, 64 above (R = 16; G = 64 is a whole wave, four neighbours a
+// pass).  The slab is column-major, f runs of CH + 4 floats (the pad of
 // four keeps every column 16-byte aligned and puts the adder lanes' 16-byte reads on different banks); two slabs alternate:
-// heavy_lds_bytes(f), at most 33 792 bytes (f = 32) — four workgroups a CU by LDS, and the 64 KiB limit is not raised.
+// heavy_lds_bytes(f), at most 34 816 bytes (f = 64; 33 792 at f = 32) — four workgroups a CU by LDS, and the 64 KiB limit is not
+// raised.
 // While lane c < f of the first wave adds column c of chunk r in stored order (sixteen 16-byte LDS reads ahead of their 64
 // adds), the values of chunk r + 1 and the column ids of chunk r + 2 are in flight.  Every fetch is unconditional: entries past
 // the row's end clamp to its last entry — a real neighbour, never a pad row of `in` — and what they fetch is written to the slab
@@ -478,7 +540,9 @@ __global__ __launch_bounds__(kHeavyBlock) void k_any_heavy_sums(const uint32_t *
 // passes: lane c < f of a group fetches float c of its entry's neighbour row (4-byte loads: f need not be a multiple of 4), all G
 // fetches of a thread in flight at once.  Entries past the row's end clamp to its last entry for the fetch — a real neighbour,
 // never a pad row — and are stored as +0.0f.  The values cross an LDS tile [f][256 + 4] (at most 33 280 bytes, f = 32) and leave
-// with 16-byte stores, 1 KiB per stream and workgroup.
+// with 16-byte stores, 1 KiB per stream and workgroup.  A launch takes the columns c0 .. c0 + min(f - c0, G) of the rows: all of
+// them (c0 = 0) for f <= 32, and a row wider than that in two launches of at most 32 columns each, so that GS stays at most 5
+// (32 fetches a thread) and the tile within 33 280 bytes.
 constexpr int kAnyGiantBlk = 256, kAnyGiantPitch = kAnyGiantBlk + 4;
 
 // meta[i] = {row, first entry, degree, first gather block}, meta[n_giant].w = the number of gather blocks
@@ -504,7 +568,7 @@ template <int GS>
 __global__ __launch_bounds__(kAnyGiantBlk) void k_any_giant_gather(const uint32_t *__restrict__ col, const float *__restrict__ in,
                                                                   float *__restrict__ slab, const uint4 *__restrict__ meta,
                                                                   const unsigned long long *__restrict__ off, uint32_t n_giant, uint32_t f,
-                                                                  uint32_t win, uint32_t lo, uint32_t hi) {
+                                                                  uint32_t win, uint32_t lo, uint32_t hi, uint32_t c0) {
     extern __shared__ float4 giant_lds4[];
     float *tile = reinterpret_cast<float *>(giant_lds4);
     constexpr uint32_t G = 1u << GS, per = (uint32_t)kAnyGiantBlk >> GS;
@@ -517,8 +581,9 @@ __global__ __launch_bounds__(kAnyGiantBlk) void k_any_giant_gather(const uint32_
     const uint32_t lpad = (deg + win - 1u) / win * win;
     if (j0 >= lpad) return;                // (block-uniform; the host lays out exactly lpad / 256 blocks a row)
     const uint32_t tid = threadIdx.x, k0 = tid >> GS, c = tid & (G - 1u);
-    const bool has = c < f;
-    const uint32_t cc = has ? c : f - 1u;
+    const uint32_t fw = min(f - c0, G);    // this launch's columns: c0 .. c0 + fw
+    const bool has = c < fw;
+    const uint32_t cc = c0 + (has ? c : fw - 1u);
     uint32_t idx[G];
     float v[G];
 #pragma unroll
@@ -536,8 +601,8 @@ __global__ __launch_bounds__(kAnyGiantBlk) void k_any_giant_gather(const uint32_
         }
     }
     __syncthreads();
-    float *dst = slab + off[i] + j0;       // (16-byte aligned: off[i], lpad and j0 are multiples of 256 floats)
-    for (uint32_t q = tid; q < f * (uint32_t)(kAnyGiantBlk / 4); q += (uint32_t)kAnyGiantBlk) {
+    float *dst = slab + off[i] + (size_t)c0 * lpad + j0;   // (16-byte aligned: off[i], lpad and j0 are multiples of 256 floats)
+    for (uint32_t q = tid; q < fw * (uint32_t)(kAnyGiantBlk / 4); q += (uint32_t)kAnyGiantBlk) {
         const uint32_t cq = q >> 6, k4 = (q & 63u) * 4u;
         *reinterpret_cast<any_f32x4 *>(dst + (size_t)cq * lpad + k4) = *reinterpret_cast<const any_f32x4 *>(&tile[cq * (uint32_t)kAnyGiantPitch + k4]);
     }
@@ -580,13 +645,17 @@ static int forced_big_threads() {
 // audit's launcher all ask it, through stage_any_fits where a yes / no is enough).
 AnyRoute stage_any_route(const StagePlan &sp) {
     AnyRoute r;
-    if (sp.f < 1 || sp.f > kAnyMaxF || sp.nd < 1 || sp.nd > kMaxDenseLayers) return r;
+    // the feature width in force (gnnvc_set_generic_feature_width): what f and the last width may be
+    const int fw = sp.feat_width > (uint32_t)kAnyMaxF && sp.feat_width <= (uint32_t)kAnyFeatMax ? (int)sp.feat_width : kAnyMaxF;
+    static_assert(kAnyMaxF == kAnyMaxLast, "one allowance covers both");
+    if (sp.f < 1 || sp.f > fw || sp.nd < 1 || sp.nd > kMaxDenseLayers) return r;
     bool small = true;   // the default bounds: the kernel as it always was
     for (int l = 0; l < sp.nd; ++l) {
         const bool last = l + 1 == sp.nd;
-        if (sp.wn[l] < 1 || sp.wn[l] > (last ? kAnyMaxLast : kAnyBigHidden)) return r;
+        if (sp.wn[l] < 1 || sp.wn[l] > (last ? fw : kAnyBigHidden)) return r;
         if (!last && sp.wn[l] > kAnySmallHidden) small = false;
     }
+    r.feat = sp.f > kAnyMaxF || sp.wn[sp.nd - 1] > kAnyMaxLast;   // (uses the allowance: a FEAT instantiation)
     const AnyShape S = any_shape(sp);
     r.lds256 = (size_t)stage_any_layout(S, kAnyRows).total * sizeof(float);
     if (small && r.lds256 <= kAnyLdsBytes) {
@@ -644,7 +713,12 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
         c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0, sel
 #define GNNVC_ANY_LAUNCH(MODE_)                                                             \
     do {                                                                                    \
-        if (!route.big) hipLaunchKernelGGL((k_stage_any<MODE_>), GNNVC_ANY_ARGS);           \
+        if (route.feat) {   /* (also within the default LDS bound: the 256-thread form) */  \
+            if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, true>), GNNVC_ANY_ARGS);     \
+            else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, true>), GNNVC_ANY_ARGS);  \
+            else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, true>), GNNVC_ANY_ARGS); \
+        }                                                                                   \
+        else if (!route.big) hipLaunchKernelGGL((k_stage_any<MODE_>), GNNVC_ANY_ARGS);      \
         else if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true>), GNNVC_ANY_ARGS); \
         else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true>), GNNVC_ANY_ARGS);   \
         else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true>), GNNVC_ANY_ARGS);           \
@@ -660,14 +734,16 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
 }
 
 // the big instantiations take more than 64 KiB of dynamic LDS: told to the runtime once per device and instantiation
-// (allow_dynamic_lds of gnnvc_kernels.hip), by gnnvc_set_generic_big_stages — a refusal surfaces there, never inside a forward
-hipError_t allow_big_stages() {
+// (allow_dynamic_lds of gnnvc_kernels.hip), by gnnvc_set_generic_big_stages — a refusal surfaces there, never inside a forward.
+// The FEAT instantiations likewise (a wide stage may be a big one too), by gnnvc_set_generic_feature_width.
+template <bool FEAT>
+static hipError_t allow_stage_forms() {
     static std::atomic<uint64_t> done[9];
     hipError_t rc = hipSuccess;
     int i = 0;
 #define GNNVC_ANY_ALLOW(MODE_, BLOCK_)                                                                                                  \
     if (rc == hipSuccess)                                                                                                               \
-        rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_stage_any<MODE_, BLOCK_, true>), (int)kAnyBigLdsBytes, done[i]);        \
+        rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_stage_any<MODE_, BLOCK_, true, FEAT>), (int)kAnyBigLdsBytes, done[i]);  \
     ++i
 #define GNNVC_ANY_ALLOW3(MODE_) GNNVC_ANY_ALLOW(MODE_, 256); GNNVC_ANY_ALLOW(MODE_, 512); GNNVC_ANY_ALLOW(MODE_, 1024)
     GNNVC_ANY_ALLOW3(kAnyAll);
@@ -677,14 +753,16 @@ hipError_t allow_big_stages() {
 #undef GNNVC_ANY_ALLOW
     return rc;
 }
+hipError_t allow_big_stages() { return allow_stage_forms<false>(); }
+hipError_t allow_feat_stages() { return allow_stage_forms<true>(); }
 
 hipError_t launch_any_heavy_sums(const StageCall &c, const AnyHeavyRows &hr) {
     if (c.row_hi <= c.row_lo || hr.n == 0) return hipSuccess;
     const StagePlan &sp = *c.sp;
     const GraphDev &g = *c.g;
-    if (sp.f < 1 || sp.f > 32 || !hr.list || !hr.hsum || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
-    const int gs = heavy_shift(sp.f);
-    const size_t lds = heavy_lds_bytes(sp.f);   // <= 33 792 bytes
+    if (sp.f < 1 || sp.f > kAnyFeatMax || !hr.list || !hr.hsum || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
+    const int gs = heavy_shift(sp.f);           // <= 6: a group is at most a wave, and the adders are lanes of the first wave
+    const size_t lds = heavy_lds_bytes(sp.f);   // <= 34 816 bytes (f = 64)
     const dim3 grid(hr.n), block(kHeavyBlock);
 #define GNNVC_HEAVY_LAUNCH(R_)                                                                                            \
     hipLaunchKernelGGL((k_any_heavy_sums<R_>), grid, block, lds, c.stream, g.rowptr, g.col, c.in, hr.list, hr.hsum, \
@@ -712,7 +790,7 @@ hipError_t launch_any_giant(const StageCall &c, const AnyGiantRows &ar, float *h
     if (c.row_hi <= c.row_lo || gr.n == 0) return hipSuccess;
     const StagePlan &sp = *c.sp;
     const GraphDev &g = *c.g;
-    if (sp.f < 1 || sp.f > 32 || !gr.meta || !gr.off || !gr.slab || !gr.agg || !ar.pos || !hsum || c.row_hi > g.hi() || c.row_lo < g.lo())
+    if (sp.f < 1 || sp.f > kAnyFeatMax || !gr.meta || !gr.off || !gr.slab || !gr.agg || !ar.pos || !hsum || c.row_hi > g.hi() || c.row_lo < g.lo())
         return hipErrorInvalidValue;
     const uint4 *meta = reinterpret_cast<const uint4 *>(gr.meta);
     const uint32_t f = (uint32_t)sp.f;
@@ -724,21 +802,26 @@ hipError_t launch_any_giant(const StageCall &c, const AnyGiantRows &ar, float *h
     }
     const uint32_t win = giant_window();
     if (giant_block() != (uint32_t)kAnyGiantBlk || win % (uint32_t)kAnyGiantBlk != 0 || gr.blocks == 0) return hipErrorInvalidValue;
-    const size_t lds = (size_t)f * kAnyGiantPitch * sizeof(float);   // <= 33 280 bytes
     const dim3 grid(gr.blocks), block(kAnyGiantBlk);
 #define GNNVC_GIANT_GATHER(GS_)                                                                                              \
     hipLaunchKernelGGL((k_any_giant_gather<GS_>), grid, block, lds, c.stream, g.col, c.in, gr.slab, meta, gr.off, gr.n, f, win, \
-                       c.row_lo, c.row_hi)
-    switch (heavy_shift(sp.f)) {
-    case 0: GNNVC_GIANT_GATHER(0); break;
-    case 1: GNNVC_GIANT_GATHER(1); break;
-    case 2: GNNVC_GIANT_GATHER(2); break;
-    case 3: GNNVC_GIANT_GATHER(3); break;
-    case 4: GNNVC_GIANT_GATHER(4); break;
-    default: GNNVC_GIANT_GATHER(5); break;
+                       c.row_lo, c.row_hi, c0)
+    for (uint32_t c0 = 0; c0 < f; c0 += 32u) {   // (one launch for f <= 32; the columns from 32 on in a second)
+        const uint32_t fw = std::min(f - c0, 32u);
+        const size_t lds = (size_t)fw * kAnyGiantPitch * sizeof(float);   // <= 33 280 bytes
+        switch (heavy_shift((int)fw)) {
+        case 0: GNNVC_GIANT_GATHER(0); break;
+        case 1: GNNVC_GIANT_GATHER(1); break;
+        case 2: GNNVC_GIANT_GATHER(2); break;
+        case 3: GNNVC_GIANT_GATHER(3); break;
+        case 4: GNNVC_GIANT_GATHER(4); break;
+        default: GNNVC_GIANT_GATHER(5); break;
+        }
+        const hipError_t rc = hipGetLastError();
+        if (rc != hipSuccess) return rc;
     }
 #undef GNNVC_GIANT_GATHER
-    return hipGetLastError();
+    return hipSuccess;
 }
 
 }  // namespace gnnvc

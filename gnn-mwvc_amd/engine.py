@@ -22,7 +22,7 @@ _LIB = pathlib.Path(os.environ["GNNVC_LIBRARY"]).resolve() if os.environ.get("GN
 ABI_SYMBOLS = [
     "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_destroy",
     "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_set_generic_heavy_rows",
-    "gnnvc_set_generic_giant_rows", "gnnvc_set_generic_big_stages",
+    "gnnvc_set_generic_giant_rows", "gnnvc_set_generic_big_stages", "gnnvc_set_generic_feature_width",
     "gnnvc_num_layers", "gnnvc_is_fused",
     "gnnvc_in_width", "gnnvc_out_width", "gnnvc_upload_graph", "gnnvc_attach_graph_device", "gnnvc_attach_graph_slice",
     "gnnvc_graph_staging", "gnnvc_staged_columns_ready", "gnnvc_commit_staged_graph",
@@ -108,6 +108,7 @@ def load_library():
     L.gnnvc_set_generic_heavy_rows.argtypes = [vp, u32]
     L.gnnvc_set_generic_giant_rows.argtypes = [vp, u32, C.c_int]
     L.gnnvc_set_generic_big_stages.argtypes = [vp, u32]
+    L.gnnvc_set_generic_feature_width.argtypes = [vp, u32]
     for name in ("gnnvc_num_layers", "gnnvc_is_fused", "gnnvc_in_width", "gnnvc_out_width",
                  "gnnvc_num_stages", "gnnvc_synchronize"):
         getattr(L, name).argtypes = [vp]
@@ -254,6 +255,14 @@ class Engine:
         limit, -1 for any other value.  get_info: "generic_big_lds", "generic_stage_lds_bytes_<s>",
         "generic_stage_threads_<s>"."""
         self._check(self._L.gnnvc_set_generic_big_stages(self._h, lds_bytes))
+
+    def set_generic_feature_width(self, max_width: int):
+        """Opt-in: generic stages whose feature width f and whose last layer are at most `max_width` (33 .. 64) instead of 32 are
+        fused too (gnnvc_set_generic_feature_width), the model's input and output widths included; 0 = off, the default.
+        Independent of set_generic_big_stages: such a stage must still fit the LDS and hidden-width bounds in force.  Takes
+        effect at once: fused, num_stages and stage_widths follow.  Same bits for every value.  Raises GnnvcError -1 for any
+        other value, -5 on a multi-device handle.  get_info: "generic_feature_width"."""
+        self._check(self._L.gnnvc_set_generic_feature_width(self._h, max_width))
 
     def audit_report(self) -> dict:
         """The on-device audit's counters and its last failure (option "audit_period"), key -> value."""

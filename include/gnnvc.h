@@ -307,7 +307,8 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         "generic_giant_last_rows", "generic_giant_last_segmented").  The bounds above are the default ones:
  *                         gnnvc_set_generic_big_stages (below) admits, on request, stages with hidden widths up to 128 and
  *                         up to 160 KiB of LDS (keys "generic_big_lds", "generic_stage_lds_bytes_<s>",
- *                         "generic_stage_threads_<s>").  "audit_period" audits nothing on
+ *                         "generic_stage_threads_<s>"), and gnnvc_set_generic_feature_width (below) input and last widths up
+ *                         to 64 (key "generic_feature_width").  "audit_period" audits nothing on
  *                         them, as on an unfused model: they are audited on demand, by gnnvc_forward_audited,
  *                         gnnvc_forward_audited_device and gnnvc_audit_stage_device (kernel k_audit_any: a wave per row, the
  *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
@@ -351,7 +352,8 @@ int gnnvc_set_generic_heavy_rows(gnnvc_engine *e, uint32_t from_degree);
 
 /* Giant rows of generic stages.  k_any_heavy_sums adds a listed row with one fp32 chain per column, about 4 ns a neighbour: a hub
  * of several hundred thousand entries holds every stage for milliseconds.  Listed rows of at least from_degree entries therefore
- * take the route the trained model's giant rows take, for any stage input width 1 <= f <= 32: k_any_giant_gather (a 256-thread
+ * take the route the trained model's giant rows take, for any stage input width f (1 .. 32; up to 64 under
+ * gnnvc_set_generic_feature_width, a row's columns then in two launches): k_any_giant_gather (a 256-thread
  * workgroup per 256 entries) writes the row's neighbour values column-major into a slab of the engine's own, one stream of
  * floats per column in stored order; k_giant_sum — behind k_giant_segsum and k_giant_segmap when a stream is spread over several
  * waves — evaluates each stream's sequential fp32 sum with the exact parallel scan (bit for bit the chain's result, for any
@@ -390,7 +392,7 @@ int gnnvc_set_generic_giant_rows(gnnvc_engine *e, uint32_t from_degree, int segm
  * The call takes effect at once, as option "generic_stages" does: the generic stage list is derived anew, and with it
  * gnnvc_is_fused, gnnvc_num_stages, gnnvc_stage_widths and "generic_stage_layers_<s>"; an attached graph's heavy and giant rows
  * are classed again by the next generic stage that runs.  A model that is still not admitted (a wider layer, a larger layout,
- * f or a last width above 32) keeps running layer by layer.  The kernels' raised LDS limit is set here, once per device: if the
+ * f or a last width above 32 — see gnnvc_set_generic_feature_width below) keeps running layer by layer.  The kernels' raised LDS limit is set here, once per device: if the
  * runtime refuses it the call returns GNNVC_ERR_UNSUPPORTED and the engine stays as it was — never a forward.  A multi-device
  * handle: GNNVC_ERR_UNSUPPORTED; a null engine: GNNVC_ERR_INVALID.
  * gnnvc_get_info: "generic_big_lds" (the value as set, 0 when off), "generic_stage_lds_bytes_<s>" (the LDS layout of stage s at 256
@@ -398,6 +400,29 @@ int gnnvc_set_generic_giant_rows(gnnvc_engine *e, uint32_t from_degree, int segm
  * within the default bounds); both per-stage keys follow "generic_stage_layers_<s>": GNNVC_ERR_INVALID for a stage that does
  * not exist or while the model is not generic. */
 int gnnvc_set_generic_big_stages(gnnvc_engine *e, uint32_t lds_bytes);
+
+/* Feature rows of generic models up to 64 wide (opt-in).  By default a generic stage is fused only if its feature width f — the
+ * model's input width, and for later stages the previous stage's last layer — and its own last layer are at most 32: a model that
+ * hands 48- or 64-wide rows from one graph layer to the next runs one launch per layer.  This call raises both bounds.
+ *   max_width 0           off (the default): the bounds are 32 and the engine behaves exactly as if this call did not exist;
+ *   max_width 33 .. 64    on: a generic stage is admitted if 1 <= f <= max_width and its last width is <= max_width — the model's
+ *                         input width (stage 0's f) and its output width included — and it fits every other bound as before;
+ *   anything else         GNNVC_ERR_INVALID, the engine unchanged.
+ * The call is independent of gnnvc_set_generic_big_stages: an admitted stage must still fit the LDS and hidden-width bounds, the
+ * default ones (64 KiB, hidden widths <= 64) or those that call allows; a stage with f = 64 and a 128-wide hidden layer needs both.
+ * A stage whose f and last width are at most 32 launches exactly the kernels it always did.  A stage that uses the allowance
+ * launches a "feat" instantiation of the same kernel source, in which a lane owns up to four neighbour-sum columns and up to four
+ * outputs of the last layer: at 256 threads when the stage is within the default LDS and hidden-width bounds, else at the big
+ * rule's 1024, 512 or 256.  Heavy rows (k_any_heavy_sums: groups of 64 lanes), giant rows (k_any_giant_gather: a row's columns in
+ * two launches of at most 32), gnnvc_stage_forward_device and the explicit audit calls (k_audit_any) serve such a stage as they
+ * serve any generic stage.  Results are bit-identical to the layer-by-layer forward for every value.
+ * The call takes effect at once: the generic stage list is derived anew, and with it gnnvc_is_fused, gnnvc_num_stages,
+ * gnnvc_stage_widths and "generic_stage_layers_<s>"; an attached graph's heavy and giant rows are classed again by the next generic
+ * stage that runs (their buffers are sized by the widest f).  The kernels' raised LDS limit is set here, once per device: if the
+ * runtime refuses it the call returns GNNVC_ERR_UNSUPPORTED and the engine stays as it was.  A multi-device handle:
+ * GNNVC_ERR_UNSUPPORTED; a null engine: GNNVC_ERR_INVALID.
+ * gnnvc_get_info: "generic_feature_width" (the value in force, 0 when off). */
+int gnnvc_set_generic_feature_width(gnnvc_engine *e, uint32_t max_width);
 
 /* Model introspection (what model::layers holds). */
 int gnnvc_num_layers(const gnnvc_engine *e);

@@ -1,6 +1,6 @@
 """The one implementation behind the synthetic-model families of the generic fused stage (k_stage_any): tools/modelgen_shapes.py
-(other widths), tools/modelgen_depths.py (other depths) and tools/modelgen_big.py (stages outside the default bounds).  Those
-three modules hold their tables of members; everything that turns a table into model texts, weights and inputs is here, once.
+(other widths), tools/modelgen_depths.py (other depths), tools/modelgen_big.py (stages outside the default LDS and hidden-width
+bounds) and tools/modelgen_feat.py (feature widths above 32).  Those modules hold their tables of members; everything that turns a table into model texts, weights and inputs is here, once.
 
 A family is data: SPECS (name -> (input width, [layer widths per stage])), the tag that opens its rng seed list, how a member's
 index in that list is taken (`sorted` or `list`, over SPECS), the prefix of the text's first line, and optionally SEEDS
