@@ -420,10 +420,17 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     gnnvc::StageCall plain = call;
     plain.g = &e->g;
     gnnvc::EmitArgs emit;
-    // (the counters are zeroed only AFTER this stage's own k_c4_choose has read what the previous stage kernel left in them)
+    // (the counters are zeroed only AFTER this stage's own k_c4_choose has read what the previous stage kernel left in them: by
+    // that kernel itself where it read them — c4_emit_zero says whether the last thing queued on them was such a launch — and
+    // by a memset here otherwise)
     auto arm_emit = [&]() -> int {
         if (!c.emit) return GNNVC_OK;
-        HIP_TRY(e, hipMemsetAsync(e->c4_emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
+        const bool zero = e->c4_emit_zero;
+        e->c4_emit_zero = false;   // (the kernel armed here counts into them)
+        if (!zero) {
+            ++e->plan_memsets;
+            HIP_TRY(e, hipMemsetAsync(e->c4_emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
+        }
         emit.spec = e->c4_desc.p + gnnvc_engine::kDescWords * stage;   // consumer stage `stage + 1`: its descriptor words
         emit.table = e->c4_table.p;
         emit.counts = e->c4_emit_counts.p;
@@ -442,6 +449,8 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         const uint32_t rows = std::min(e->opt.pilot_rows, hi - lo);
         if ((uint64_t)rows * 8 > (uint64_t)(hi - lo)) return GNNVC_OK;   // (a graph this small is its own pilot: not worth a launch)
         uint32_t *cons = e->c4_desc.p + gnnvc_engine::kDescWords * stage;   // consumer stage `stage + 1`
+        e->c4_emit_zero = false;
+        ++e->plan_memsets;
         HIP_TRY(e, hipMemsetAsync(e->c4_emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
         gnnvc::EmitArgs pe;
         pe.spec = e->c4_desc.p + 2 * gnnvc_engine::kDescWords + 4;   // a word that is always 0: count, do not write table rows
@@ -451,7 +460,8 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         first.row_hi = lo + rows;
         first.logits = nullptr;
         HIP_TRY(e, gnnvc::launch_stage(first, {.interleave = true, .emit = pe}));
-        HIP_TRY(e, gnnvc::compact_choose(e->c4_emit_counts.p, 64, rows, cons, 1u, e->stream));
+        HIP_TRY(e, gnnvc::compact_choose(e->c4_emit_counts.p, 64, rows, cons, 1u, e->stream, /*clear_counts=*/true));
+        e->c4_emit_zero = true;
         return GNNVC_OK;
     };
     if (c.emit_t4) {   // this stage's epilogue counts its output's columns and writes the next stage's table (for that stage's last choice)
@@ -478,10 +488,12 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         rc = arm_emit();
         if (rc) return rc;
     }
-    if (c.sums == StageChoice::kLdsTable)   // (the sums share the blocked plan's buffer)
+    if (c.sums == StageChoice::kLdsTable) {   // (the sums share the blocked plan's buffer)
+        ++e->plan_memsets;   // (the flag "this input does not match the table": cleared by a memset ahead of k_lt_bytes_x)
         return hip_rc(e, gnnvc::launch_stage0_lds_table(plain, lds_table_plan(e), e->lt_bytes.p, e->blk_acc.p, e->lt_bad.p,
                                                         {.long_thresh = c.long_thresh, .mfma = e->opt.mfma == 1,
                                                          .interleave = e->interleave, .emit = emit}));
+    }
     if (c.sums == StageChoice::kBlocked)
         return hip_rc(e, gnnvc::launch_stage0_blocked(plain,
                                                       {.nblocks = e->blk_count, .bp = e->blk_ptr.p, .colb = e->blk_col.p, .acc = e->blk_acc.p},
@@ -500,9 +512,14 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         // what: 1 = choose the columns + write the table, 2 = the sums; the prepared table only needs its sums, a call
         // that runs its sums round by round (below) only the preparation
         const int what = !whole ? 2 : (c.rounds ? 1 : 3);
+        // (its k_c4_choose clears what this stage counts into: desc[5], the rounds' counters, and the producer's counters
+        // where it is the one that reads them)
+        if (fused) e->c4_emit_zero = false;
+        if (!(what & 1)) ++e->plan_memsets;   // (no k_c4_choose in this call: launch_compact_gather clears desc[5] with a memset)
         HIP_TRY(e, gnnvc::launch_compact_gather(e->g, compact_plan(e), in, fused ? e->c4_emit_counts.p : e->c4_counts.p, fused ? 64 : 1,
                                                 desc, e->c4_table.p, e->c4_acc.p, lo, hi, e->c4_dirty.p, e->c4_dirty_cap,
-                                                e->c4_agg16.p, e->stream, what));
+                                                e->c4_agg16.p, e->stream, what, c.rounds ? e->c4_round_counts.p : nullptr, 256u * e->c4_rows, fused));
+        if (fused) e->c4_emit_zero = true;
     }
     if (c.sums != StageChoice::kLdsTable && c.sums != StageChoice::kBlocked) {
         int rc = pilot();
@@ -523,11 +540,10 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
                                           .sums = sums, .mfma_agg = e->opt.mfma == 1, .emit = emit, .dense_part = !c.rounds,
                                           .so_pruned = so_p.vertex ? &so_p : nullptr}));
     if (!c.rounds) return GNNVC_OK;
-    HIP_TRY(e, hipMemsetAsync(desc + 5, 0, sizeof(uint32_t), e->stream));        // dirty-row counter
-    HIP_TRY(e, hipMemsetAsync(e->c4_marks.p, 0, sizeof(uint32_t), e->stream));   // marks[0]
+    // (desc[5] is zero and each round's counter at the round's first slot: k_c4_choose, what = 1 above)
     const uint32_t rows = e->c4_rows, c0 = (lo - e->c4_base) / rows, c1 = (hi - 1 - e->c4_base) / rows;
     const uint32_t nrounds = (c1 - c0) / 256u + 1u;
-    if (nrounds + 1 > 64) return fail(e, GNNVC_ERR_UNSUPPORTED, "too many rounds of the compact-table plan");
+    if (nrounds > gnnvc::compact_rounds()) return fail(e, GNNVC_ERR_UNSUPPORTED, "too many rounds of the compact-table plan");
     {
         int rc = ensure_round_events(e, nrounds);
         if (rc) return rc;
@@ -536,16 +552,19 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         const uint32_t ca = c0 + 256u * k, cb = std::min(c1 + 1u, ca + 256u);
         const uint32_t ra = std::max(lo, e->c4_base + ca * rows);
         const uint32_t rb = (uint32_t)std::min<uint64_t>(hi, (uint64_t)e->c4_base + (uint64_t)cb * rows);
+        // round k hands out its dirty-row slots from word k, which starts at its first chunk's row offset within the call:
+        // rows are done by whole chunks, so the round's dirty rows fit below the next round's first slot, and below c4_dirty_cap
+        uint32_t *const count = e->c4_round_counts.p + k;
+        const uint32_t slot_base = 256u * k * rows;
         HIP_TRY(e, gnnvc::compact_sums(e->g, compact_plan(e), desc, e->c4_table.p, e->c4_acc.p, ra, rb, e->c4_dirty.p, e->c4_dirty_cap,
-                                       e->stream, /*one_round=*/true));
-        HIP_TRY(e, gnnvc::compact_mark(desc, e->c4_marks.p, k + 1, e->stream));
+                                       e->stream, count));
         const bool last = k + 1 == nrounds;
         hipStream_t ds = last ? e->stream : e->aux_stream;
         if (!last) {
             HIP_TRY(e, hipEventRecord(e->round_ev[k], e->stream));
             HIP_TRY(e, hipStreamWaitEvent(e->aux_stream, e->round_ev[k], 0));
         }
-        HIP_TRY(e, gnnvc::compact_fix(e->g, in, desc, e->c4_dirty.p, e->c4_dirty_cap, e->c4_agg16.p, e->c4_marks.p + k, ds,
+        HIP_TRY(e, gnnvc::compact_fix(e->g, in, desc, e->c4_dirty.p, e->c4_dirty_cap, e->c4_agg16.p, count, slot_base, ds,
                                       /*blocks=*/64));
         gnnvc::StageCall round = plain;
         round.row_lo = ra;
@@ -1153,6 +1172,7 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
             else *value = k == "compact_gather_last_ok" ? (d[0] ? 1 : 0) : (k == "compact_gather_last_passes" ? (long)d[0] : (long)d[5]);
         }
     }
+    else if (k == "plan_memsets_last_forward") *value = (long)e->plan_memsets;
     else if (k == "lds_table_active") *value = e->pg.lt_ready ? 1 : 0;
     else if (k == "lds_table_last_ok") {   // did the last forward's input fit the table?  (waits for the stream; tests and tools)
         *value = 0;
@@ -1759,6 +1779,7 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     if (!d_x || !d_scores) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
     int rc = use_device(e);
     if (rc) return rc;
+    e->plan_memsets = 0;
     e->generic_ran = e->generic_on();
     e->heavy_last_rows = 0;
     e->ggiant_last_rows = 0;

@@ -189,11 +189,14 @@ struct gnnvc_engine {
     DevBuf<uint4> c4_map_meta;
     DevBuf<uint4> c4_steps;
     DevBuf<float> c4_table, c4_acc, c4_agg16;
-    DevBuf<uint32_t> c4_marks;            // dirty-row slots handed out after each round of the aggregation grid
+    DevBuf<uint32_t> c4_round_counts;     // next dirty-row slot of each round of the aggregation grid (compact_rounds() words; set by k_c4_choose)
     std::vector<gnnvc::Event> round_ev;    // "round k's sums are done" (main stream -> aux stream)
     DevBuf<uint32_t> c4_dirty;
     uint32_t c4_dirty_cap = 0;
     DevBuf<unsigned long long> c4_counts, c4_emit_counts;
+    uint32_t plan_memsets = 0;            // memsets the plans' launches queued between kernels since the last whole forward began
+                                          // (gnnvc_get_info "plan_memsets_last_forward": 1 in a steady forward on the plans, the LDS table's flag)
+    bool c4_emit_zero = false;            // the last thing queued on c4_emit_counts was a k_c4_choose that clears them behind its read
     uint32_t c4_base = 0, c4_end = 0;   // the plan's row range: the whole graph, or the rows a multi-GPU rank computes
     const float *c4_prepared_in = nullptr;   // gnnvc_stage_input_ready: the table's input (pg.c4_prepared_stage) as found at this address
     int c4_fused_for = -1;          // stage whose input statistics (and table) the previous stage kernel of this forward produced

@@ -459,6 +459,7 @@ uint32_t compact_block();
 uint32_t compact_shift();
 uint32_t compact_slices();   // a chunk = this many row slices (one per wave); the plan is built per slice
 uint32_t compact_step();     // entries per step
+uint32_t compact_rounds();   // dirty-row counters a call may run its sums with, one per round (round_counts below)
 // counts: per-column non-zero counts of `in` — 16 counters from column_counts() (count_slots = 1) or the
 // producer's kEmitCounters (count_slots = 64: 17 counters per slot, the 17th = rows seen; the table may then
 // already hold the rows' compact form for the columns in desc, see EmitArgs)
@@ -473,19 +474,25 @@ struct CompactPlan {   // the per-graph part of the plan, as the launches need i
     const uint32_t *rowmap = nullptr;    // null: slices of consecutive rows
 };
 // table: max_passes x (n + 1) rows of 16 bytes, acc4: max_passes x n
-hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const float *in, const unsigned long long *counts,
+hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const float *in, unsigned long long *counts,
                                  int count_slots, uint32_t *desc, float *table, float *acc4, uint32_t row_lo, uint32_t row_hi,
                                  uint32_t *dirty_rows, uint32_t dirty_cap, float *agg16, hipStream_t stream,
-                                 int what = 3 /* 1 = prepare, 2 = sums, 3 = both */);
+                                 int what = 3 /* 1 = prepare, 2 = sums, 3 = both */,
+                                 uint32_t *round_counts = nullptr /* compact_rounds() words the preparation sets as well ... */,
+                                 uint32_t round_stride = 0 /* ... word k to k * round_stride, round k's first dirty-row slot */,
+                                 bool clear_counts = false /* the preparation clears `counts` once it has read them */);
+// (the preparation — k_c4_choose — clears desc[5], the stage's dirty-row counter; a call with what == 2 clears it itself)
 
-hipError_t compact_choose(const unsigned long long *counts, int count_slots, uint32_t rows, uint32_t *desc, uint32_t max_passes,
-                          hipStream_t stream);
-// the parts of launch_compact_gather's second half, for callers that run them round by round
+hipError_t compact_choose(unsigned long long *counts, int count_slots, uint32_t rows, uint32_t *desc, uint32_t max_passes,
+                          hipStream_t stream, bool clear_counts = false);
+// the parts of launch_compact_gather's second half, for callers that run them round by round: round k of a call hands out its
+// dirty-row slots from a word of its own, which the preparation set to the round's first slot — the row offset of its first
+// chunk within the call; compact_fix with that word and that first slot does exactly those slots and adds their number to desc[5]
 hipError_t compact_sums(const GraphDev &g, const CompactPlan &cp, uint32_t *desc, const float *table, float *acc4, uint32_t row_lo,
-                        uint32_t row_hi, uint32_t *dirty_rows, uint32_t dirty_cap, hipStream_t stream, bool one_round = false);
-hipError_t compact_mark(const uint32_t *desc, uint32_t *marks, uint32_t k, hipStream_t stream);
-hipError_t compact_fix(const GraphDev &g, const float *in, const uint32_t *desc, const uint32_t *dirty_rows, uint32_t dirty_cap,
-                       float *agg16, const uint32_t *marks, hipStream_t stream, uint32_t blocks = 1024);
+                        uint32_t row_hi, uint32_t *dirty_rows, uint32_t dirty_cap, hipStream_t stream,
+                        uint32_t *round_count = nullptr);
+hipError_t compact_fix(const GraphDev &g, const float *in, uint32_t *desc, const uint32_t *dirty_rows, uint32_t dirty_cap,
+                       float *agg16, const uint32_t *dirty_count, uint32_t slot_base, hipStream_t stream, uint32_t blocks = 1024);
 
 // The next graph derived from the resident one (see the k_derive_* kernels): new_of is scratch of
 // old_g.n words, tail receives per new row the number of entries the device cannot derive, *bad != 0 afterwards means

@@ -711,15 +711,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
 // Three routes, uniform per wave: (A) no dirty row, no vertex with stray non-zeros: <= 11 terms; (B) dirty rows (their sixteen
 // sums from agg16) but no stray vertex: 16 + <= 7 terms; (C) anything else (a stray vertex among the wave's own rows, several
 // passes): the full chain from full rows.  Terms run in ascending k in every route: the reference's order.
+// Dirty rows are rare per row and common per wave (a fifth of the metric graph's waves hold one), and nearly all of a dirty wave's
+// twelve extra sums are zero in all 64 lanes: routes B and C run each term behind dense_live's wave-uniform test, under the
+// condition that gates routes A and B anyway (skip bit 0; route C without it runs every term).
+// (the chains as pairs, as in dense_live: left to itself the compiler pairs out[1] with out[2] across the routes' branches and
+// shuffles every weight row into place, fifteen scalar moves a term)
 template <int N>
-__device__ __forceinline__ void fma_term(float (&out)[N], float a, const float *__restrict__ Wrow) {
+__device__ __forceinline__ void fma_term(f32x2 (&acc)[N / 2], float a, const float *__restrict__ Wrow) {
+    const f32x2 aa = {a, a};
 #pragma unroll
-    for (int j = 0; j < N; ++j) out[j] = __builtin_fmaf(a, Wrow[j], out[j]);
+    for (int j = 0; j < N / 2; ++j) acc[j] = __builtin_elementwise_fma(aa, f32x2{Wrow[2 * j], Wrow[2 * j + 1]}, acc[j]);
 }
 template <int N>
-__device__ __forceinline__ void bias_relu(float (&out)[N], const float *__restrict__ b) {
+__device__ __forceinline__ void bias_relu(const f32x2 (&acc)[N / 2], float (&out)[N], const float *__restrict__ b) {
 #pragma unroll
-    for (int j = 0; j < N; ++j) out[j] = relu_ref(out[j] + b[j]);
+    for (int j = 0; j < N; ++j) out[j] = relu_ref(acc[j / 2][j % 2] + b[j]);
 }
 
 template <int N1, int N2, int N3, bool SIGMOID>
@@ -751,38 +757,60 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
     const float *W2 = b1 + N1, *b2 = W2 + N1 * N2;
     const float *W3 = b2 + N2, *b3 = W3 + N2 * N3;
     float x1[N1];
-    if (!__any(stray)) {
+    // k_c4_choose writes the table's columns in ascending order, the slots without a column (0xFFFFFFFF) last; route B walks them
+    // in that order, and a descriptor that is not so sends its dirty waves to route C, which asks nothing of it (a guard only:
+    // k_c4_choose is the one writer of these words, so no input reaches it and no test can)
+    const bool ascending = (d0 < d1 || d1 == 0xFFFFFFFFu) && (d1 < d2 || d2 == 0xFFFFFFFFu) && (d2 < d3 || d3 == 0xFFFFFFFFu);
+    if (!__any(stray) && (ascending || !__any(dirty))) {
         // the own-row terms of the chain: k = 16 (h[0]), 17 .. 19, 16 + d for a table column d >= 4 (h[1..3] are overwritten by
         // degree and weights in the reference's layout); a column slot without a column reads 0xFFFFFFFF
+        static_assert(N1 % 2 == 0, "outputs in pairs");
+        f32x2 acc[N1 / 2];
         auto own_terms = [&]() {
-            if (d0 == 0u) fma_term<N1>(x1, t.x, W1 + 16 * N1);
-            fma_term<N1>(x1, f_deg, W1 + 17 * N1);
-            fma_term<N1>(x1, f_w, W1 + 18 * N1);
-            fma_term<N1>(x1, f_nw, W1 + 19 * N1);
-            if (d0 >= 4u && d0 < 16u) fma_term<N1>(x1, t.x, W1 + (16u + d0) * N1);
-            if (d1 >= 4u && d1 < 16u) fma_term<N1>(x1, t.y, W1 + (16u + d1) * N1);
-            if (d2 >= 4u && d2 < 16u) fma_term<N1>(x1, t.z, W1 + (16u + d2) * N1);
-            if (d3 >= 4u && d3 < 16u) fma_term<N1>(x1, t.w, W1 + (16u + d3) * N1);
+            if (d0 == 0u) fma_term<N1>(acc, t.x, W1 + 16 * N1);
+            fma_term<N1>(acc, f_deg, W1 + 17 * N1);
+            fma_term<N1>(acc, f_w, W1 + 18 * N1);
+            fma_term<N1>(acc, f_nw, W1 + 19 * N1);
+            if (d0 >= 4u && d0 < 16u) fma_term<N1>(acc, t.x, W1 + (16u + d0) * N1);
+            if (d1 >= 4u && d1 < 16u) fma_term<N1>(acc, t.y, W1 + (16u + d1) * N1);
+            if (d2 >= 4u && d2 < 16u) fma_term<N1>(acc, t.z, W1 + (16u + d2) * N1);
+            if (d3 >= 4u && d3 < 16u) fma_term<N1>(acc, t.w, W1 + (16u + d3) * N1);
         };
 #pragma unroll
-        for (int j = 0; j < N1; ++j) x1[j] = 0.0f;
+        for (int j = 0; j < N1 / 2; ++j) acc[j] = f32x2{0.0f, 0.0f};
         if (!__any(dirty)) {   // (A)
-            if (d0 < 16u) fma_term<N1>(x1, a.x, W1 + d0 * N1);
-            if (d1 < 16u) fma_term<N1>(x1, a.y, W1 + d1 * N1);
-            if (d2 < 16u) fma_term<N1>(x1, a.z, W1 + d2 * N1);
-            if (d3 < 16u) fma_term<N1>(x1, a.w, W1 + d3 * N1);
+            if (d0 < 16u) fma_term<N1>(acc, a.x, W1 + d0 * N1);
+            if (d1 < 16u) fma_term<N1>(acc, a.y, W1 + d1 * N1);
+            if (d2 < 16u) fma_term<N1>(acc, a.z, W1 + d2 * N1);
+            if (d3 < 16u) fma_term<N1>(acc, a.w, W1 + d3 * N1);
         } else {               // (B)
             const size_t slot = dirty ? (size_t)__float_as_uint(a.y) : 0;
             const float4 g0 = agg16[slot * 4], g1 = agg16[slot * 4 + 1], g2 = agg16[slot * 4 + 2], g3 = agg16[slot * 4 + 3];
             const float gg[16] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w, g3.x, g3.y, g3.z, g3.w};
+            // a dirty row's sum is non-zero outside the table's columns only where one of its neighbours has a stray non-zero in
+            // that very column: each of the sixteen terms behind dense_live's test (uniform; NaNs count as non-zero and stay),
+            // its weight row fetched inside its branch.  The values are pinned in VGPRs first, as dense_live pins its inputs.
+            // A clean row's value of term k is its sum for a table column and zero otherwise; the table's columns ascend (see
+            // `ascending`), so one compare a term walks them.
+            float v[16], c0 = a.x, c1 = a.y, c2 = a.z, c3 = a.w;
+            uint32_t e0 = d0, e1 = d1, e2 = d2, e3 = d3;
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
-                const float clean = ((uint32_t)k == d0) ? a.x : ((uint32_t)k == d1) ? a.y : ((uint32_t)k == d2) ? a.z : ((uint32_t)k == d3) ? a.w : 0.0f;
-                fma_term<N1>(x1, dirty ? gg[k] : clean, W1 + k * N1);
+                float clean = 0.0f;
+                if ((uint32_t)k == e0) {   // (uniform)
+                    clean = c0;
+                    c0 = c1; c1 = c2; c2 = c3;
+                    e0 = e1; e1 = e2; e2 = e3; e3 = 0xFFFFFFFFu;
+                }
+                v[k] = dirty ? gg[k] : clean;
+                asm volatile("" : "+v"(v[k]));
             }
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (__any((__float_as_uint(v[k]) << 1) != 0u)) fma_term<N1>(acc, v[k], W1 + k * N1);   // (uniform)
         }
         own_terms();
-        bias_relu<N1>(x1, b1);
+        bias_relu<N1>(acc, x1, b1);
     } else {                   // (C)
         const float4 h0 = fin[(size_t)u * 4], h1 = fin[(size_t)u * 4 + 1], h2 = fin[(size_t)u * 4 + 2], h3 = fin[(size_t)u * 4 + 3];
         // first-layer inputs in k order: 0..15 aggregate, 16 = h[0], 17 = degree, 18 = W/ws, 19 = NW/ws, 20..31 = h[4..15]
@@ -811,7 +839,9 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
         x0[20] = h1.x; x0[21] = h1.y; x0[22] = h1.z; x0[23] = h1.w;
         x0[24] = h2.x; x0[25] = h2.y; x0[26] = h2.z; x0[27] = h2.w;
         x0[28] = h3.x; x0[29] = h3.y; x0[30] = h3.z; x0[31] = h3.w;
-        dense<32, 32, N1, 0>(x0, x1, W1, b1);   // rows 32..34 of W1 meet exact zeros
+        // rows 32..34 of W1 meet exact zeros; of the 32 others, the terms that are zero in the whole wave go where the layer's
+        // weights allow it (skip bit 0; without it, and under dense_skip_zeros = 0, every term runs)
+        dense_live<32, N1, 0>(x0, x1, W1, b1, (skip & 1u) != 0);
     }
     float x2[N2], x3[N3];
     dense_live<N1, N2, 0>(x1, x2, W2, b2, (skip & 2u) != 0);
@@ -3195,6 +3225,7 @@ constexpr int kC4LaneEntries = 3;         // consecutive entries a lane takes pe
 constexpr uint32_t kC4Step = 64u * kC4LaneEntries;   // entries per step
 constexpr uint32_t kC4DirtyWords = (kC4SliceRows + 31) / 32;
 constexpr uint32_t kC4NoRow = (1u << (32 - kC4Shift)) - 1u;   // row field of a slot past the step's end
+constexpr uint32_t kC4Rounds = 64;        // dirty-row counters of a call whose sums run round by round (compact_rounds())
 static_assert(kC4SliceRows < kC4NoRow - 1u, "row field too narrow");
 
 // desc words: [0] passes, [1..4] / [8..11] / [12..15] the chosen columns, [5] dirty-row counter, [6] the table(s) still have to
@@ -3202,8 +3233,13 @@ static_assert(kC4SliceRows < kC4NoRow - 1u, "row field too narrow");
 // slots == 1: counts[16] from k_column_counts.  slots == 64: the producer's counters (17 per slot; the 17th
 // counts the rows it saw — if that is not n, the producer that ran was not the emitting one and nothing here can
 // be trusted for this forward).  desc on entry = the previous forward's choice (the producer's spec).
-__global__ __launch_bounds__(64) void k_c4_choose(const unsigned long long *__restrict__ counts, int slots, uint32_t n,
-                                                  uint32_t *__restrict__ desc, uint32_t max_passes) {
+// The kernel runs ahead of everything that counts for its stage, alone on its stream, so it also does that stage's clearing (no
+// memset between the kernels): desc[5] always; the rounds' dirty-row counters where the caller has some (round_counts: kC4Rounds
+// words, counter k set to k * round_stride: the first slot round k hands out, so that k_c4_agg needs no base of its own); and,
+// with clear_counts, the producer's counters — it is their only reader, and clears them once it has read them.
+__global__ __launch_bounds__(64) void k_c4_choose(unsigned long long *__restrict__ counts, int slots, uint32_t n,
+                                                  uint32_t *__restrict__ desc, uint32_t max_passes, uint32_t *__restrict__ round_counts,
+                                                  uint32_t round_stride, int clear_counts) {
     // one wave, everything in registers: lane i < 17 ends up with the total of counter i (16 columns + the rows seen)
     const int lane = threadIdx.x;
     unsigned long long mine = 0;
@@ -3218,6 +3254,7 @@ __global__ __launch_bounds__(64) void k_c4_choose(const unsigned long long *__re
         for (int t = 0; t < kEmitStride; ++t) {
             const int idx = t * 64 + lane;                 // counts[idx] = counter idx % 17 of slot idx / 17
             part[t] = idx < slots * kEmitStride ? counts[idx] : 0ull;
+            if (clear_counts && idx < slots * kEmitStride) counts[idx] = 0ull;
         }
         // lane L holds pieces of counters (t * 64 + L) % 17, t = 0..16; sum per counter over all lanes and trips
         for (int c = 0; c < kEmitStride; ++c) {
@@ -3231,6 +3268,9 @@ __global__ __launch_bounds__(64) void k_c4_choose(const unsigned long long *__re
         }
     }
     const unsigned long long rows = ((unsigned long long)__shfl((unsigned)(mine >> 32), 16) << 32) | __shfl((unsigned)mine, 16);
+    static_assert(kC4Rounds == 64, "one lane per round counter");
+    if (round_counts) round_counts[lane] = (uint32_t)lane * round_stride;
+    if (lane == 0) desc[5] = 0u;
     const bool prev_ok = desc[0] == 1u;
     const uint32_t p1 = desc[1], p2 = desc[2], p3 = desc[3], p4 = desc[4];
     if (rows != n) {   // no (complete) statistics for this input
@@ -3356,7 +3396,11 @@ __global__ __launch_bounds__(1024) void k_c4_agg(const uint32_t *__restrict__ st
                                                  uint32_t slice1, uint32_t nslices, uint32_t last_entry, uint32_t *__restrict__ desc,
                                                  uint32_t *__restrict__ dirty_rows, uint32_t dirty_cap, uint32_t block_cols,
                                                  uint32_t nblocks, uint32_t row_base, uint32_t row_end, uint32_t pass,
-                                                 const uint32_t *__restrict__ rowmap) {
+                                                 const uint32_t *__restrict__ rowmap, uint32_t *__restrict__ dirty_count) {
+    // dirty_count: the next dirty-row slot — &desc[5], from 0, for a call done in one launch; a round of a call done round by
+    // round has a word of its own that STARTS at the round's first slot, the row offset of its first chunk within the call (a
+    // round's dirty rows are rows of its chunks: they always fit below the next round's first slot), so that no round has to
+    // know how many slots the rounds before it handed out.
     // pass: which of the plan's tables `table` is (desc[0] = how many the device chose for this input; the dirty rows are
     // registered by pass 0 only — the flags are the same in every table).  rowmap != nullptr: slice s holds the rows
     // rowmap[s * slice_rows ..] (0xFFFFFFFF = none) instead of slice_rows consecutive ones (skewed graphs: slices of
@@ -3519,7 +3563,7 @@ __global__ __launch_bounds__(1024) void k_c4_agg(const uint32_t *__restrict__ st
                     // a dirty row: its aggregate is recomputed from full rows (k_c4_fix) into slot `slot` of the
                     // side buffer; the sums here are not used.  No slot left: the stage kernel gathers it itself.
                     if (pass == 0) {
-                        const uint32_t slot = atomicAdd(&desc[5], 1u);
+                        const uint32_t slot = atomicAdd(dirty_count, 1u);
                         if (slot < dirty_cap) dirty_rows[slot] = row;
                         a[0] = __uint_as_float(0x80000000u);
                         a[1] = __uint_as_float(slot < dirty_cap ? slot : 0xFFFFFFFFu);
@@ -3532,13 +3576,15 @@ __global__ __launch_bounds__(1024) void k_c4_agg(const uint32_t *__restrict__ st
 
 // dirty rows (rows with a neighbour that has stray non-zeros): the plain aggregate, full 64-byte rows in CSR
 // order, one quad of lanes per row (lane c: columns 4c .. 4c+3) -> agg16[slot]
-__global__ __launch_bounds__(256) void k_c4_fix(GraphDev g, const float4 *__restrict__ fin, const uint32_t *__restrict__ desc,
+__global__ __launch_bounds__(256) void k_c4_fix(GraphDev g, const float4 *__restrict__ fin, uint32_t *__restrict__ desc,
                                                 const uint32_t *__restrict__ dirty_rows, uint32_t dirty_cap,
-                                                float4 *__restrict__ agg16, const uint32_t *__restrict__ marks) {
+                                                float4 *__restrict__ agg16, const uint32_t *__restrict__ dirty_count, uint32_t slot_base) {
     if (!desc[0]) return;
-    // marks != nullptr: only the slots handed out between two marks (one round of the aggregation grid)
-    const uint32_t first = marks ? min(marks[0], dirty_cap) : 0u;
-    const uint32_t count = min(marks ? marks[1] : desc[5], dirty_cap);
+    // the slots k_c4_agg handed out from the same counter: [slot_base, *dirty_count).  A round's count is added to desc[5]
+    // here, once, so that desc[5] ends up as the call's number of dirty rows whichever way its sums ran.
+    const uint32_t first = min(slot_base, dirty_cap);
+    const uint32_t count = min(*dirty_count, dirty_cap);
+    if (dirty_count != desc + 5 && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&desc[5], *dirty_count - slot_base);
     const uint32_t c = threadIdx.x & 3;
     for (uint32_t slot = first + ((blockIdx.x * blockDim.x + threadIdx.x) >> 2); slot < count; slot += (gridDim.x * blockDim.x) >> 2) {
         const uint32_t u = dirty_rows[slot];
@@ -3557,9 +3603,6 @@ __global__ __launch_bounds__(256) void k_c4_fix(GraphDev g, const float4 *__rest
         agg16[(size_t)slot * 4 + c] = a;
     }
 }
-
-// marks[k] = the number of dirty-row slots handed out so far (after round k - 1 of the aggregation grid)
-__global__ void k_c4_mark(const uint32_t *__restrict__ desc, uint32_t *__restrict__ marks, uint32_t k) { marks[k] = desc[5]; }
 
 // ------------------------------------------------------------------ pruned adjacency (skewed graphs, 16-wide stages)
 // On skewed graphs the trained model drives the features of every high-degree vertex to zero: after the first stage
@@ -5412,40 +5455,49 @@ uint32_t compact_block() { return kC4Block; }
 uint32_t compact_shift() { return kC4Shift; }
 uint32_t compact_slices() { return kC4Slices; }
 uint32_t compact_step() { return kC4Step; }
+uint32_t compact_rounds() { return kC4Rounds; }
 
 // counts -> desc -> table(s) -> four sums per pass and row of [row_lo, row_hi) (chunks that straddle the ends are done
 // whole; a mapped plan always does all of its rows).  `counts` holds the per-column non-zero counts of `in`
 // (column_counts, same stream).
-hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const float *in, const unsigned long long *counts,
+hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const float *in, unsigned long long *counts,
                                  int count_slots, uint32_t *desc, float *table, float *acc4, uint32_t row_lo, uint32_t row_hi,
-                                 uint32_t *dirty_rows, uint32_t dirty_cap, float *agg16, hipStream_t stream, int what) {
+                                 uint32_t *dirty_rows, uint32_t dirty_cap, float *agg16, hipStream_t stream, int what,
+                                 uint32_t *round_counts, uint32_t round_stride, bool clear_counts) {
     if (row_hi <= row_lo || g.nnz == 0 || row_lo < cp.plan_base || row_hi > cp.plan_end) return hipErrorInvalidValue;
     if (cp.rows_per_chunk == 0 || cp.rows_per_chunk > kC4MaxRows || cp.rows_per_chunk % kC4Slices) return hipErrorInvalidValue;
     if (cp.max_passes < 1 || cp.max_passes > kC4MaxPasses) return hipErrorInvalidValue;
     if (what & 1) {   // prepare: choose the columns and (unless the producing kernel did) write the table(s)
-        GNNVC_LAUNCH(k_c4_choose, dim3(1), dim3(64), 0, stream, counts, count_slots, g.n, desc, cp.max_passes);
+        GNNVC_LAUNCH(k_c4_choose, dim3(1), dim3(64), 0, stream, counts, count_slots, g.n, desc, cp.max_passes, round_counts,
+                     round_stride, clear_counts ? 1 : 0);
         GNNVC_LAUNCH(k_c4_compact, dim3(std::min<unsigned>((g.n + 256) / 256, 4096u)), dim3(256), 0, stream,
                            reinterpret_cast<const float4 *>(in), g.n, desc, reinterpret_cast<f32x4 *>(table));
     }
     if (!(what & 2)) return hipGetLastError();
-    hipError_t rc0 = hipMemsetAsync(desc + 5, 0, sizeof(uint32_t), stream);   // dirty-row counter
+    hipError_t rc0 = hipSuccess;
+    if (!(what & 1)) rc0 = hipMemsetAsync(desc + 5, 0, sizeof(uint32_t), stream);   // dirty-row counter (k_c4_choose cleared it otherwise)
     if (rc0 != hipSuccess) return rc0;
     rc0 = compact_sums(g, cp, desc, table, acc4, row_lo, row_hi, dirty_rows, dirty_cap, stream);
     if (rc0 != hipSuccess) return rc0;
-    return compact_fix(g, in, desc, dirty_rows, dirty_cap, agg16, nullptr, stream);
+    return compact_fix(g, in, desc, dirty_rows, dirty_cap, agg16, desc + 5, 0, stream);
 }
 
 // the choice of table columns alone, from counters that cover `rows` rows (a pilot over the first rows of a stage's output)
-hipError_t compact_choose(const unsigned long long *counts, int count_slots, uint32_t rows, uint32_t *desc, uint32_t max_passes,
-                          hipStream_t stream) {
-    GNNVC_LAUNCH(k_c4_choose, dim3(1), dim3(64), 0, stream, counts, count_slots, rows, desc, max_passes);
+hipError_t compact_choose(unsigned long long *counts, int count_slots, uint32_t rows, uint32_t *desc, uint32_t max_passes,
+                          hipStream_t stream, bool clear_counts) {
+    GNNVC_LAUNCH(k_c4_choose, dim3(1), dim3(64), 0, stream, counts, count_slots, rows, desc, max_passes, (uint32_t *)nullptr,
+                 0u, clear_counts ? 1 : 0);
     return hipGetLastError();
 }
 
-// the sums of the chunks that hold rows [row_lo, row_hi) (the dirty-row counter desc[5] is the caller's to reset): one
-// launch per pass the plan allows; the launches of passes the device did not choose (desc[0]) leave at once
+// the sums of the chunks that hold rows [row_lo, row_hi): one launch per pass the plan allows; the launches of passes the
+// device did not choose (desc[0]) leave at once.  round_count == nullptr: the whole call in one launch, dirty rows counted in
+// desc[5]; otherwise one round of the persistent grid, its dirty rows taking the slots *round_count, + 1, ...  On entry
+// desc[5] is zero and *round_count the round's first slot: k_c4_choose's work, or the caller's.
 hipError_t compact_sums(const GraphDev &g, const CompactPlan &cp, uint32_t *desc, const float *table, float *acc4, uint32_t row_lo,
-                        uint32_t row_hi, uint32_t *dirty_rows, uint32_t dirty_cap, hipStream_t stream, bool one_round) {
+                        uint32_t row_hi, uint32_t *dirty_rows, uint32_t dirty_cap, hipStream_t stream, uint32_t *round_count) {
+    const bool one_round = round_count != nullptr;
+    uint32_t *const dirty_count = one_round ? round_count : desc + 5;
     if (row_hi <= row_lo || g.nnz == 0 || row_lo < cp.plan_base || row_hi > cp.plan_end) return hipErrorInvalidValue;
     if (cp.rows_per_chunk == 0 || cp.rows_per_chunk > kC4MaxRows || cp.rows_per_chunk % kC4Slices) return hipErrorInvalidValue;
     if (cp.rowmap && one_round) return hipErrorInvalidValue;
@@ -5470,27 +5522,23 @@ hipError_t compact_sums(const GraphDev &g, const CompactPlan &cp, uint32_t *desc
         if (one_round)
             GNNVC_LAUNCH(k_c4_agg<1>, grid, block, lds, stream, cp.step_ptr, reinterpret_cast<const uint4 *>(cp.steps), cp.entries, tq, aq,
                                g.n, slice_rows, c0 * kC4Slices, std::min(c1 * kC4Slices, nslices), nslices, cp.last_entry, desc,
-                               dirty_rows, dirty_cap, cp.block_cols, cp.nblocks, cp.plan_base, cp.plan_end, pass, cp.rowmap);
+                               dirty_rows, dirty_cap, cp.block_cols, cp.nblocks, cp.plan_base, cp.plan_end, pass, cp.rowmap, dirty_count);
         else
             GNNVC_LAUNCH(k_c4_agg<0>, grid, block, lds, stream, cp.step_ptr, reinterpret_cast<const uint4 *>(cp.steps), cp.entries, tq, aq,
                                g.n, slice_rows, c0 * kC4Slices, std::min(c1 * kC4Slices, nslices), nslices, cp.last_entry, desc,
-                               dirty_rows, dirty_cap, cp.block_cols, cp.nblocks, cp.plan_base, cp.plan_end, pass, cp.rowmap);
+                               dirty_rows, dirty_cap, cp.block_cols, cp.nblocks, cp.plan_base, cp.plan_end, pass, cp.rowmap, dirty_count);
     }
     return hipGetLastError();
 }
 
-// marks[k] = dirty-row slots handed out so far
-hipError_t compact_mark(const uint32_t *desc, uint32_t *marks, uint32_t k, hipStream_t stream) {
-    GNNVC_LAUNCH(k_c4_mark, dim3(1), dim3(1), 0, stream, desc, marks, k);
-    return hipGetLastError();
-}
-
-// full-row aggregates of the dirty rows: all of them (marks == nullptr) or those of slots [marks[0], marks[1]); `blocks`:
-// a small grid when the kernel runs beside the aggregation grid (it strides over what it has to do)
-hipError_t compact_fix(const GraphDev &g, const float *in, const uint32_t *desc, const uint32_t *dirty_rows, uint32_t dirty_cap,
-                       float *agg16, const uint32_t *marks, hipStream_t stream, uint32_t blocks) {
+// full-row aggregates of the dirty rows in slots [slot_base, *dirty_count): the counter compact_sums counted with and the slot
+// it started from (desc + 5 and 0 for a call done in one launch); `blocks`: a small grid when the kernel runs beside the aggregation grid (it
+// strides over what it has to do)
+hipError_t compact_fix(const GraphDev &g, const float *in, uint32_t *desc, const uint32_t *dirty_rows, uint32_t dirty_cap,
+                       float *agg16, const uint32_t *dirty_count, uint32_t slot_base, hipStream_t stream, uint32_t blocks) {
     GNNVC_LAUNCH(k_c4_fix, dim3(std::min<uint32_t>((dirty_cap + 63) / 64, blocks)), dim3(256), 0, stream, g,
-                       reinterpret_cast<const float4 *>(in), desc, dirty_rows, dirty_cap, reinterpret_cast<float4 *>(agg16), marks);
+                       reinterpret_cast<const float4 *>(in), desc, dirty_rows, dirty_cap, reinterpret_cast<float4 *>(agg16), dirty_count,
+                       slot_base);
     return hipGetLastError();
 }
 

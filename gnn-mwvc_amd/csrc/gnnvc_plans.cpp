@@ -812,12 +812,13 @@ int c4_begin(gnnvc_engine *e, uint32_t base, uint32_t end) {
     HIP_TRY(e, e->c4_desc.reserve(kFlagWord + 8));
     HIP_TRY(e, e->c4_counts.reserve(16));
     HIP_TRY(e, e->c4_emit_counts.reserve(gnnvc::kEmitCounters));
+    e->c4_emit_zero = false;   // (perhaps a new buffer)
     HIP_TRY(e, e->c4_segcnt.reserve((size_t)slices * nblocks));
     HIP_TRY(e, e->c4_stepcnt.reserve(slices));
     HIP_TRY(e, e->c4_stepptr.reserve((size_t)slices + 2));
     HIP_TRY(e, e->c4_entries.reserve(entry_cap));
     HIP_TRY(e, e->c4_table.reserve(((size_t)g.n + 1) * 4 * passes));
-    HIP_TRY(e, e->c4_marks.reserve(64));
+    HIP_TRY(e, e->c4_round_counts.reserve(gnnvc::compact_rounds()));
     HIP_TRY(e, e->c4_acc.reserve((size_t)g.n * 4 * passes));
     e->c4_dirty_cap = g.n;   // rows recomputed from full rows (every row could be one: the dense-only stage kernel never gathers)
     HIP_TRY(e, e->c4_dirty.reserve(e->c4_dirty_cap));
