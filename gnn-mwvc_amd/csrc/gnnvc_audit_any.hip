@@ -3,7 +3,10 @@
 // n[0 .. d), ReLU | sigmoid — for rows [lo, hi) from the stage's own input and compares every value the fused path wrote: the
 // n[d - 1]-wide output row, or the scores and the logits on the sigmoid stage.  Bounds: whatever stage_any_fits admits (1 <= f <= 32,
 // every width but the last <= 64 — <= 128 in a big stage, gnnvc_set_generic_big_stages — the last <= 32; f and the last width up to
-// 64 under gnnvc_set_generic_feature_width).
+// 64 under gnnvc_set_generic_feature_width).  Under gnnvc_set_generic_patterns a stage may be DENSE — no graph layer: the row is
+// the stage's own input row, f columns, and the first K is f — and the model's last stage may end in a ReLU or in its bare linear
+// layer, whose pre-activation is then what the fused path stored (`sig`: kEndRelu, kEndSigmoid, kEndNone; logits are compared on a
+// sigmoid stage only).
 //
 // What is computed is the layer-by-layer kernels' arithmetic (k_graph_layer, k_linear, k_relu, k_sigmoid):
 //   neighbour-sum column c   one fp32 add chain in stored CSR order from +0.0f;
@@ -77,11 +80,11 @@ __device__ __forceinline__ bool is_nan_bits(uint32_t b) { return (b & 0x7FFFFFFF
 __global__ __launch_bounds__(kBlockThreads) void k_audit_any(AuditGraph g, float ws, const float *__restrict__ P,
                                                              const float *__restrict__ in, float *out, float *logits, uint32_t lo,
                                                              uint32_t hi, AuditShape S, int sig, unsigned long long *__restrict__ rec,
-                                                             int repair) {
+                                                             int repair, int dense) {
     __shared__ float vec[kWaves][2][kVec];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t f = (uint32_t)S.f;
-    const int d = S.d, k1 = 2 * S.f + 3;
+    const int d = S.d, k1 = dense ? S.f : 2 * S.f + 3;   // (dense: wave-uniform, a kernel argument)
     const uint32_t cl = min((uint32_t)lane, f - 1u);   // the lane's neighbour column (lanes >= f fetch a copy nobody uses)
     // what this wave has found over all its rows (kept by every lane alike; lane 0 submits it once, at the end)
     unsigned long long n_bad = 0, n_nan = 0, first_row = 0;
@@ -90,39 +93,44 @@ __global__ __launch_bounds__(kBlockThreads) void k_audit_any(AuditGraph g, float
     for (uint64_t u64 = (uint64_t)lo + (uint64_t)blockIdx.x * kWaves + (uint64_t)wave; u64 < hi; u64 += (uint64_t)gridDim.x * kWaves) {
         const uint32_t u = (uint32_t)u64;
         float *a = vec[wave][0], *b = vec[wave][1];
-        // ---- graph layer: column cl's chain
-        const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
-        float s = 0.0f;
-        uint32_t next_ids = (rs + (uint32_t)lane < re) ? g.col[rs + lane] : 0u;
-        for (uint32_t e = rs; e < re; e += 64u) {
-            const uint32_t ids = next_ids, m = min(64u, re - e);
-            next_ids = (e + 64u + (uint32_t)lane < re) ? g.col[e + 64u + lane] : 0u;
-            if (f == 1u) {
-                const float mine = in[ids];   // (lanes >= m: ids == 0, a valid row nobody adds)
-                for (uint32_t i = 0; i < m; ++i) s = s + __shfl(mine, (int)i);
-            } else {
-                for (uint32_t i0 = 0; i0 < m; i0 += 8u) {
-                    float v[8];
+        if (dense) {
+            // ---- a dense stage: the row is row u of the input (f <= 64: one column a lane); no array of the graph is read
+            if ((uint32_t)lane < f) a[lane] = in[(size_t)u * f + (uint32_t)lane];
+        } else {
+            // ---- graph layer: column cl's chain
+            const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
+            float s = 0.0f;
+            uint32_t next_ids = (rs + (uint32_t)lane < re) ? g.col[rs + lane] : 0u;
+            for (uint32_t e = rs; e < re; e += 64u) {
+                const uint32_t ids = next_ids, m = min(64u, re - e);
+                next_ids = (e + 64u + (uint32_t)lane < re) ? g.col[e + 64u + lane] : 0u;
+                if (f == 1u) {
+                    const float mine = in[ids];   // (lanes >= m: ids == 0, a valid row nobody adds)
+                    for (uint32_t i = 0; i < m; ++i) s = s + __shfl(mine, (int)i);
+                } else {
+                    for (uint32_t i0 = 0; i0 < m; i0 += 8u) {
+                        float v[8];
 #pragma unroll
-                    for (uint32_t t = 0; t < 8u; ++t) {
-                        const uint32_t nb = (uint32_t)__shfl((int)ids, (int)min(i0 + t, m - 1u));
-                        v[t] = in[(size_t)nb * f + cl];
+                        for (uint32_t t = 0; t < 8u; ++t) {
+                            const uint32_t nb = (uint32_t)__shfl((int)ids, (int)min(i0 + t, m - 1u));
+                            v[t] = in[(size_t)nb * f + cl];
+                        }
+#pragma unroll
+                        for (uint32_t t = 0; t < 8u; ++t)
+                            if (i0 + t < m) s = s + v[t];
                     }
-#pragma unroll
-                    for (uint32_t t = 0; t < 8u; ++t)
-                        if (i0 + t < m) s = s + v[t];
                 }
             }
-        }
-        const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
-        for (int c = lane; c < k1; c += 64) {
-            float v = 0.0f;
-            if (c < (int)f) v = s;   // (f <= 64: c == lane here)
-            else if (c < 2 * (int)f) v = in[(size_t)u * f + (uint32_t)(c - (int)f)];
-            if (c == (int)f + 1) v = deg;
-            if (c == (int)f + 2) v = wv;
-            if (c == (int)f + 3) v = nwv;
-            a[c] = v;
+            const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
+            for (int c = lane; c < k1; c += 64) {
+                float v = 0.0f;
+                if (c < (int)f) v = s;   // (f <= 64: c == lane here)
+                else if (c < 2 * (int)f) v = in[(size_t)u * f + (uint32_t)(c - (int)f)];
+                if (c == (int)f + 1) v = deg;
+                if (c == (int)f + 2) v = wv;
+                if (c == (int)f + 3) v = nwv;
+                a[c] = v;
+            }
         }
         wave_handoff();
         // ---- the dense layers: lane o = output o; W[k * N + o] from the parameter block as stored
@@ -165,9 +173,11 @@ __global__ __launch_bounds__(kBlockThreads) void k_audit_any(AuditGraph g, float
                 if (repair) *p = want;
             };
             const size_t at = (size_t)u * (uint32_t)n_out + (uint32_t)lane;
-            if (sig) {
+            if (sig == kEndSigmoid) {
                 check(out + at, sigmoid_ref(r), (uint32_t)lane);
                 if (logits) check(logits + at, r, 64u + (uint32_t)lane);
+            } else if (sig == kEndNone) {
+                check(out + at, r, (uint32_t)lane);
             } else {
                 check(out + at, relu_ref(r), (uint32_t)lane);
             }
@@ -213,12 +223,12 @@ hipError_t launch_audit_any(const StageCall &c, unsigned long long *rec, bool re
     for (int l = 0; l < kMaxDenseLayers; ++l) S.n[l] = (l < sp.nd) ? sp.wn[l] : 0;
     // (stage_any_fits' bounds are what the vectors and the column code are sized for: the static_assert at kVec)
     // the graph as handed over and nothing else: no plan's view can reach the audit
-    const AuditGraph plain{g.rowptr, g.col, g.w, g.nw};
+    const AuditGraph plain = sp.dense ? AuditGraph{nullptr, nullptr, nullptr, nullptr} : AuditGraph{g.rowptr, g.col, g.w, g.nw};
     // a persistent grid: a wave per row, up to eight workgroups on each of 256 CUs
     const size_t need = ((size_t)(c.row_hi - c.row_lo) + kWaves - 1) / kWaves;
     const dim3 grid((unsigned)std::min<size_t>(need, 2048u)), block(kBlockThreads);
     hipLaunchKernelGGL(k_audit_any, grid, block, 0, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, c.out,
-                       sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0, rec, repair ? 1 : 0);
+                       sp.sigmoid_last ? c.logits : nullptr, c.row_lo, c.row_hi, S, sp.end, rec, repair ? 1 : 0, sp.dense ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -173,6 +173,13 @@ int plan_model(gnnvc_engine *e) {
 // each stage carries as big_lds, and the feature width of gnnvc_set_generic_feature_width, carried as feat_width); every activation a ReLU but the model's last, a sigmoid (a model that ends in a ReLU stays layer
 // by layer, as for the trained shapes).  One stage outside the bounds leaves the whole model layer by layer.  Derives e->gstages
 // anew from the layers (their parameter offsets are plan_model's): at model load, and when the opt-in's limit moves.
+//
+// With gnnvc_set_generic_patterns (e->patterns, carried by every stage as `patterns`) the pattern is [P] S*, at least one stage: P, a
+// DENSE stage (Linear, activation){1..6} in front of the first graph layer (stage 0 of the list), and a last activation that may
+// also be a ReLU or be missing.  This function only reads the layer sequence into stages — a sigmoid inside the model, two graph
+// layers in a row, two linear layers without an activation between them or a block of seven dense layers is no sequence of
+// stages under any mask — and says of each whether it is dense, how it ends and whether it is the model's last; whether the mask
+// admits that is stage_any_route's decision, like every bound.
 void plan_generic(gnnvc_engine *e) {
     e->gstages.clear();
     std::vector<StagePlan> gs;
@@ -181,21 +188,29 @@ void plan_generic(gnnvc_engine *e) {
     for (size_t i = 0; gok && i < e->layers.size();) {
         const Layer *L = &e->layers[i];
         const size_t left = e->layers.size() - i;
-        gok = L[0].kind == kGraph;
-        if (!gok) break;
         StagePlan sp;
+        sp.dense = i == 0 && L[0].kind == kLinear;   // (only the model's first stage may lack its graph layer)
+        gok = sp.dense || L[0].kind == kGraph;
+        if (!gok) break;
         sp.f = f;
         sp.nd = 0;
-        int k = 2 * f + 3;
-        size_t at = 1;
-        while (gok && at + 1 < left && L[at].kind == kLinear) {   // (a pair needs its activation: at + 1 is inside the model)
-            const bool model_end = at + 2 == left;
-            gok = sp.nd < gnnvc::kMaxDenseLayers && (int)L[at].k == k && L[at + 1].kind == (model_end ? kSigmoid : kRelu);
+        sp.patterns = e->patterns;
+        int k = sp.dense ? f : 2 * f + 3;
+        size_t at = sp.dense ? 0 : 1;
+        while (gok && at < left && L[at].kind == kLinear) {
+            // what follows the linear layer: its ReLU, the model's last sigmoid, or nothing — the model's last layer is this one
+            const bool bare = at + 1 == left;
+            const bool model_end = bare || at + 2 == left;
+            const int end = bare ? gnnvc::kEndNone : L[at + 1].kind == kRelu ? gnnvc::kEndRelu
+                            : (L[at + 1].kind == kSigmoid && model_end) ? gnnvc::kEndSigmoid : -1;
+            gok = sp.nd < gnnvc::kMaxDenseLayers && (int)L[at].k == k && end >= 0;
             if (!gok) break;
             if (sp.nd == 0) sp.param_offset = L[at].w_off;   // (the parameter buffer is in layer order: W b W b ... are contiguous)
             sp.wn[sp.nd++] = k = (int)L[at].m;
-            sp.sigmoid_last = model_end;
-            at += 2;
+            sp.end = end;
+            sp.model_last = model_end;
+            sp.sigmoid_last = end == gnnvc::kEndSigmoid;
+            at += bare ? 1 : 2;
         }
         gok = gok && sp.nd >= 1 && (at == left || L[at].kind == kGraph);
         if (!gok) break;
@@ -741,6 +756,10 @@ int forward_unfused(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
 // giant chain and then the heavy sums go to the side queue beside the light rows (fork / join as launch_side_rows) or ahead of
 // them on the main stream (heavy_overlap()); the listed rows' launch follows all of them.
 int run_generic_stage(gnnvc_engine *e, const StagePlan &sp, const float *in, float *out, float *logits, uint32_t lo, uint32_t hi) {
+    if (sp.dense) {   // a dense stage (gnnvc_set_generic_patterns): no neighbour sums, so no row is classed and nothing is split — one launch
+        HIP_TRY(e, gnnvc::launch_stage_any(stage_call(e, sp, in, out, logits, lo, hi)));
+        return GNNVC_OK;
+    }
     {   // (lazily: option "generic_stages" set after the attach, or a threshold that has moved)
         const int rc = class_heavy_rows(e);
         if (rc) return rc;
@@ -811,8 +830,9 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
             if (rc != GNNVC_OK) return rc;
         }
         if (e->audit_now) {   // (gnnvc_forward_audited* only: "audit_period" never sets it for a generic-stage model)
-            std::string plan = e->heavy_last_rows ? "k_stage_any (light rows, listed rows) + k_any_heavy_sums" : "k_stage_any";
-            if (e->ggiant_last_rows)
+            std::string plan = st[s].dense ? "k_stage_any (dense rows)"
+                               : e->heavy_last_rows ? "k_stage_any (light rows, listed rows) + k_any_heavy_sums" : "k_stage_any";
+            if (!st[s].dense && e->ggiant_last_rows)
                 plan += e->ggiant_last_segmented ? " + k_any_giant_gather, k_giant_segsum, k_giant_segmap, k_giant_sum, k_any_giant_place"
                                                  : " + k_any_giant_gather, k_giant_sum, k_any_giant_place";
             const int rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan);
@@ -1031,6 +1051,19 @@ int gnnvc_set_generic_feature_width(gnnvc_engine *e, uint32_t max_width) {
     return GNNVC_OK;
 }
 
+int gnnvc_set_generic_patterns(gnnvc_engine *e, uint32_t mask) {
+    if (!e) return GNNVC_ERR_INVALID;
+    NOT_ON_MULTI(e, "gnnvc_set_generic_patterns");
+    if (mask & ~(uint32_t)(GNNVC_PATTERN_PROLOGUE | GNNVC_PATTERN_OPEN_END))
+        return fail(e, GNNVC_ERR_INVALID, "gnnvc_set_generic_patterns: 0x%x has bits other than GNNVC_PATTERN_PROLOGUE | GNNVC_PATTERN_OPEN_END", mask);
+    static_assert(GNNVC_PATTERN_PROLOGUE == gnnvc::kPatternPrologue && GNNVC_PATTERN_OPEN_END == gnnvc::kPatternOpenEnd, "one mask");
+    if (mask == e->patterns) return GNNVC_OK;
+    e->patterns = mask;             // (no LDS limit to raise: a dense stage outside the default bounds needs the big or feat call, which raise theirs)
+    plan_generic(e);                // (at once, as gnnvc_set_generic_big_stages)
+    e->pg.heavy_known = false;      // an attached graph is classed again by the next generic graph stage that runs (class_heavy_rows)
+    return GNNVC_OK;
+}
+
 // "<prefix><s>" of a generic model: the stage index, or -1 (no such stage, not a number, the model is not generic)
 static long generic_stage_index(const gnnvc_engine *e, const std::string &k, size_t prefix_len) {
     const char *num = k.c_str() + prefix_len;
@@ -1075,6 +1108,17 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     }
     else if (k == "generic_big_lds") *value = (long)e->big_lds;                       // gnnvc_set_generic_big_stages, as set
     else if (k == "generic_feature_width") *value = (long)e->feat_width;              // gnnvc_set_generic_feature_width, as set
+    else if (k == "generic_patterns") *value = (long)e->patterns;                     // gnnvc_set_generic_patterns, as set
+    else if (k.rfind("generic_stage_dense_", 0) == 0) {       // "generic_stage_dense_<s>": 1 = stage s has no graph layer (a prologue)
+        const long s = generic_stage_index(e, k, sizeof("generic_stage_dense_") - 1);
+        if (s < 0) return GNNVC_ERR_INVALID;
+        *value = e->gstages[(size_t)s].dense ? 1 : 0;
+    }
+    else if (k.rfind("generic_stage_end_", 0) == 0) {         // "generic_stage_end_<s>": 0 = it ends in a ReLU, 1 = in the sigmoid, 2 = in its bare linear layer
+        const long s = generic_stage_index(e, k, sizeof("generic_stage_end_") - 1);
+        if (s < 0) return GNNVC_ERR_INVALID;
+        *value = e->gstages[(size_t)s].end;
+    }
     else if (k.rfind("generic_stage_lds_bytes_", 0) == 0) {   // "generic_stage_lds_bytes_<s>": the stage's LDS layout at 256 threads
         const long s = generic_stage_index(e, k, sizeof("generic_stage_lds_bytes_") - 1);
         if (s < 0) return GNNVC_ERR_INVALID;

@@ -67,6 +67,9 @@ struct gnnvc_engine {
     // gnnvc_set_generic_feature_width: 0 = off, else what f and a stage's last width may be (33 .. 64) instead of 32; carried by
     // every plan in gstages like big_lds
     uint32_t feat_width = 0;
+    // gnnvc_set_generic_patterns: 0 = off, else the mask of GNNVC_PATTERN_PROLOGUE | GNNVC_PATTERN_OPEN_END (a dense stage in front
+    // of the first graph layer; a model that ends in a ReLU or in its bare linear layer); carried by every plan in gstages too
+    uint32_t patterns = 0;
     bool generic_on() const { return !gstages.empty() && (opt.generic == 2 || (opt.generic == 1 && stages.empty())); }
     const std::vector<StagePlan> &stage_list() const { return generic_on() ? gstages : stages; }   // what the ABI reports and runs
     // Heavy rows of generic stages (gnnvc_set_generic_heavy_rows): rows of at least heavy_from entries (0: none) get a workgroup

@@ -80,6 +80,12 @@ struct StagePlan {
     int wn[kMaxDenseLayers] = {0, 0, 0, 0, 0, 0};   // their widths, wn[nd - 1] == n3 (filled for generic stages)
     uint32_t big_lds = 0;     // a generic stage: the LDS limit of gnnvc_set_generic_big_stages it was planned under (0 = off)
     uint32_t feat_width = 0;  // a generic stage: the feature width of gnnvc_set_generic_feature_width it was planned under (0 = off)
+    // a generic stage under gnnvc_set_generic_patterns (all 0 / kEndRelu | kEndSigmoid for every stage planned without it):
+    int dense = 0;            // 1: a dense stage — no graph layer in front, the row is the input row itself and the first K is f
+    int end = 0;              // how it ends (kEndRelu, kEndSigmoid, kEndNone: the last layer's pre-activation is stored);
+                              // sigmoid_last == (end == kEndSigmoid)
+    int model_last = 0;       // 1: the model's last stage — the only one that may end otherwise than in a ReLU
+    uint32_t patterns = 0;    // the mask of gnnvc_set_generic_patterns it was planned under (0 = off)
     uint32_t skip_ok = 0;     // bit l set: dense layer l + 1 has finite weights only and no bias with the bits of -0.0f, so terms
                               // whose input is +-0 may be left out of its chains bit for bit (set at model load)
 };
@@ -213,6 +219,13 @@ hipError_t launch_audit_flip(float *out, size_t at, hipStream_t stream);
 // is never read), out: rows [row_lo, row_hi) of an (n + 1) x n3 matrix, logits likewise (sigmoid stage, optional).
 constexpr int kAnyMaxF = 32, kAnySmallHidden = 64, kAnyBigHidden = 128, kAnyMaxLast = 32;   // the widths stage_any_route admits
 constexpr int kAnyFeatMax = 64;   // ... and the most that f and the last width may be raised to (gnnvc_set_generic_feature_width)
+//   a DENSE stage    sp.dense (gnnvc_set_generic_patterns, bit kPatternPrologue): (Linear, activation){1..6} in front of the model's
+//                    first graph layer.  The same bounds with the first K equal to f where a graph stage has 2 f + 3; one launch
+//                    (the kAnyDense instantiations: no graph array is read, no row is classed);
+//   an OPEN ending   the model's last stage may end in a ReLU or in its bare linear layer (sp.end, bit kPatternOpenEnd); only a
+//                    stage that ends in the sigmoid writes logits.
+constexpr uint32_t kPatternPrologue = 1u, kPatternOpenEnd = 2u;   // GNNVC_PATTERN_PROLOGUE, GNNVC_PATTERN_OPEN_END
+enum { kEndRelu = 0, kEndSigmoid = 1, kEndNone = 2 };             // StagePlan::end, "generic_stage_end_<s>"
 struct AnyRoute {
     bool ok = false, big = false, feat = false;   // feat: f or the last width above 32 (a FEAT instantiation)
     int threads = 256;           // the workgroup size the launcher uses

@@ -322,7 +322,8 @@ int class_heavy_rows(gnnvc_engine *e) {
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     if (found[0] == 0) return GNNVC_OK;
     int fmax = 1;
-    for (const StagePlan &sp : e->gstages) fmax = std::max(fmax, sp.f);
+    for (const StagePlan &sp : e->gstages)
+        if (!sp.dense) fmax = std::max(fmax, sp.f);   // (a dense stage has no sums: hsum and the giant slab follow the graph stages' f)
     HIP_TRY(e, e->heavy_sum.reserve((size_t)found[0] * (size_t)fmax));
     if (heavy_overlap()) {   // the sums run on the side queue, beside the light rows
         const int rc = ensure_side_streams(e);

@@ -19,6 +19,9 @@
 // most 160 KiB, a CU's LDS): it launches a BIG instantiation (below), whose limit allow_big_stages has raised.  With
 // gnnvc_set_generic_feature_width f and the last width may be up to the width given (33 .. 64): a stage that uses the allowance
 // launches a FEAT instantiation (below), and must still fit the LDS and hidden-width bounds, default or big, like any other.
+// With gnnvc_set_generic_patterns a stage may be DENSE — no graph layer in front: the row is row u of the input itself and the
+// first K is f, within the same bounds (the kAnyDense instantiations below) — and the model's last stage may end in a ReLU or in
+// its bare linear layer, whose pre-activation is stored (the OPEN instantiations).
 //
 // Shape of the kernel: 256-thread workgroups walk the row range 16 rows at a time (grid-stride; no workgroup barrier inside
 // the walk, so a wave that sits on a very long row holds up nobody else).  Each workgroup first transposes the stage's
@@ -85,9 +88,10 @@ __host__ __device__ inline int any_round4(int v) { return (v + 3) / 4 * 4; }
 __host__ __device__ inline int any_pitch(int k) {
     return 4 * (((k + 3) / 4) | 1);   // an odd number of 16-byte slots: rows o .. o + 15 start in sixteen different slots
 }
-__host__ __device__ inline StageAnyLayout stage_any_layout(const AnyShape &S, int rows) {   // rows: a workgroup's rows per pass (threads / 16)
+// first_k: the first layer's K — 0 = a graph stage's 2 f + 3 (every call site but a dense stage's), f for a dense stage
+__host__ __device__ inline StageAnyLayout stage_any_layout(const AnyShape &S, int rows, int first_k = 0) {   // rows: a workgroup's rows per pass (threads / 16)
     StageAnyLayout L;
-    int K = 2 * S.f + 3, wsum = 0, nsum = 0, a = K, b = 0;   // a, b: the longest vector that lands in A, in B
+    int K = first_k ? first_k : 2 * S.f + 3, wsum = 0, nsum = 0, a = K, b = 0;   // a, b: the longest vector that lands in A, in B
     for (int l = 0; l < S.d; ++l) {
         const int N = S.n[l];
         wsum += N * any_pitch(K);
@@ -165,8 +169,11 @@ __device__ __forceinline__ void any_hidden_n(const float *x, int K, const float 
     }
 }
 
-// the stage's last layer, straight to memory: row u of out (and of logits, sigmoid stage, when asked for)
-template <int T>
+// the stage's last layer, straight to memory: row u of out (and of logits, sigmoid stage, when asked for).  sig: kEndRelu or
+// kEndSigmoid — and, in the OPEN instantiations only, kEndNone: the pre-activation itself is stored (a select beside the ReLU's).
+// OPEN is a template argument so that the instantiations that were there compile to what they compiled to: as a third runtime
+// value of `sig` it changed the code of all of them (67 to 254 more instructions each, other SGPR counts).
+template <int T, bool OPEN>
 __device__ __forceinline__ void any_last(const float *x, int K, const float *wt, int pitch, const float *bias, int N, int j,
                                          int sig, float *out_row, float *logit_row) {
     float r[T];
@@ -175,11 +182,12 @@ __device__ __forceinline__ void any_last(const float *x, int K, const float *wt,
     for (int t = 0; t < T; ++t) {
         const int o = j + 16 * t;
         if (o < N) {
-            if (sig) {
+            if (OPEN ? sig == kEndSigmoid : sig != 0) {
                 out_row[o] = sigmoid_ref(r[t]);
                 if (logit_row) logit_row[o] = r[t];
             } else {
-                out_row[o] = relu_ref(r[t]);
+                if constexpr (OPEN) out_row[o] = sig == kEndNone ? r[t] : relu_ref(r[t]);
+                else out_row[o] = relu_ref(r[t]);
             }
         }
     }
@@ -290,11 +298,15 @@ __device__ __forceinline__ float any_gather1(const uint32_t *__restrict__ col, c
 //   kAnyAll     every row of [lo, hi) — a graph without heavy rows launches this and nothing else;
 //   kAnyLight   the rows of [lo, hi) below `from` entries;
 //   kAnyListed  the rows list[0 .. nlist) that lie in [lo, hi): a group's row is list[i], its sums are hsum[i * f + c]
-//               (k_any_heavy_sums below wrote them), there is no gather.
+//               (k_any_heavy_sums below wrote them), there is no gather;
+//   kAnyDense   every row of [lo, hi) of a DENSE stage (gnnvc_set_generic_patterns: a prologue in front of the first graph
+//               layer): vector A is row u of `in`, f floats, and the first K is f.  Nothing of the graph is read — no rowptr, col,
+//               w or nw, no gather, no heavy or giant split; everything behind the row build is the same source.  All of it sits
+//               behind `if constexpr`, so the other instantiations compile to what they compiled to.
 // MODE is a template argument, not a kernel argument: as a wave-uniform runtime value it cost the all-rows launch seven more
 // VGPRs and 2 % of a forward on an Erdős–Rényi graph, which has no heavy row (profiles/generic_stages/README.md, "Heavy rows");
 // kAnyAll is the kernel as it was.
-enum { kAnyAll = 0, kAnyLight = 1, kAnyListed = 2 };
+enum { kAnyAll = 0, kAnyLight = 1, kAnyListed = 2, kAnyDense = 3 };
 struct AnyRowSel {
     uint32_t from, nlist;
     const uint32_t *list;
@@ -312,15 +324,19 @@ struct AnyRowSel {
 // hsum) and up to four outputs of the last layer.  Everything it adds sits behind `if constexpr (FEAT)`, so the other twelve
 // instantiations compile to what they compiled to.  A FEAT stage within the default LDS and hidden-width bounds launches the
 // 256-thread form; one outside them needs big stages too and follows their rule for 1024 / 512 / 256 threads.
-template <int MODE, int BLOCK = kAnyBlock, bool BIG = false, bool FEAT = false>
+//
+// The OPEN form (gnnvc_set_generic_patterns) is the same source once more for a stage that ends in its bare linear layer — and for
+// every dense stage, whose instantiations are new anyway: any_last<T, true> knows the third ending.
+template <int MODE, int BLOCK = kAnyBlock, bool BIG = false, bool FEAT = false, bool OPEN = MODE == 3 /* kAnyDense */>
 __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
                                                         float *__restrict__ out, float *__restrict__ logits, uint32_t lo, uint32_t hi,
                                                         AnyShape S, int sig, AnyRowSel R) {
     extern __shared__ float4 any_lds4[];
     float *lds = reinterpret_cast<float *>(any_lds4);
     constexpr int ROWS = BLOCK / 16;
-    const StageAnyLayout L = stage_any_layout(S, ROWS);
-    const int f = S.f, d = S.d, k1 = 2 * f + 3;
+    constexpr bool dense = MODE == kAnyDense;
+    const int f = S.f, d = S.d, k1 = dense ? f : 2 * f + 3;
+    const StageAnyLayout L = stage_any_layout(S, ROWS, dense ? f : 0);
     float *bs = lds + L.bias;
     // parameters, transposed: wt[o * pitch + k] = W[k * N + o]   (W1 b1 W2 b2 ... are contiguous from P)
     {
@@ -351,45 +367,50 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
             u = R.list[u64];
             if (u < lo || u >= hi) continue;   // listed, but not in this call's range
         }
-        // ---- graph layer
-        const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
-        if (MODE == kAnyLight && re - rs >= R.from) continue;   // a heavy row: the listed-rows launch has it
-        float s0 = 0.0f, s1 = 0.0f;
-        [[maybe_unused]] float s2 = 0.0f, s3 = 0.0f;   // (FEAT: columns j + 32, j + 48)
-        if (listed) {
-            const float *hs = R.hsum + (size_t)u64 * (uint32_t)f;
-            s0 = hs[min(j, f - 1)];
-            s1 = hs[min(j + 16, f - 1)];
-            if constexpr (FEAT) {
-                s2 = hs[min(j + 32, f - 1)];
-                s3 = hs[min(j + 48, f - 1)];
-            }
-        } else if (FEAT && f > 32) {
-            if constexpr (FEAT) {
-                float sn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (f <= 48) any_gather_n<3>(g.col, in, rs, re, (uint32_t)f, j, gbase, sn);
-                else any_gather_n<4>(g.col, in, rs, re, (uint32_t)f, j, gbase, sn);
-                s0 = sn[0];
-                s1 = sn[1];
-                s2 = sn[2];
-                s3 = sn[3];
-            }
-        } else if (f == 1) {
-            s0 = any_gather1(g.col, in, rs, re, j, gbase);
-        } else if (f <= 16) {
-            any_gather<false>(g.col, in, rs, re, (uint32_t)f, j, gbase, s0, s1);
+        if constexpr (dense) {
+            // ---- the row itself: vector A = row u of `in`
+            for (int c = j; c < f; c += 16) xs[c] = in[(size_t)u * (uint32_t)f + (uint32_t)c];
         } else {
-            any_gather<true>(g.col, in, rs, re, (uint32_t)f, j, gbase, s0, s1);
-        }
-        const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
-        for (int c = j; c < k1; c += 16) {
-            float v = 0.0f;
-            if (c < f) v = c < 16 ? s0 : (!FEAT || c < 32) ? s1 : (c < 48 ? s2 : s3);
-            else if (c < 2 * f) v = in[(size_t)u * (uint32_t)f + (uint32_t)(c - f)];
-            if (c == f + 1) v = deg;
-            if (c == f + 2) v = wv;
-            if (c == f + 3) v = nwv;
-            xs[c] = v;
+            // ---- graph layer
+            const uint32_t rs = g.rowptr[u], re = g.rowptr[u + 1];
+            if (MODE == kAnyLight && re - rs >= R.from) continue;   // a heavy row: the listed-rows launch has it
+            float s0 = 0.0f, s1 = 0.0f;
+            [[maybe_unused]] float s2 = 0.0f, s3 = 0.0f;   // (FEAT: columns j + 32, j + 48)
+            if (listed) {
+                const float *hs = R.hsum + (size_t)u64 * (uint32_t)f;
+                s0 = hs[min(j, f - 1)];
+                s1 = hs[min(j + 16, f - 1)];
+                if constexpr (FEAT) {
+                    s2 = hs[min(j + 32, f - 1)];
+                    s3 = hs[min(j + 48, f - 1)];
+                }
+            } else if (FEAT && f > 32) {
+                if constexpr (FEAT) {
+                    float sn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (f <= 48) any_gather_n<3>(g.col, in, rs, re, (uint32_t)f, j, gbase, sn);
+                    else any_gather_n<4>(g.col, in, rs, re, (uint32_t)f, j, gbase, sn);
+                    s0 = sn[0];
+                    s1 = sn[1];
+                    s2 = sn[2];
+                    s3 = sn[3];
+                }
+            } else if (f == 1) {
+                s0 = any_gather1(g.col, in, rs, re, j, gbase);
+            } else if (f <= 16) {
+                any_gather<false>(g.col, in, rs, re, (uint32_t)f, j, gbase, s0, s1);
+            } else {
+                any_gather<true>(g.col, in, rs, re, (uint32_t)f, j, gbase, s0, s1);
+            }
+            const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
+            for (int c = j; c < k1; c += 16) {
+                float v = 0.0f;
+                if (c < f) v = c < 16 ? s0 : (!FEAT || c < 32) ? s1 : (c < 48 ? s2 : s3);
+                else if (c < 2 * f) v = in[(size_t)u * (uint32_t)f + (uint32_t)(c - f)];
+                if (c == f + 1) v = deg;
+                if (c == f + 2) v = wv;
+                if (c == f + 3) v = nwv;
+                xs[c] = v;
+            }
         }
         wave_lds_sync();
         // ---- the hidden layers, linear + ReLU each (A -> B -> A ...), then the last: linear + ReLU | sigmoid (-> memory)
@@ -415,10 +436,10 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
         const int n_out = S.n[d - 1];
         float *out_row = out + (size_t)u * (uint32_t)n_out;
         float *logit_row = logits ? logits + (size_t)u * (uint32_t)n_out : nullptr;   // (null unless this is the sigmoid stage)
-        if (n_out <= 16) any_last<1>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
-        else if (!FEAT || n_out <= 32) any_last<2>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
-        else if (n_out <= 48) any_last<3>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
-        else any_last<4>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        if (n_out <= 16) any_last<1, OPEN>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        else if (!FEAT || n_out <= 32) any_last<2, OPEN>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        else if (n_out <= 48) any_last<3, OPEN>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
+        else any_last<4, OPEN>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
         wave_lds_sync();   // (the group's LDS is rewritten by its next row)
     }
 }
@@ -655,9 +676,14 @@ AnyRoute stage_any_route(const StagePlan &sp) {
         if (sp.wn[l] < 1 || sp.wn[l] > (last ? fw : kAnyBigHidden)) return r;
         if (!last && sp.wn[l] > kAnySmallHidden) small = false;
     }
+    // the patterns in force (gnnvc_set_generic_patterns): a dense stage needs kPatternPrologue; a stage that is not the model's last
+    // ends in a ReLU, the model's last in the sigmoid or — with kPatternOpenEnd — in a ReLU or in its bare linear layer
+    if (sp.dense && !(sp.patterns & kPatternPrologue)) return r;
+    if (sp.end != (sp.model_last ? kEndSigmoid : kEndRelu) && !(sp.model_last && (sp.patterns & kPatternOpenEnd))) return r;
     r.feat = sp.f > kAnyMaxF || sp.wn[sp.nd - 1] > kAnyMaxLast;   // (uses the allowance: a FEAT instantiation)
     const AnyShape S = any_shape(sp);
-    r.lds256 = (size_t)stage_any_layout(S, kAnyRows).total * sizeof(float);
+    const int first_k = sp.dense ? sp.f : 0;   // (a dense stage's first K is f; 0: a graph stage's 2 f + 3)
+    r.lds256 = (size_t)stage_any_layout(S, kAnyRows, first_k).total * sizeof(float);
     if (small && r.lds256 <= kAnyLdsBytes) {
         r.ok = true;
         r.lds = r.lds256;
@@ -670,7 +696,7 @@ AnyRoute stage_any_route(const StagePlan &sp) {
     // the workgroup size: the largest whose layout fits the limit (the weights are in LDS once per workgroup, and above 80 KiB a
     // CU holds one workgroup: its waves are all there is to cover the dense layers' LDS reads; measured, 1024 against 512 against
     // 256 threads: profiles/generic_stages/README.md, "Big stages")
-    const auto bytes_at = [&](int t) { return (size_t)stage_any_layout(S, t / 16).total * sizeof(float); };
+    const auto bytes_at = [&](int t) { return (size_t)stage_any_layout(S, t / 16, first_k).total * sizeof(float); };
     const int forced = forced_big_threads();
     const int cap = forced && bytes_at(forced) <= sp.big_lds ? forced : 1024;   // (a forced size that does not fit: the rule)
     for (int t : {1024, 512}) {
@@ -690,6 +716,7 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
     const GraphDev &g = *c.g;
     const AnyRoute route = stage_any_route(sp);
     if (!route.ok || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
+    if (sp.dense && rows != AnyRows::kAll) return hipErrorInvalidValue;   // (a dense stage has no heavy or giant split)
     AnyRowSel sel{0u, 0u, nullptr, nullptr};
     if (rows == AnyRows::kLight) {
         sel = AnyRowSel{hr.from, 0u, nullptr, nullptr};
@@ -698,7 +725,7 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
         if (!hr.list || !hr.hsum) return hipErrorInvalidValue;
         sel = AnyRowSel{hr.from, hr.n, hr.list, hr.hsum};
     }
-    const AnyGraph plain{g.rowptr, g.col, g.w, g.nw};
+    const AnyGraph plain = sp.dense ? AnyGraph{nullptr, nullptr, nullptr, nullptr} : AnyGraph{g.rowptr, g.col, g.w, g.nw};   // (a dense stage reads none of it)
     const AnyShape S = any_shape(sp);
     const size_t lds = route.lds;   // <= 64 KiB, or (a big stage) <= the limit gnnvc_set_generic_big_stages was given
     // a persistent grid: as many workgroups as the LDS lets a CU hold (at most 8, and 2048 threads), on 256 CUs
@@ -710,24 +737,34 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
     const dim3 grid(std::min(need, 256u * per_cu)), block((unsigned)route.threads);
 #define GNNVC_ANY_ARGS                                                                                                        \
     grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, c.out, sp.sigmoid_last ? c.logits : nullptr, \
-        c.row_lo, c.row_hi, S, sp.sigmoid_last ? 1 : 0, sel
-#define GNNVC_ANY_LAUNCH(MODE_)                                                             \
+        c.row_lo, c.row_hi, S, sp.end, sel
+#define GNNVC_ANY_FORMS(MODE_, OPEN_)                                                       \
     do {                                                                                    \
         if (route.feat) {   /* (also within the default LDS bound: the 256-thread form) */  \
-            if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, true>), GNNVC_ANY_ARGS);     \
-            else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, true>), GNNVC_ANY_ARGS);  \
-            else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, true>), GNNVC_ANY_ARGS); \
+            if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, true, OPEN_>), GNNVC_ANY_ARGS);     \
+            else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, true, OPEN_>), GNNVC_ANY_ARGS);  \
+            else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, true, OPEN_>), GNNVC_ANY_ARGS); \
         }                                                                                   \
-        else if (!route.big) hipLaunchKernelGGL((k_stage_any<MODE_>), GNNVC_ANY_ARGS);      \
-        else if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true>), GNNVC_ANY_ARGS); \
-        else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true>), GNNVC_ANY_ARGS);   \
-        else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true>), GNNVC_ANY_ARGS);           \
+        else if (!route.big) hipLaunchKernelGGL((k_stage_any<MODE_, kAnyBlock, false, false, OPEN_>), GNNVC_ANY_ARGS);      \
+        else if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, false, OPEN_>), GNNVC_ANY_ARGS); \
+        else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, false, OPEN_>), GNNVC_ANY_ARGS);   \
+        else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, false, OPEN_>), GNNVC_ANY_ARGS);           \
+    } while (0)
+    // (OPEN: only a stage that ends in its bare linear layer leaves the instantiations that were there; a dense stage's are OPEN)
+#define GNNVC_ANY_LAUNCH(MODE_)                              \
+    do {                                                     \
+        if (sp.end == kEndNone) GNNVC_ANY_FORMS(MODE_, true); \
+        else GNNVC_ANY_FORMS(MODE_, false);                  \
     } while (0)
     switch (rows) {
-    case AnyRows::kAll: GNNVC_ANY_LAUNCH(kAnyAll); break;
+    case AnyRows::kAll:
+        if (sp.dense) GNNVC_ANY_FORMS(kAnyDense, true);
+        else GNNVC_ANY_LAUNCH(kAnyAll);
+        break;
     case AnyRows::kLight: GNNVC_ANY_LAUNCH(kAnyLight); break;
     case AnyRows::kListed: GNNVC_ANY_LAUNCH(kAnyListed); break;
     }
+#undef GNNVC_ANY_FORMS
 #undef GNNVC_ANY_LAUNCH
 #undef GNNVC_ANY_ARGS
     return hipGetLastError();
@@ -738,17 +775,21 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
 // The FEAT instantiations likewise (a wide stage may be a big one too), by gnnvc_set_generic_feature_width.
 template <bool FEAT>
 static hipError_t allow_stage_forms() {
-    static std::atomic<uint64_t> done[9];
+    static std::atomic<uint64_t> done[21];
     hipError_t rc = hipSuccess;
     int i = 0;
-#define GNNVC_ANY_ALLOW(MODE_, BLOCK_)                                                                                                  \
+#define GNNVC_ANY_ALLOW(MODE_, BLOCK_, OPEN_)                                                                                                  \
     if (rc == hipSuccess)                                                                                                               \
-        rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_stage_any<MODE_, BLOCK_, true, FEAT>), (int)kAnyBigLdsBytes, done[i]);  \
+        rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_stage_any<MODE_, BLOCK_, true, FEAT, OPEN_>), (int)kAnyBigLdsBytes, done[i]);  \
     ++i
-#define GNNVC_ANY_ALLOW3(MODE_) GNNVC_ANY_ALLOW(MODE_, 256); GNNVC_ANY_ALLOW(MODE_, 512); GNNVC_ANY_ALLOW(MODE_, 1024)
-    GNNVC_ANY_ALLOW3(kAnyAll);
-    GNNVC_ANY_ALLOW3(kAnyLight);
-    GNNVC_ANY_ALLOW3(kAnyListed);
+#define GNNVC_ANY_ALLOW3(MODE_, OPEN_) GNNVC_ANY_ALLOW(MODE_, 256, OPEN_); GNNVC_ANY_ALLOW(MODE_, 512, OPEN_); GNNVC_ANY_ALLOW(MODE_, 1024, OPEN_)
+    GNNVC_ANY_ALLOW3(kAnyAll, false);
+    GNNVC_ANY_ALLOW3(kAnyLight, false);
+    GNNVC_ANY_ALLOW3(kAnyListed, false);
+    GNNVC_ANY_ALLOW3(kAnyAll, true);      // (gnnvc_set_generic_patterns: a last stage that ends in its bare linear layer)
+    GNNVC_ANY_ALLOW3(kAnyLight, true);
+    GNNVC_ANY_ALLOW3(kAnyListed, true);
+    GNNVC_ANY_ALLOW3(kAnyDense, true);    // (... and a dense stage)
 #undef GNNVC_ANY_ALLOW3
 #undef GNNVC_ANY_ALLOW
     return rc;

@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_destroy",
     "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_set_generic_heavy_rows",
     "gnnvc_set_generic_giant_rows", "gnnvc_set_generic_big_stages", "gnnvc_set_generic_feature_width",
+    "gnnvc_set_generic_patterns",
     "gnnvc_num_layers", "gnnvc_is_fused",
     "gnnvc_in_width", "gnnvc_out_width", "gnnvc_upload_graph", "gnnvc_attach_graph_device", "gnnvc_attach_graph_slice",
     "gnnvc_graph_staging", "gnnvc_staged_columns_ready", "gnnvc_commit_staged_graph",
@@ -36,6 +37,7 @@ ABI_SYMBOLS = [
     "gnnvc_sigmoid_forward", "gnnvc_sgemm", "gnnvc_stream_sum", "gnnvc_kernel_trace",
 ]
 COL_PAD = 64
+PATTERN_PROLOGUE, PATTERN_OPEN_END = 1, 2   # GNNVC_PATTERN_*: the bits of Engine.set_generic_patterns
 ERR_AUDIT = -6   # GNNVC_ERR_AUDIT: the on-device audit (option "audit_period") found a fused stage's values wrong
 
 # gnnvc_get_info keys of the on-device audit (Engine.audit_report)
@@ -109,6 +111,7 @@ def load_library():
     L.gnnvc_set_generic_giant_rows.argtypes = [vp, u32, C.c_int]
     L.gnnvc_set_generic_big_stages.argtypes = [vp, u32]
     L.gnnvc_set_generic_feature_width.argtypes = [vp, u32]
+    L.gnnvc_set_generic_patterns.argtypes = [vp, u32]
     for name in ("gnnvc_num_layers", "gnnvc_is_fused", "gnnvc_in_width", "gnnvc_out_width",
                  "gnnvc_num_stages", "gnnvc_synchronize"):
         getattr(L, name).argtypes = [vp]
@@ -263,6 +266,17 @@ class Engine:
         effect at once: fused, num_stages and stage_widths follow.  Same bits for every value.  Raises GnnvcError -1 for any
         other value, -5 on a multi-device handle.  get_info: "generic_feature_width"."""
         self._check(self._L.gnnvc_set_generic_feature_width(self._h, max_width))
+
+    def set_generic_patterns(self, mask: int):
+        """Opt-in: generic models of other layer sequences are fused too (gnnvc_set_generic_patterns).  mask is a set of bits:
+        PATTERN_PROLOGUE (1) admits a dense stage, (Linear_Layer, activation){1..6} in front of the first Graph_Layer, as stage 0
+        (also a model of that stage alone); PATTERN_OPEN_END (2) a model whose last activation is a ReLU or is missing, so that its
+        last layer is the Linear_Layer.  0 = off, the default.  Independent of set_generic_big_stages and
+        set_generic_feature_width.  Takes effect at once: fused, num_stages and stage_widths follow.  Same bits for every mask;
+        logits are written by a model that ends in the sigmoid only.  Raises GnnvcError -1 for any other bit, -5 on a
+        multi-device handle.  get_info: "generic_patterns", "generic_stage_dense_<s>", "generic_stage_end_<s>" (0 ReLU, 1 sigmoid,
+        2 none)."""
+        self._check(self._L.gnnvc_set_generic_patterns(self._h, mask))
 
     def audit_report(self) -> dict:
         """The on-device audit's counters and its last failure (option "audit_period"), key -> value."""

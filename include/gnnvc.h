@@ -308,7 +308,9 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         gnnvc_set_generic_big_stages (below) admits, on request, stages with hidden widths up to 128 and
  *                         up to 160 KiB of LDS (keys "generic_big_lds", "generic_stage_lds_bytes_<s>",
  *                         "generic_stage_threads_<s>"), and gnnvc_set_generic_feature_width (below) input and last widths up
- *                         to 64 (key "generic_feature_width").  "audit_period" audits nothing on
+ *                         to 64 (key "generic_feature_width"), and gnnvc_set_generic_patterns (below) a dense stage in front
+ *                         of the first graph layer and a model that ends in a ReLU or in a bare linear layer (keys
+ *                         "generic_patterns", "generic_stage_dense_<s>", "generic_stage_end_<s>").  "audit_period" audits nothing on
  *                         them, as on an unfused model: they are audited on demand, by gnnvc_forward_audited,
  *                         gnnvc_forward_audited_device and gnnvc_audit_stage_device (kernel k_audit_any: a wave per row, the
  *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
@@ -424,6 +426,39 @@ int gnnvc_set_generic_big_stages(gnnvc_engine *e, uint32_t lds_bytes);
  * GNNVC_ERR_UNSUPPORTED; a null engine: GNNVC_ERR_INVALID.
  * gnnvc_get_info: "generic_feature_width" (the value in force, 0 when off). */
 int gnnvc_set_generic_feature_width(gnnvc_engine *e, uint32_t max_width);
+
+/* Layer sequences of generic models beyond (Graph_Layer, (Linear_Layer, activation){1..6})+ with a last sigmoid (opt-in).  By default
+ * a model with an input embedding in front of its first graph layer, a model cut after a stage (it ends in a ReLU) or a model that
+ * ends in a bare Linear_Layer runs one launch per layer.  mask is a set of bits:
+ *   GNNVC_PATTERN_PROLOGUE (1)   a DENSE stage — (Linear_Layer, activation){1..6} before the first Graph_Layer — is admitted as
+ *                                stage 0 of the stage list (the graph stages then number from 1); a model of that stage alone, with
+ *                                no graph layer, too.  Its bounds are a graph stage's with the first K equal to f where a graph
+ *                                stage has 2 f + 3: f and its last width at most 32 (64 under gnnvc_set_generic_feature_width), hidden
+ *                                widths at most 64 (128 under gnnvc_set_generic_big_stages), its LDS layout within the limit in force;
+ *   GNNVC_PATTERN_OPEN_END (2)   the model's last activation may be a ReLU, or be missing, so that the model's last layer is the
+ *                                Linear_Layer, whose outputs are stored as they are;
+ *   0                            off (the default): the engine behaves exactly as if this call did not exist;
+ *   any other bit                GNNVC_ERR_INVALID, the engine unchanged.
+ * With the mask the admitted pattern is [P] S*, at least one stage in all: S today's graph stage, P the dense stage; every activation a
+ * ReLU except the model's last.  A sigmoid inside the model, two Graph_Layers in a row, two Linear_Layers without an activation
+ * between them, a block of seven dense layers keep the model layer by layer under every mask, silently and with the same bits; a model
+ * of the trained shape keeps its own plans.  The call is independent of gnnvc_set_generic_big_stages and of
+ * gnnvc_set_generic_feature_width: a 48-wide prologue needs the latter too, a 128-wide hidden layer in a prologue the former.
+ * A dense stage is one k_stage_any launch over the call's rows (the kAnyDense instantiations: the row is the stage's own input row;
+ * no array of the graph is read, no row is classed heavy or giant) — a graph must still be attached, it gives the number of rows.
+ * d_logits is written by a stage that ends in the sigmoid and by no other.  gnnvc_forward, gnnvc_forward_device,
+ * gnnvc_stage_forward_device and the explicit audit calls (k_audit_any, "audit_repair" included) serve these stages as they serve any
+ * generic stage; "audit_period" goes on auditing nothing on generic models.  Results are bit-identical to the layer-by-layer forward
+ * for every mask.
+ * The call takes effect at once: the generic stage list is derived anew, and with it gnnvc_is_fused, gnnvc_num_stages,
+ * gnnvc_stage_widths and "generic_stage_layers_<s>"; an attached graph's heavy and giant rows are classed again by the next generic
+ * graph stage that runs.  A multi-device handle: GNNVC_ERR_UNSUPPORTED; a null engine: GNNVC_ERR_INVALID.
+ * gnnvc_get_info: "generic_patterns" (the mask in force), "generic_stage_dense_<s>" (1 = stage s is a dense stage, else 0) and
+ * "generic_stage_end_<s>" (0 = stage s ends in a ReLU, 1 = in the sigmoid, 2 = in its bare linear layer); both per-stage keys follow
+ * "generic_stage_layers_<s>": GNNVC_ERR_INVALID for a stage that does not exist or while the model is not generic. */
+#define GNNVC_PATTERN_PROLOGUE 1u
+#define GNNVC_PATTERN_OPEN_END 2u
+int gnnvc_set_generic_patterns(gnnvc_engine *e, uint32_t mask);
 
 /* Model introspection (what model::layers holds). */
 int gnnvc_num_layers(const gnnvc_engine *e);

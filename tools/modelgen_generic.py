@@ -63,9 +63,11 @@ def _pitch(k: int) -> int:
     return 4 * (((k + 3) // 4) | 1)
 
 
-def stage_lds_bytes(f: int, widths, rows: int = 16) -> int:
-    """stage_any_layout(...).total * 4 for a stage of input width f and these layer widths, `rows` rows a pass (threads / 16)."""
-    k, wsum, nsum, a, b = 2 * f + 3, 0, 0, 2 * f + 3, 0
+def stage_lds_bytes(f: int, widths, rows: int = 16, first_k: int = 0) -> int:
+    """stage_any_layout(...).total * 4 for a stage of input width f and these layer widths, `rows` rows a pass (threads / 16).
+    first_k: the first layer's K — 0 = a graph stage's 2 f + 3, f for a dense stage (tools/modelgen_patterns.py)."""
+    k0 = first_k if first_k else 2 * f + 3
+    k, wsum, nsum, a, b = k0, 0, 0, k0, 0
     for l, n in enumerate(widths):
         wsum += n * _pitch(k)
         nsum += n
