@@ -922,7 +922,7 @@ int gnnvc_create_multi(gnnvc_engine **out, const char *model_text, size_t len, c
     if (rc != GNNVC_OK) return rc;
     std::string err;
     try {
-        rc = gnnvc::multi_create(&e->multi, model_text, len, devices, n_devices, err);
+        rc = gnnvc::multi_create(&e->multi, model_text, len, devices, n_devices, /*generic=*/false, nullptr, err);
     } catch (const std::bad_alloc &) {
         rc = GNNVC_ERR_NOMEM;
     } catch (...) {
@@ -995,6 +995,12 @@ int gnnvc_set_option(gnnvc_engine *e, const char *key, long value) {
     return (fx & gnnvc::kFxForward) && e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
 }
 
+// The bodies of gnnvc_set_generic_big_stages / _feature_width / _patterns behind their refusal on a multi-device handle:
+// gnnvc_create_multi_generic applies its config to the front handle through these, never through the public setters.
+static int set_big_stages(gnnvc_engine *e, uint32_t lds_bytes);
+static int set_feature_width(gnnvc_engine *e, uint32_t max_width);
+static int set_patterns(gnnvc_engine *e, uint32_t mask);
+
 int gnnvc_set_generic_heavy_rows(gnnvc_engine *e, uint32_t from_degree) {
     if (!e) return GNNVC_ERR_INVALID;
     NOT_ON_MULTI(e, "gnnvc_set_generic_heavy_rows");
@@ -1013,6 +1019,10 @@ int gnnvc_set_generic_giant_rows(gnnvc_engine *e, uint32_t from_degree, int segm
 int gnnvc_set_generic_big_stages(gnnvc_engine *e, uint32_t lds_bytes) {
     if (!e) return GNNVC_ERR_INVALID;
     NOT_ON_MULTI(e, "gnnvc_set_generic_big_stages");
+    return set_big_stages(e, lds_bytes);
+}
+
+static int set_big_stages(gnnvc_engine *e, uint32_t lds_bytes) {
     if (lds_bytes != 0 && (lds_bytes < 65536u || lds_bytes > 163840u))
         return fail(e, GNNVC_ERR_INVALID, "gnnvc_set_generic_big_stages: %u is neither 0 nor within 65536 .. 163840", lds_bytes);
     if (lds_bytes == e->big_lds) return GNNVC_OK;
@@ -1033,6 +1043,10 @@ int gnnvc_set_generic_big_stages(gnnvc_engine *e, uint32_t lds_bytes) {
 int gnnvc_set_generic_feature_width(gnnvc_engine *e, uint32_t max_width) {
     if (!e) return GNNVC_ERR_INVALID;
     NOT_ON_MULTI(e, "gnnvc_set_generic_feature_width");
+    return set_feature_width(e, max_width);
+}
+
+static int set_feature_width(gnnvc_engine *e, uint32_t max_width) {
     if (max_width != 0 && (max_width <= (uint32_t)gnnvc::kAnyMaxF || max_width > (uint32_t)gnnvc::kAnyFeatMax))
         return fail(e, GNNVC_ERR_INVALID, "gnnvc_set_generic_feature_width: %u is neither 0 nor within %d .. %d", max_width,
                     gnnvc::kAnyMaxF + 1, gnnvc::kAnyFeatMax);
@@ -1054,6 +1068,10 @@ int gnnvc_set_generic_feature_width(gnnvc_engine *e, uint32_t max_width) {
 int gnnvc_set_generic_patterns(gnnvc_engine *e, uint32_t mask) {
     if (!e) return GNNVC_ERR_INVALID;
     NOT_ON_MULTI(e, "gnnvc_set_generic_patterns");
+    return set_patterns(e, mask);
+}
+
+static int set_patterns(gnnvc_engine *e, uint32_t mask) {
     if (mask & ~(uint32_t)(GNNVC_PATTERN_PROLOGUE | GNNVC_PATTERN_OPEN_END))
         return fail(e, GNNVC_ERR_INVALID, "gnnvc_set_generic_patterns: 0x%x has bits other than GNNVC_PATTERN_PROLOGUE | GNNVC_PATTERN_OPEN_END", mask);
     static_assert(GNNVC_PATTERN_PROLOGUE == gnnvc::kPatternPrologue && GNNVC_PATTERN_OPEN_END == gnnvc::kPatternOpenEnd, "one mask");
@@ -1061,6 +1079,56 @@ int gnnvc_set_generic_patterns(gnnvc_engine *e, uint32_t mask) {
     e->patterns = mask;             // (no LDS limit to raise: a dense stage outside the default bounds needs the big or feat call, which raise theirs)
     plan_generic(e);                // (at once, as gnnvc_set_generic_big_stages)
     e->pg.heavy_known = false;      // an attached graph is classed again by the next generic graph stage that runs (class_heavy_rows)
+    return GNNVC_OK;
+}
+
+// gnnvc_create_multi with the generic opt-ins made at creation (the setters stay refused on the handle).  Everything that can be
+// refused without a device is refused before one is touched.
+int gnnvc_create_multi_generic(gnnvc_engine **out, const char *model_text, size_t len, const int *devices, int n_devices,
+                               const gnnvc_generic_config *cfg) {
+    if (out) *out = nullptr;
+    if (!out || !model_text || !devices || n_devices < 1) return GNNVC_ERR_INVALID;
+    gnnvc_generic_config c{(uint32_t)sizeof(gnnvc_generic_config), GNNVC_GENERIC_DEFAULT, GNNVC_GENERIC_DEFAULT, -1, 0, 0, 0};
+    if (cfg) {
+        if (cfg->size != sizeof(gnnvc_generic_config)) return GNNVC_ERR_INVALID;
+        c = *cfg;
+    }
+    // (what the matching single-device setter would reject; the heavy and giant thresholds and the segments take any value)
+    if (c.big_stages_lds != 0 && (c.big_stages_lds < 65536u || c.big_stages_lds > 163840u)) return GNNVC_ERR_INVALID;
+    if (c.feature_width != 0 && (c.feature_width <= (uint32_t)gnnvc::kAnyMaxF || c.feature_width > (uint32_t)gnnvc::kAnyFeatMax)) return GNNVC_ERR_INVALID;
+    if (c.patterns & ~(uint32_t)(GNNVC_PATTERN_PROLOGUE | GNNVC_PATTERN_OPEN_END)) return GNNVC_ERR_INVALID;
+    gnnvc_engine *e = nullptr;
+    int rc = gnnvc_create(&e, model_text, len, devices[0]);
+    if (rc != GNNVC_OK) return rc;
+    // the front handle answers gnnvc_num_stages, gnnvc_stage_widths, "generic_patterns", "generic_stage_layers_<s>" ... as a single
+    // engine with the same settings would (a model of the trained shape keeps its own plans: the config has no effect on it)
+    if (e->stages.empty()) {
+        if (c.heavy_rows != GNNVC_GENERIC_DEFAULT) e->heavy_from = c.heavy_rows;
+        if (c.giant_rows != GNNVC_GENERIC_DEFAULT) e->ggiant_from = c.giant_rows;
+        e->ggiant_segments = c.giant_segments;
+        if (rc == GNNVC_OK && c.big_stages_lds) rc = set_big_stages(e, c.big_stages_lds);
+        if (rc == GNNVC_OK && c.feature_width) rc = set_feature_width(e, c.feature_width);
+        if (rc == GNNVC_OK && c.patterns) rc = set_patterns(e, c.patterns);
+    }
+    std::string err;
+    if (rc == GNNVC_OK) {
+        try {
+            rc = gnnvc::multi_create(&e->multi, model_text, len, devices, n_devices, /*generic=*/true, &c, err);
+        } catch (const std::bad_alloc &) {
+            rc = GNNVC_ERR_NOMEM;
+        } catch (...) {
+            rc = GNNVC_ERR_INVALID;
+        }
+    } else {
+        err = e->err;
+    }
+    if (rc != GNNVC_OK) {
+        if (!err.empty()) fprintf(stderr, "gnnvc_create_multi_generic: %s\n", err.c_str());
+        gnnvc_destroy(e);
+        return rc;
+    }
+    (void)hipSetDevice(devices[0]);
+    *out = e;
     return GNNVC_OK;
 }
 
@@ -1086,6 +1154,10 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     }
     else if (e->multi && k.rfind("audit_", 0) == 0) {   // the parts' audits (gnnvc_multi.cpp)
         if (!gnnvc::multi_audit_info(e->multi, key, value)) return GNNVC_ERR_INVALID;
+    }
+    else if (e->multi && gnnvc::multi_is_generic(e->multi) &&   // the parts' classings summed (the front itself holds no graph)
+             (k == "generic_heavy_rows" || k == "generic_heavy_entries" || k == "generic_giant_rows" || k == "generic_giant_entries")) {
+        if (!gnnvc::multi_sum_info(e->multi, key, value)) return GNNVC_ERR_INVALID;
     }
     else if (k == "generic_stages" || k == "plans_at_handoff" || k == "mfma_dense") (void)gnnvc::read_option(e->opt, key, value);   // (as set)
     else if (k == "generic_stages_model") *value = e->generic_on() ? 1 : 0;   // would a forward run k_stage_any now
@@ -1782,6 +1854,8 @@ static int forward_device_impl(gnnvc_engine *e, const float *d_x, float *d_score
         if (rc) return rc;
         HIP_TRY(e, hipStreamSynchronize(e->stream));   // (whatever produced d_x on this handle's stream)
         std::string err;
+        // (generic parts audit on demand only, as a single generic engine: "audit_period" audits nothing on such a handle)
+        if (gnnvc::multi_is_generic(e->multi)) audit = explicit_audit;
         rc = gnnvc::multi_forward_device(e->multi, d_x, d_scores, d_logits, audit, err);
         (void)hipSetDevice(e->device);
         if (rc) rc = fail(e, rc, "%s", err.c_str());
@@ -2006,13 +2080,14 @@ static int forward_host(gnnvc_engine *e, const float *x, float *scores, float *l
         if (!x || !scores) return fail(e, GNNVC_ERR_INVALID, "null host buffers");
         int rc = use_device(e);
         if (rc) return rc;
-        const size_t bytes = (size_t)n * sizeof(float);
-        HIP_TRY(e, hipMemcpyAsync(e->x.p, x, bytes, hipMemcpyHostToDevice, e->stream));
+        const size_t in_b = (size_t)n * e->in_width * sizeof(float);   // (1 x 1 for the trained model; a generic model's own widths)
+        const size_t out_b = (size_t)n * e->out_width * sizeof(float);
+        HIP_TRY(e, hipMemcpyAsync(e->x.p, x, in_b, hipMemcpyHostToDevice, e->stream));
         const bool want_logits = logits && e->ends_in_sigmoid;
         rc = device_forward(e, e->x.p, e->scores.p, want_logits ? e->logits.p : nullptr);
         if (rc && rc != GNNVC_ERR_AUDIT) return rc;   // (a failed audit: the outputs as the fused path wrote them, and the error)
-        HIP_TRY(e, hipMemcpyAsync(scores, e->scores.p, bytes, hipMemcpyDeviceToHost, e->stream));
-        if (want_logits) HIP_TRY(e, hipMemcpyAsync(logits, e->logits.p, bytes, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipMemcpyAsync(scores, e->scores.p, out_b, hipMemcpyDeviceToHost, e->stream));
+        if (want_logits) HIP_TRY(e, hipMemcpyAsync(logits, e->logits.p, out_b, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(e, hipStreamSynchronize(e->stream));
         return rc;
     }
@@ -2168,6 +2243,20 @@ int gnnvc_push_piece(gnnvc_engine *e, const float *d_region, uint32_t rows, uint
     int rc = use_device(e);
     if (rc) return rc;
     HIP_TRY(e, gnnvc::push_piece(d_region, rows, kp, exc_cap, n_dst, d_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream));
+    return GNNVC_OK;
+}
+
+int gnnvc_push_rows(gnnvc_engine *e, const float *d_src, uint64_t words, uint32_t n_dst, float *const *d_dst, void *hip_stream) {
+    if (!e) return GNNVC_ERR_INVALID;
+    if (n_dst > 64) return fail(e, GNNVC_ERR_INVALID, "push of %u destinations (at most 64)", n_dst);
+    if (n_dst && !d_dst) return fail(e, GNNVC_ERR_INVALID, "null device buffers");
+    for (uint32_t i = 0; i < n_dst; ++i)
+        if (!d_dst[i] || (reinterpret_cast<uintptr_t>(d_dst[i]) & 3u)) return fail(e, GNNVC_ERR_INVALID, "destination %u is null or not 4-byte aligned", i);
+    if (!n_dst || !words) return GNNVC_OK;
+    if (!d_src || (reinterpret_cast<uintptr_t>(d_src) & 3u)) return fail(e, GNNVC_ERR_INVALID, "the source is null or not 4-byte aligned");
+    int rc = use_device(e);
+    if (rc) return rc;
+    HIP_TRY(e, gnnvc::push_rows(d_src, (size_t)words, n_dst, d_dst, hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream));
     return GNNVC_OK;
 }
 

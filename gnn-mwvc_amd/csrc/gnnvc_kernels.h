@@ -538,6 +538,9 @@ struct UnpackPiece {
 };
 hipError_t push_piece(const float *region, uint32_t rows, uint32_t kp, uint32_t cap, uint32_t n_dst, float *const *dst, hipStream_t stream);
 hipError_t unpack_pieces(const UnpackPiece *pieces, uint32_t n_pieces, uint32_t cap, uint32_t mask, uint32_t kp, float *feat, hipStream_t stream);
+// ... and of generic-stage models: `words` floats from src (any 4-byte boundary) stored to each of n_dst (<= 64) destinations in one
+// launch (k_push_rows): 16 bytes per lane where every destination has the source's 16-byte phase, else 4.  words == 0: nothing
+hipError_t push_rows(const float *src, size_t words, uint32_t n_dst, float *const *dst, hipStream_t stream);
 
 // Reduction-rule predicates per vertex (one byte each) on the device CSR; see the kernel.
 hipError_t launch_reduction_flags(const GraphDev &g, uint32_t max_degree, uint8_t *flags, hipStream_t stream);

@@ -4312,6 +4312,29 @@ __global__ __launch_bounds__(256) void k_push_piece(const float *__restrict__ sr
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)count + 1; i += stride) o4[i] = e4[i];
 }
 
+// Full rows of a generic-stage model to every peer (gnnvc_create_multi_generic): rows [r0, r1) of a row-major n x f matrix are one
+// run of `words` floats that starts and ends at any 4-byte boundary (f is 1 .. 64).  Destination blockIdx.y gets the run at its
+// own pointer.  kVec: source and destination share their 16-byte phase (the launcher has checked every destination) — up to three
+// head words as scalars until the source is 16-byte aligned, the body 16 bytes per lane, up to three tail words as scalars.
+// !kVec: 4 bytes per lane throughout, for destinations of another phase.
+template <bool kVec>
+__global__ __launch_bounds__(256) void k_push_rows(const float *__restrict__ src, size_t words, PushDst dst) {
+    float *__restrict__ out = dst.p[blockIdx.y];
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    if constexpr (!kVec) {
+        for (size_t i = tid; i < words; i += stride) out[i] = src[i];
+    } else {
+        const size_t head = min(words, (size_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15u)) & 15u) / 4u);
+        if (tid < head) out[tid] = src[tid];
+        const size_t quads = (words - head) / 4;
+        const float4 *__restrict__ s4 = reinterpret_cast<const float4 *>(src + head);
+        float4 *__restrict__ d4 = reinterpret_cast<float4 *>(out + head);
+        for (size_t i = tid; i < quads; i += stride) d4[i] = s4[i];
+        const size_t done = head + 4 * quads;
+        if (tid < words - done) out[done + tid] = src[done + tid];
+    }
+}
+
 struct PieceRef {
     const float *region;
     uint32_t row_lo, row_hi;
@@ -5828,6 +5851,27 @@ hipError_t push_piece(const float *region, uint32_t rows, uint32_t kp, uint32_t 
     // (a modest grid per destination: the stores are paced by the links, and the CUs are wanted by the next piece's kernels)
     const unsigned bx = (unsigned)std::min<size_t>(std::max<size_t>((dense_words / 4 + 255) / 256, 1), 64);
     GNNVC_LAUNCH(k_push_piece, dim3(bx, n_dst), dim3(256), 0, stream, region, dense_words, cap, pd);
+    return hipGetLastError();
+}
+
+hipError_t push_rows(const float *src, size_t words, uint32_t n_dst, float *const *dst, hipStream_t stream) {
+    if (!n_dst || !words) return hipSuccess;
+    if (n_dst > 64 || !src || !dst || (reinterpret_cast<uintptr_t>(src) & 3u)) return hipErrorInvalidValue;
+    PushDst pd{};
+    bool same_phase = true;
+    for (uint32_t i = 0; i < n_dst; ++i) {
+        if (!dst[i] || (reinterpret_cast<uintptr_t>(dst[i]) & 3u)) return hipErrorInvalidValue;
+        same_phase = same_phase && ((reinterpret_cast<uintptr_t>(dst[i]) ^ reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
+        pd.p[i] = dst[i];
+    }
+    // (a modest grid per destination, as push_piece: the stores are paced by the links, the CUs are wanted by the next piece's kernels)
+    if (same_phase) {
+        const unsigned bx = (unsigned)std::min<size_t>(std::max<size_t>((words / 4 + 255) / 256, 1), 64);
+        GNNVC_LAUNCH(k_push_rows<true>, dim3(bx, n_dst), dim3(256), 0, stream, src, words, pd);
+    } else {   // one destination of another phase: the whole launch stores 4 bytes per lane, never a misaligned 16-byte store
+        const unsigned bx = (unsigned)std::min<size_t>(std::max<size_t>((words + 255) / 256, 1), 64);
+        GNNVC_LAUNCH(k_push_rows<false>, dim3(bx, n_dst), dim3(256), 0, stream, src, words, pd);
+    }
     return hipGetLastError();
 }
 

@@ -14,6 +14,9 @@
 // (gnnvc_unpack_pieces).  Parts synchronise through HIP events only; the host threads only tell each other when an
 // event has been recorded.  A row is still summed on one device in stored order: the bits are those of the
 // single-device engine.  No reference counterpart.
+//
+// All of that is the TRAINED model's route (forward_part).  A model that is a generic stage list (gnnvc_create_multi_generic)
+// takes a route of its own, forward_part_generic: S stages of any widths, full rows to every peer (gnnvc_push_rows), no packing.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -62,6 +65,7 @@ struct Part {
     Event packed[2][kMaxPieces];          // piece k of stage s is computed (and packed): on `stream`
     Event pushed[2][kMaxPieces];          // ... and has reached every peer: on `copy`
     Event t0, t1;                         // this part's span of the last forward (timing enabled)
+    std::vector<Event> gdone, gpushed;    // the generic route's, [s * kMaxPieces + k] for its S - 1 exchanged stages: computed / at every peer
     uint64_t counts[2][16] = {{0}};                   // first forward on a graph: non-zeros per column of my rows of stage s
     int rc = GNNVC_OK;                                // of the job at hand
     std::string err;
@@ -80,6 +84,14 @@ struct MultiState {
     bool have_graph = false;
     int stages = 0;
     double last_ms = 0.0;
+    // the generic route (gnnvc_create_multi_generic, a model that is a generic stage list): forward_part_generic instead of
+    // forward_part, full rows of any width instead of the 16-wide codec
+    bool generic = false;
+    std::vector<int> gw_out;     // stage s writes rows of gw_out[s] floats
+    std::vector<char> gdense;    // stage s has no graph layer (admitted at s = 0 only, multi_create)
+    int in_width = 1, out_width = 1, wmax = 1;   // wmax: the widest intermediate stage output (the ping-pong buffers' row)
+    bool ends_in_sigmoid = true;
+    bool fw_audit = false;       // this forward is audited: k_audit_any right behind every piece's stage call
     bool peer_stores = true;     // every pair of distinct devices can store into each other's memory
     // options (gnnvc_set_option on the front handle: keys "multi_*", and what the front hands on — kMultiRows)
     struct Opts {
@@ -164,6 +176,53 @@ void fail_job(MultiState *m) {
     m->failed.store(1, std::memory_order_release);
     std::lock_guard<std::mutex> lk(m->bar_mu);
     m->bar_cv.notify_all();
+}
+
+// the generic route's description of the model, from part 0's stage list (every part read the same text under the same config), and
+// what is sized by it: the events and the `rec` cells of its S - 1 exchanges
+int describe_generic(MultiState *m, std::string &err) {
+    gnnvc_engine *e0 = m->parts[0].eng;
+    const int S = m->stages;
+    m->gw_out.assign((size_t)S, 0);
+    m->gdense.assign((size_t)S, 0);
+    m->in_width = gnnvc_in_width(e0);
+    m->out_width = gnnvc_out_width(e0);
+    m->wmax = 1;
+    for (int s = 0; s < S; ++s) {
+        int fin = 0, fout = 0;
+        long dense = 0, end = 0;
+        const std::string at = std::to_string(s);
+        if (gnnvc_stage_widths(e0, s, &fin, &fout) != GNNVC_OK || gnnvc_get_info(e0, ("generic_stage_dense_" + at).c_str(), &dense) != GNNVC_OK ||
+            gnnvc_get_info(e0, ("generic_stage_end_" + at).c_str(), &end) != GNNVC_OK) {
+            err = "reading the generic stage list failed";
+            return GNNVC_ERR_STATE;
+        }
+        // the ordering invariant (forward_part_generic) holds for the admitted pattern [P] S*: the one stage that does not wait for
+        // its peers, a dense one, stands at position 0 only
+        if (dense && s > 0) {
+            err = "a dense stage behind the first one: the exchange's ordering does not cover it";
+            return GNNVC_ERR_UNSUPPORTED;
+        }
+        m->gw_out[(size_t)s] = fout;
+        m->gdense[(size_t)s] = dense ? 1 : 0;
+        if (s + 1 < S) m->wmax = std::max(m->wmax, fout);
+        if (s + 1 == S) m->ends_in_sigmoid = end == 1;
+    }
+    const size_t cells = (size_t)std::max(S - 1, 1) * kMaxPieces;
+    m->rec = std::vector<std::atomic<uint64_t>>(m->parts.size() * cells);
+    for (auto &c : m->rec) c.store(0);
+    for (Part &p : m->parts) {
+        hipError_t h = hipSetDevice(p.device);
+        p.gdone.resize((size_t)(S - 1) * kMaxPieces);
+        p.gpushed.resize((size_t)(S - 1) * kMaxPieces);
+        for (size_t i = 0; i < p.gdone.size() && h == hipSuccess; ++i) {
+            h = p.gdone[i].create(hipEventDisableTiming);
+            if (h == hipSuccess) h = p.gpushed[i].create(hipEventDisableTiming);
+        }
+        if (h != hipSuccess) return hip_fail(err, h, "event creation");
+    }
+    m->generic = true;
+    return GNNVC_OK;
 }
 
 int pieces_for(const MultiState *m) {
@@ -260,13 +319,23 @@ int upload_part(MultiState *m, Part &p, std::string &err) {
     MTRY(p.w.reserve(std::max<uint32_t>(rows, 1u)));
     MTRY(p.nw.reserve(std::max<uint32_t>(rows, 1u)));
     const size_t frows = (size_t)n + 1;
-    MTRY(p.x.reserve(frows));
-    MTRY(p.h[0].reserve(frows * 16));
-    MTRY(p.h[1].reserve(frows * 16));
-    MTRY(p.scores.reserve(frows));
-    MTRY(p.logits.reserve(frows));
-    MTRY(p.flag.reserve(2));
-    MTRY(p.flag_pin.reserve(4));
+    if (m->generic) {
+        // every buffer a forward writes — this part's kernels or a peer's stores — is reserved HERE, never inside a forward: the
+        // route needs no barrier of the workers.  Generic stages read no pad row: n rows each.
+        MTRY(p.x.reserve((size_t)n * (size_t)m->in_width));
+        if (m->stages > 1)
+            for (auto &h : p.h) MTRY(h.reserve((size_t)n * (size_t)m->wmax));
+        MTRY(p.scores.reserve((size_t)n * (size_t)m->out_width));
+        MTRY(p.logits.reserve((size_t)n * (size_t)m->out_width));
+    } else {
+        MTRY(p.x.reserve(frows));
+        MTRY(p.h[0].reserve(frows * 16));
+        MTRY(p.h[1].reserve(frows * 16));
+        MTRY(p.scores.reserve(frows));
+        MTRY(p.logits.reserve(frows));
+        MTRY(p.flag.reserve(2));
+        MTRY(p.flag_pin.reserve(4));
+    }
     std::vector<uint32_t> local((size_t)rows + 1);
     for (uint32_t i = 0; i <= rows; ++i) local[i] = (uint32_t)(rp(p.lo + i) - first);
     MTRY(hipMemcpyAsync(p.rowptr.p, local.data(), ((size_t)rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p.stream));
@@ -277,7 +346,8 @@ int upload_part(MultiState *m, Part &p, std::string &err) {
         MTRY(hipMemcpyAsync(p.nw.p, m->up_nw + p.lo, (size_t)rows * sizeof(uint32_t), hipMemcpyHostToDevice, p.stream));
     }
     // the pad rows of the 16-wide feature buffers read as zero: no kernel ever writes them, once per graph will do
-    for (auto &h : p.h) MTRY(hipMemsetAsync(h.p + (size_t)n * 16, 0, 16 * sizeof(float), p.stream));
+    if (!m->generic)
+        for (auto &h : p.h) MTRY(hipMemsetAsync(h.p + (size_t)n * 16, 0, 16 * sizeof(float), p.stream));
     MTRY(hipStreamSynchronize(p.stream));   // (`local` leaves scope; the attach below reads the arrays on the same stream anyway)
     if (n == 0) return GNNVC_OK;
     PTRY(p, gnnvc_attach_graph_slice(p.eng, n, p.lo, p.hi, p.nnz, p.rowptr.p, p.col.p, p.w.p, p.nw.p), "gnnvc_attach_graph_slice");
@@ -434,6 +504,117 @@ int forward_part(MultiState *m, Part &me, std::string &err) {
     return GNNVC_OK;
 }
 
+// ------------------------------------------------------------------ the generic route (gnnvc_create_multi_generic)
+// A model that is a generic stage list: S stages of any widths, every row computed by k_stage_any on one device in stored order
+// (gnnvc_stage_forward_device on the part's slice, heavy and giant rows included), so the bits are the single engine's.  After
+// every stage but the last a part ships the rows it computed, as FULL rows of gw_out[s] floats, straight into every peer's
+// ping-pong buffer of that stage: one k_push_rows launch for all peers (gnnvc_push_rows) or one hipMemcpyPeerAsync per peer.
+// Nothing is packed, nothing is chosen by a first forward, nothing is reserved here: no barrier of the workers.
+//
+// THE ORDERING INVARIANT.  Stage s reads buffer (s - 1) & 1 and writes buffer s & 1, so a peer's stage-s rows land in my buffer
+// s & 1 — which is also the INPUT of my stage s - 1.  That is safe only because
+//   - a peer cannot start graph stage s before it holds all my pieces of stage s - 1 (it waits for every pushed event), and
+//   - I ship my last piece of stage s - 1 after my last stage-(s - 1) kernel (the event behind it, in my stream's order),
+// so by the time a peer's stage-s row arrives my stage s - 1 has read its input to the end.  The same two facts keep my own
+// stage-(s + 2) kernels, which write my rows of buffer s & 1 again, behind the copies that still read my stage-s rows from it.
+// The one stage that waits for nobody is a dense stage (it reads its own rows only): multi_create admits it at s = 0 only.
+std::atomic<uint64_t> &gen_cell(MultiState *m, int r, int s, int k) {
+    return m->rec[((size_t)r * (size_t)std::max(m->stages - 1, 1) + (size_t)s) * kMaxPieces + (size_t)k];
+}
+
+// wait_piece for the generic route's cells and events
+int wait_rows(MultiState *m, Part &me, int r, int s, int k, std::string &err) {
+    std::atomic<uint64_t> &cell = gen_cell(m, r, s, k);
+    int spins = 0;
+    while (cell.load(std::memory_order_acquire) != m->epoch) {
+        if (m->failed.load(std::memory_order_acquire)) {
+            err = "another part of the forward failed";
+            return GNNVC_ERR_STATE;
+        }
+        if (++spins > 64) std::this_thread::yield();
+    }
+    MTRY(hipStreamWaitEvent(me.stream, m->parts[(size_t)r].gpushed[(size_t)s * kMaxPieces + k], 0));
+    return GNNVC_OK;
+}
+
+// ship_piece for full rows of any width: rows [cut[k], cut[k + 1]) of stage s, which `me` just computed into `out`
+int ship_rows(MultiState *m, Part &me, int s, int k, float *out, std::string &err) {
+    const size_t P = m->parts.size(), f = (size_t)m->gw_out[(size_t)s], at = (size_t)s * kMaxPieces + (size_t)k;
+    const uint32_t r0 = me.cut[k], r1 = me.cut[k + 1];
+    const float *src = out + (size_t)r0 * f;
+    const uint64_t words = (uint64_t)(r1 - r0) * f;
+    MTRY(hipEventRecord(me.gdone[at], me.stream));
+    MTRY(hipStreamWaitEvent(me.copy, me.gdone[at], 0));
+    if (m->opt.push && m->peer_stores) {   // (source and destinations share the row index and width in 256-byte-aligned buffers: one 16-byte phase)
+        float *dst[64];
+        uint32_t nd = 0;
+        for (size_t q = 0; q < P; ++q)
+            if ((int)q != me.index) dst[nd++] = m->parts[q].h[s & 1].p + (size_t)r0 * f;
+        PTRY(me, gnnvc_push_rows(me.eng, src, words, nd, dst, me.copy), "gnnvc_push_rows");
+    } else {
+        for (size_t q = 0; q < P; ++q)
+            if ((int)q != me.index)
+                MTRY(hipMemcpyPeerAsync(m->parts[q].h[s & 1].p + (size_t)r0 * f, m->parts[q].device, src, me.device, (size_t)words * sizeof(float),
+                                        me.copy));
+    }
+    MTRY(hipEventRecord(me.gpushed[at], me.copy));
+    gen_cell(m, me.index, s, k).store(m->epoch, std::memory_order_release);
+    return GNNVC_OK;
+}
+
+int forward_part_generic(MultiState *m, Part &me, std::string &err) {
+    const uint32_t n = m->n;
+    const size_t P = m->parts.size();
+    const int dev0 = m->parts[0].device, S = m->stages;
+    const bool solo = m->opt.only_part >= 0;
+    if (solo && m->opt.only_part != me.index) return GNNVC_OK;
+    MTRY(hipSetDevice(me.device));
+    MTRY(hipEventRecord(me.t0, me.stream));
+    MTRY(hipMemcpyPeerAsync(me.x.p, me.device, m->fw_x, dev0, (size_t)n * (size_t)m->in_width * sizeof(float), me.stream));   // the input, replicated
+    hipEvent_t last_push = nullptr;
+    for (int s = 0; s < S; ++s) {
+        const bool last = s + 1 == S;
+        const float *in = s == 0 ? me.x.p : me.h[(s - 1) & 1].p;
+        float *out = last ? me.scores.p : me.h[s & 1].p;
+        // a graph stage's input is complete on this device once every peer's pieces of the last stage have landed (a dense stage
+        // reads its own rows only and waits for nothing; empty pieces were never shipped)
+        if (s >= 1 && P > 1 && !solo && !m->gdense[(size_t)s])
+            for (size_t r = 0; r < P; ++r) {
+                const Part &pr = m->parts[r];
+                if ((int)r == me.index) continue;
+                for (int k = 0; k < pr.pieces; ++k)
+                    if (pr.cut[k + 1] > pr.cut[k]) {
+                        const int rc = wait_rows(m, me, (int)r, s - 1, k, err);
+                        if (rc) return rc;
+                    }
+            }
+        for (int k = 0; k < me.pieces; ++k) {
+            const uint32_t r0 = me.cut[k], r1 = me.cut[k + 1];
+            if (r1 <= r0) continue;   // (an empty piece, an empty part: no launch, nothing shipped, nobody waits for it)
+            PTRY(me, gnnvc_stage_forward_device(me.eng, s, r0, r1, in, out, last ? me.logits.p : nullptr), "gnnvc_stage_forward_device");
+            // an audited forward: k_audit_any over the piece right behind its stage call (it synchronises this part's stream; the
+            // part's engine is quiet, so a mismatch is counted — or repaired, before the rows leave — and the worker goes on)
+            if (m->fw_audit)
+                PTRY(me, gnnvc_audit_stage_device(me.eng, s, r0, r1, in, out, last ? me.logits.p : nullptr), "gnnvc_audit_stage_device");
+            if (!last && P > 1) {
+                const int rc = ship_rows(m, me, s, k, out, err);
+                if (rc) return rc;
+                last_push = me.gpushed[(size_t)s * kMaxPieces + (size_t)k];
+            }
+        }
+        if (last && me.hi > me.lo && !solo) {   // the scores (and logits) of these rows, to the caller's arrays on the first device
+            const size_t ow = (size_t)m->out_width, words = (size_t)(me.hi - me.lo) * ow;
+            MTRY(hipMemcpyPeerAsync(m->fw_scores + (size_t)me.lo * ow, dev0, me.scores.p + (size_t)me.lo * ow, me.device, words * sizeof(float), me.stream));
+            if (m->fw_logits && m->ends_in_sigmoid)
+                MTRY(hipMemcpyPeerAsync(m->fw_logits + (size_t)me.lo * ow, dev0, me.logits.p + (size_t)me.lo * ow, me.device, words * sizeof(float),
+                                        me.stream));
+        }
+    }
+    if (last_push) MTRY(hipStreamWaitEvent(me.stream, last_push, 0));   // (the span ends when the last push has landed: the copy stream runs in order)
+    MTRY(hipEventRecord(me.t1, me.stream));
+    return GNNVC_OK;
+}
+
 // whatever happened: nothing of this part's work is left in flight when the job returns (a failed forward must not
 // leave kernels and peer copies writing into the caller's arrays behind an error return)
 void drain_part(Part &p) {
@@ -457,7 +638,7 @@ void worker(MultiState *m, Part *p) {
         p->err.clear();
         p->rc = GNNVC_OK;
         if (job == kUpload) p->rc = upload_part(m, *p, p->err);
-        else if (job == kForward) p->rc = forward_part(m, *p, p->err);
+        else if (job == kForward) p->rc = m->generic ? forward_part_generic(m, *p, p->err) : forward_part(m, *p, p->err);
         if (p->rc != GNNVC_OK) fail_job(m);
         if (job == kForward) {
             drain_part(*p);
@@ -505,7 +686,23 @@ int run_job(MultiState *m, int job, std::string &err) {
 
 }  // namespace
 
-int multi_create(MultiState **out, const char *model_text, size_t len, const int *devices, int n_devices, std::string &err) {
+// the generic opt-ins of gnnvc_create_multi_generic on one part's engine (an ordinary engine: the public setters)
+static int apply_generic_config(gnnvc_engine *e, const gnnvc_generic_config &c) {
+    int rc = GNNVC_OK;
+    if (c.heavy_rows != GNNVC_GENERIC_DEFAULT) rc = gnnvc_set_generic_heavy_rows(e, c.heavy_rows);
+    if (rc == GNNVC_OK && (c.giant_rows != GNNVC_GENERIC_DEFAULT || c.giant_segments != -1)) {
+        long from = 0;
+        (void)gnnvc_get_info(e, "generic_giant_from", &from);
+        rc = gnnvc_set_generic_giant_rows(e, c.giant_rows != GNNVC_GENERIC_DEFAULT ? c.giant_rows : (uint32_t)from, c.giant_segments);
+    }
+    if (rc == GNNVC_OK && c.big_stages_lds) rc = gnnvc_set_generic_big_stages(e, c.big_stages_lds);
+    if (rc == GNNVC_OK && c.feature_width) rc = gnnvc_set_generic_feature_width(e, c.feature_width);
+    if (rc == GNNVC_OK && c.patterns) rc = gnnvc_set_generic_patterns(e, c.patterns);
+    return rc;
+}
+
+int multi_create(MultiState **out, const char *model_text, size_t len, const int *devices, int n_devices, bool generic,
+                 const gnnvc_generic_config *cfg, std::string &err) {
     *out = nullptr;
     if (!devices || n_devices < 1 || n_devices > 64) {
         err = "gnnvc_create_multi: 1 .. 64 devices";
@@ -541,8 +738,14 @@ int multi_create(MultiState **out, const char *model_text, size_t len, const int
         // a part records its audits without failing its stage calls: the job's barriers do not recover from a part that gives
         // up, so mismatches are reported by multi_forward_device once the job has drained
         rc = gnnvc_set_option(p.eng, "audit_quiet", 1);
+        // (gnnvc_create_multi_generic: the config before the stage list is read; a model of the trained shape keeps its own plans and
+        // the config has no effect on it)
+        long part_generic = 0;
+        if (rc == GNNVC_OK && generic && cfg && gnnvc_get_info(p.eng, "generic_stages_model", &part_generic) == GNNVC_OK &&
+            !(gnnvc_is_fused(p.eng) && part_generic == 0))
+            rc = apply_generic_config(p.eng, *cfg);
         if (rc != GNNVC_OK) {
-            err = "setting up a per-device engine failed";
+            err = std::string("setting up a per-device engine failed: ") + gnnvc_last_error(p.eng);
             break;
         }
         hipError_t h = hipSetDevice(p.device);
@@ -584,10 +787,13 @@ int multi_create(MultiState **out, const char *model_text, size_t len, const int
         m->stages = gnnvc_num_stages(m->parts[0].eng);
         // (a three-stage model of other widths reports fused too — option "generic_stages" — but the packers, the exchange and the
         // plans here are made for the trained shape's 16-wide rows)
-        long generic = 0;
-        (void)gnnvc_get_info(m->parts[0].eng, "generic_stages_model", &generic);
-        if (m->stages != 3 || !gnnvc_is_fused(m->parts[0].eng) || generic != 0) {
-            err = "a multi-device handle runs the fused three-stage model of the trained widths only";
+        long is_generic = 0;
+        (void)gnnvc_get_info(m->parts[0].eng, "generic_stages_model", &is_generic);
+        if (generic && is_generic != 0 && m->stages >= 1 && gnnvc_is_fused(m->parts[0].eng)) {
+            rc = describe_generic(m, err);   // gnnvc_create_multi_generic and a generic stage list: the generic route
+        } else if (m->stages != 3 || !gnnvc_is_fused(m->parts[0].eng) || is_generic != 0) {
+            err = generic ? "the model stays layer by layer under this config: a multi-device handle runs fused stages only"
+                          : "a multi-device handle runs the fused three-stage model of the trained widths only";
             rc = GNNVC_ERR_UNSUPPORTED;
         }
     }
@@ -649,9 +855,35 @@ static uint64_t shipped_bytes(MultiState *m, const Part &p, int s) {
     return bytes;
 }
 
+bool multi_is_generic(const MultiState *m) { return m && m->generic; }
+
+bool multi_sum_info(MultiState *m, const char *key, long *value) {
+    long total = 0;
+    for (const Part &p : m->parts) {
+        long v = 0;
+        if (gnnvc_get_info(p.eng, key, &v) != GNNVC_OK) return false;
+        total += v;
+    }
+    *value = total;
+    return true;
+}
+
 bool multi_get_info(MultiState *m, const char *key, long *value) {
     const std::string k(key);
-    if (k == "multi_pieces") *value = m->parts.empty() ? 0 : m->parts[0].pieces;
+    static const char kBytes[] = "multi_exchange_bytes_per_peer_stage";
+    if (k == "multi_generic") *value = m->generic ? 1 : 0;
+    else if (k == "multi_exchanges") *value = m->parts.size() > 1 ? std::max(m->stages - 1, 0) : 0;   // stages whose rows travel
+    else if (m->generic && k.rfind(kBytes, 0) == 0) {   // full rows: the busiest part's rows x width x 4
+        const char *num = k.c_str() + sizeof kBytes - 1;
+        char *end = nullptr;
+        const long s = strtol(num, &end, 10);
+        if (*num < '0' || *num > '9' || *end != 0 || s + 1 >= (long)m->stages) return false;
+        uint64_t most = 0;
+        if (m->have_graph && m->parts.size() > 1)
+            for (const Part &p : m->parts) most = std::max<uint64_t>(most, (uint64_t)(p.hi - p.lo) * (uint64_t)m->gw_out[(size_t)s] * sizeof(float));
+        *value = (long)most;
+    }
+    else if (k == "multi_pieces") *value = m->parts.empty() ? 0 : m->parts[0].pieces;
     else if (k == "multi_packed_stage0" || k == "multi_packed_stage1") *value = m->pk[k.back() - '0'].known && m->pk[k.back() - '0'].on ? 1 : 0;
     else if (k == "multi_packed_columns_stage0" || k == "multi_packed_columns_stage1") *value = m->pk[k.back() - '0'].on ? (long)m->pk[k.back() - '0'].kp : 16;
     else if (k == "multi_exchange_bytes_per_peer_stage0" || k == "multi_exchange_bytes_per_peer_stage1") {
@@ -808,12 +1040,56 @@ bool multi_audit_info(MultiState *m, const char *key, long *value) {
     return gnnvc_get_info(p.eng, key, value) == GNNVC_OK;
 }
 
+// multi_forward_device of the generic route: no packing to choose, no attempt to repeat; audit = gnnvc_forward_audited* (the parts'
+// "audit_period" stays 0: a generic engine audits on demand only, each worker calls gnnvc_audit_stage_device itself)
+static int forward_generic_handle(MultiState *m, const float *d_x, float *d_scores, float *d_logits, bool audit, std::string &err) {
+    std::vector<long> failures(m->parts.size(), 0);
+    if (audit)
+        for (size_t r = 0; r < m->parts.size(); ++r)
+            if (gnnvc_get_info(m->parts[r].eng, "audit_failures", &failures[r]) != GNNVC_OK) {
+                err = "reading a part's audit counters failed";
+                return GNNVC_ERR_STATE;
+            }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (m->opt.poison && m->opt.only_part < 0 && m->stages > 1) {   // (tests, fuzz; before any part starts: peers write into these buffers on their own streams)
+        for (Part &p : m->parts) {
+            if (hipSetDevice(p.device) != hipSuccess) continue;
+            for (auto &h : p.h)
+                if (h.p) (void)hipMemsetAsync(h.p, 0xFF, (size_t)m->n * (size_t)m->wmax * sizeof(float), p.stream);
+            (void)hipStreamSynchronize(p.stream);
+        }
+    }
+    m->fw_x = d_x;
+    m->fw_scores = d_scores;
+    m->fw_logits = d_logits;
+    m->fw_audit = audit;
+    ++m->epoch;
+    int rc = run_job(m, kForward, err);
+    m->fw_audit = false;
+    if (rc == GNNVC_OK && audit) {   // every part has drained: did any part's audit find a mismatch?
+        for (size_t r = 0; r < m->parts.size(); ++r) {
+            long now = 0;
+            if (gnnvc_get_info(m->parts[r].eng, "audit_failures", &now) != GNNVC_OK || now == failures[r]) continue;
+            m->audit_last_part = (int)r;
+            if (!m->opt.audit_repair) {
+                err = "part " + std::to_string(r) + ": " + gnnvc_last_error(m->parts[r].eng);
+                rc = GNNVC_ERR_AUDIT;
+            }
+            break;
+        }
+    }
+    (void)hipSetDevice(m->parts[0].device);
+    m->last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
 int multi_forward_device(MultiState *m, const float *d_x, float *d_scores, float *d_logits, bool audit, std::string &err) {
     if (!m->have_graph) {
         err = "no graph attached";
         return GNNVC_ERR_STATE;
     }
     if (m->n == 0) return GNNVC_OK;
+    if (m->generic) return forward_generic_handle(m, d_x, d_scores, d_logits, audit, err);
     if (m->opt.only_part >= 0 && m->parts.size() > 1 && !(m->pk[0].known && m->pk[1].known)) {
         err = "multi_only_part needs a complete forward on this graph first";
         return GNNVC_ERR_STATE;

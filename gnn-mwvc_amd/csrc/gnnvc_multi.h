@@ -11,11 +11,20 @@
 
 #include <string>
 
+#include "../../include/gnnvc.h"
+
 namespace gnnvc {
 
 struct MultiState;
 
-int multi_create(MultiState **out, const char *model_text, size_t len, const int *devices, int n_devices, std::string &err);
+// generic = gnnvc_create_multi_generic: a model that is a generic stage list under *cfg (never null then; applied to every part's
+// engine before its stage list is read) runs the generic route — full rows of any width exchanged after every stage but the
+// last; false = gnnvc_create_multi, which refuses such a model.  A model of the trained shape gets the same handle either way.
+int multi_create(MultiState **out, const char *model_text, size_t len, const int *devices, int n_devices, bool generic,
+                 const gnnvc_generic_config *cfg, std::string &err);
+bool multi_is_generic(const MultiState *m);
+// a gnnvc_get_info key of the parts' engines, summed over the parts ("generic_heavy_rows" ...)
+bool multi_sum_info(MultiState *m, const char *key, long *value);
 void multi_destroy(MultiState *m);
 int multi_devices(const MultiState *m);
 uint32_t multi_vertices(const MultiState *m);

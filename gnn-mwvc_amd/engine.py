@@ -20,7 +20,7 @@ _LIB = pathlib.Path(os.environ["GNNVC_LIBRARY"]).resolve() if os.environ.get("GN
 # every symbol include/gnnvc.h declares (tests check the library exports all of them).  gnnvc_debug_probe is exported too and
 # deliberately left out: a debugging aid outside the header (Option C), used by tests/test_gpu_lifetime.py
 ABI_SYMBOLS = [
-    "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_destroy",
+    "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_create_multi_generic", "gnnvc_destroy",
     "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_set_generic_heavy_rows",
     "gnnvc_set_generic_giant_rows", "gnnvc_set_generic_big_stages", "gnnvc_set_generic_feature_width",
     "gnnvc_set_generic_patterns",
@@ -31,18 +31,37 @@ ABI_SYMBOLS = [
     "gnnvc_forward", "gnnvc_forward_device", "gnnvc_forward_audited", "gnnvc_forward_audited_device", "gnnvc_audit_stage_device",
     "gnnvc_num_stages", "gnnvc_stage_widths",
     "gnnvc_stage_forward_device", "gnnvc_stage_input_ready", "gnnvc_live_columns", "gnnvc_column_counts", "gnnvc_pack_rows", "gnnvc_unpack_rows", "gnnvc_unpack_gathered",
-    "gnnvc_push_piece", "gnnvc_unpack_pieces", "gnnvc_get_stream",
+    "gnnvc_push_piece", "gnnvc_push_rows", "gnnvc_unpack_pieces", "gnnvc_get_stream",
     "gnnvc_reduction_flags", "gnnvc_score_keys", "gnnvc_synchronize", "gnnvc_last_forward_ms",
     "gnnvc_graph_layer_forward", "gnnvc_linear_forward", "gnnvc_relu_forward",
     "gnnvc_sigmoid_forward", "gnnvc_sgemm", "gnnvc_stream_sum", "gnnvc_kernel_trace",
 ]
 COL_PAD = 64
 PATTERN_PROLOGUE, PATTERN_OPEN_END = 1, 2   # GNNVC_PATTERN_*: the bits of Engine.set_generic_patterns
+GENERIC_DEFAULT = 0xFFFFFFFF   # GNNVC_GENERIC_DEFAULT: a threshold of gnnvc_generic_config left at the engine's default
 ERR_AUDIT = -6   # GNNVC_ERR_AUDIT: the on-device audit (option "audit_period") found a fused stage's values wrong
 
 # gnnvc_get_info keys of the on-device audit (Engine.audit_report)
 AUDIT_KEYS = ("audit_runs", "audit_failures", "audit_repairs", "audit_nan_pairs", "audit_last_stage", "audit_last_row",
               "audit_last_col", "audit_last_mismatches", "audit_last_fused_bits", "audit_last_plain_bits")
+
+
+class GenericConfig(C.Structure):
+    """gnnvc_generic_config: the generic opt-ins of gnnvc_create_multi_generic, made at creation."""
+    _fields_ = [("size", C.c_uint32), ("heavy_rows", C.c_uint32), ("giant_rows", C.c_uint32), ("giant_segments", C.c_int32),
+                ("big_stages_lds", C.c_uint32), ("feature_width", C.c_uint32), ("patterns", C.c_uint32)]
+
+    KEYS = ("heavy_rows", "giant_rows", "giant_segments", "big_stages_lds", "feature_width", "patterns")
+
+    @classmethod
+    def of(cls, values=None) -> "GenericConfig":
+        """All defaults, then the keys of `values` (a dict with keys of KEYS)."""
+        c = cls(C.sizeof(cls), GENERIC_DEFAULT, GENERIC_DEFAULT, -1, 0, 0, 0)
+        for k, v in dict(values or {}).items():
+            if k not in cls.KEYS:
+                raise ValueError(f"generic: unknown key {k!r} (one of {', '.join(cls.KEYS)})")
+            setattr(c, k, v)
+        return c
 
 
 class GnnvcError(RuntimeError):
@@ -101,6 +120,7 @@ def load_library():
     L.gnnvc_last_error.argtypes = [vp]
     L.gnnvc_create.argtypes = [C.POINTER(vp), C.c_char_p, C.c_size_t, C.c_int]
     L.gnnvc_create_multi.argtypes = [C.POINTER(vp), C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int]
+    L.gnnvc_create_multi_generic.argtypes = [C.POINTER(vp), C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(GenericConfig)]
     L.gnnvc_destroy.argtypes = [vp]
     L.gnnvc_destroy.restype = None
     L.gnnvc_set_weight_scale.argtypes = [vp, C.c_float]
@@ -139,6 +159,7 @@ def load_library():
     L.gnnvc_pack_rows.argtypes = [vp, f32p, u32, u32, u32, u32, u32, f32p, vp, u32, vp]
     L.gnnvc_unpack_rows.argtypes = [vp, f32p, vp, u32, u32, u32, u32, u32, u32, f32p]
     L.gnnvc_unpack_gathered.argtypes = [vp, f32p, u32, u32, u64, u32, u32, u32, u32, u32, u32, u32, u32, u32, f32p]
+    L.gnnvc_push_rows.argtypes = [vp, f32p, u64, u32, C.POINTER(vp), vp]
     L.gnnvc_last_forward_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
     L.gnnvc_graph_layer_forward.argtypes = [vp, u32, f32p, f32p]
     L.gnnvc_linear_forward.argtypes = [vp, u32, u32, u32, f32p, f32p, f32p, f32p]
@@ -166,12 +187,22 @@ def _np_ptr(a: np.ndarray):
 class Engine:
     """One engine = one model on one GPU (mirrors `gnn::model`)."""
 
-    def __init__(self, model_text: str | None = None, device: int = 0, devices=None):
-        """devices = [ordinals]: several devices behind this one handle (gnnvc_create_multi); an ordinal may repeat."""
+    def __init__(self, model_text: str | None = None, device: int = 0, devices=None, generic=None):
+        """devices = [ordinals]: several devices behind this one handle (gnnvc_create_multi); an ordinal may repeat.
+        generic (with devices): None = gnnvc_create_multi, which runs the trained model only; True, or a dict with keys of
+        heavy_rows, giant_rows, giant_segments, big_stages_lds, feature_width, patterns (values as the set_generic_* methods
+        take them) = gnnvc_create_multi_generic, which also runs a model that is a generic stage list under these settings and
+        raises GnnvcError -5 for one that stays layer by layer, -1 for a value the matching setter would reject."""
         self._L = load_library()
         self._h = C.c_void_p()
         raw = (model_text if model_text is not None else default_model_text()).encode()
-        if devices is not None:
+        if generic is not None and generic is not False and devices is None:
+            raise ValueError("generic= goes with devices=: a single engine has the set_generic_* methods")
+        if devices is not None and generic is not None and generic is not False:
+            arr = (C.c_int * len(devices))(*devices)
+            cfg = GenericConfig.of(None if generic is True else generic)
+            rc = self._L.gnnvc_create_multi_generic(C.byref(self._h), raw, len(raw), arr, len(devices), C.byref(cfg))
+        elif devices is not None:
             arr = (C.c_int * len(devices))(*devices)
             rc = self._L.gnnvc_create_multi(C.byref(self._h), raw, len(raw), arr, len(devices))
         else:
@@ -425,6 +456,13 @@ class Engine:
                     exc_ptr: int = 0, exc_cap: int = 0, width: int = 16):
         self._check(self._L.gnnvc_unpack_rows(self._h, dense_ptr, exc_ptr or None, exc_cap, width, row_lo, row_hi,
                                               mask, kp, feat_ptr))
+
+    def push_rows(self, src_ptr: int, words: int, dst_ptrs, stream: int = 0):
+        """`words` floats from the device pointer src_ptr stored to every device pointer of dst_ptrs (at most 64) in one launch
+        (gnnvc_push_rows, kernel k_push_rows): full rows of any width on their way to the peers of a generic multi-device handle.
+        Asynchronous on `stream` (0 = the engine's)."""
+        dst = (C.c_void_p * max(len(dst_ptrs), 1))(*[C.c_void_p(p or None) for p in dst_ptrs])
+        self._check(self._L.gnnvc_push_rows(self._h, src_ptr or None, words, len(dst_ptrs), dst, stream or None))
 
     def reduction_flags(self, max_degree: int = 20) -> np.ndarray:
         flags = np.zeros(self.n, dtype=np.uint8)

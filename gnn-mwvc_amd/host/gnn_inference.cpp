@@ -33,6 +33,10 @@
 #include "gnnvc.h"
 #include "gnnvc_host.hpp"
 
+// gnnvc_create_multi_generic is called only under GNNVC_GENERIC: this mirror also links against stand-ins of the C ABI that
+// implement the calls it has always made and no others, so the reference stays weak and is checked where it is used
+#pragma weak gnnvc_create_multi_generic
+
 // ------------------------------------------------------------------ glue
 
 namespace gnnvc_host {
@@ -408,7 +412,30 @@ gnnvc_engine *engine_for(const void *key, const std::string &name, const std::ve
     const std::vector<int> devs = gnnvc_host::device_list();
     if (devs.empty())
         check(gnnvc_create(&b.eng, text.data(), text.size(), gnnvc_host::device_ordinal()), "gnnvc_create(model)");
-    else
+    else if (const char *gen = std::getenv("GNNVC_GENERIC")) {
+        // GNNVC_GENERIC (with GNNVC_DEVICES): create through gnnvc_create_multi_generic, which also runs a retrained model that is a
+        // generic stage list.  "key=value,key=value" with gnnvc_generic_config's members (heavy_rows, giant_rows, giant_segments,
+        // big_stages_lds, feature_width, patterns); empty or "1" = all defaults.  An unknown key ends the run.
+        if (!gnnvc_create_multi_generic) check(GNNVC_ERR_UNSUPPORTED, "GNNVC_GENERIC: the linked library has no gnnvc_create_multi_generic");
+        gnnvc_generic_config cfg{(uint32_t)sizeof(gnnvc_generic_config), GNNVC_GENERIC_DEFAULT, GNNVC_GENERIC_DEFAULT, -1, 0, 0, 0};
+        const std::string all(gen);
+        for (size_t at = 0; at < all.size() && all != "1";) {
+            const size_t end = std::min(all.find(',', at), all.size());
+            const std::string kv = all.substr(at, end - at);
+            const size_t eq = kv.find('=');
+            const std::string key = kv.substr(0, eq);
+            const long long v = eq == std::string::npos ? 0 : std::atoll(kv.c_str() + eq + 1);
+            if (key == "heavy_rows") cfg.heavy_rows = (uint32_t)v;
+            else if (key == "giant_rows") cfg.giant_rows = (uint32_t)v;
+            else if (key == "giant_segments") cfg.giant_segments = (int32_t)v;
+            else if (key == "big_stages_lds") cfg.big_stages_lds = (uint32_t)v;
+            else if (key == "feature_width") cfg.feature_width = (uint32_t)v;
+            else if (key == "patterns") cfg.patterns = (uint32_t)v;
+            else if (!kv.empty()) check(GNNVC_ERR_INVALID, "GNNVC_GENERIC: unknown key");
+            at = end + 1;
+        }
+        check(gnnvc_create_multi_generic(&b.eng, text.data(), text.size(), devs.data(), (int)devs.size(), &cfg), "gnnvc_create_multi_generic(model)");
+    } else
         check(gnnvc_create_multi(&b.eng, text.data(), text.size(), devs.data(), (int)devs.size()), "gnnvc_create_multi(model)");
     // GNNVC_OPTIONS="key=value,key=value": engine options (include/gnnvc.h) for a driver that cannot call gnnvc_set_option itself
     if (const char *opts = std::getenv("GNNVC_OPTIONS")) {

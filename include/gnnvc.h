@@ -98,6 +98,55 @@ void gnnvc_destroy(gnnvc_engine *e);
  * single engine behind the same code path. */
 int gnnvc_create_multi(gnnvc_engine **out, const char *model_text, size_t len, const int *devices, int n_devices);
 
+/* Generic-stage models on several devices behind one handle (opt-in).  gnnvc_create_multi keeps refusing every model but the
+ * trained 32/32/16 one, and the gnnvc_set_generic_* calls keep returning GNNVC_ERR_UNSUPPORTED on its handle — so the opt-ins of
+ * a generic model are made HERE, at creation, in *cfg (NULL = all defaults):
+ *   size            sizeof(gnnvc_generic_config); anything else: GNNVC_ERR_INVALID;
+ *   heavy_rows      as gnnvc_set_generic_heavy_rows;  GNNVC_GENERIC_DEFAULT (0xFFFFFFFF) = leave the engine's default (512);
+ *   giant_rows      as gnnvc_set_generic_giant_rows;  GNNVC_GENERIC_DEFAULT = leave the default (16 384);
+ *   giant_segments  as that call's `segments`; -1 = its rule;
+ *   big_stages_lds  as gnnvc_set_generic_big_stages;    0 = off;
+ *   feature_width   as gnnvc_set_generic_feature_width; 0 = off;
+ *   patterns        as gnnvc_set_generic_patterns;      0 = off.
+ * Null arguments, a wrong size or a value the matching single-device call would reject: GNNVC_ERR_INVALID with *out null, before
+ * any device is touched.  Then
+ *   a model of the trained shape               gives exactly the handle gnnvc_create_multi gives; cfg has no effect;
+ *   a model that is a generic stage list under cfg   (option "generic_stages": gnnvc_is_fused on a single engine with the same
+ *                         settings) runs the route below;
+ *   a model that stays layer by layer under cfg      GNNVC_ERR_UNSUPPORTED, as is a stage list with a dense stage behind stage 0.
+ * The config is applied to every part's engine before its stage list is read, and to the front handle: gnnvc_num_stages,
+ * gnnvc_stage_widths, gnnvc_in_width, gnnvc_out_width, "generic_patterns", "generic_stage_layers_<s>" and their kin answer on the
+ * handle as a single engine with the same settings would; "generic_heavy_rows", "generic_heavy_entries", "generic_giant_rows" and
+ * "generic_giant_entries" are the parts' summed.  The gnnvc_set_generic_* calls stay refused on the handle.
+ * The route: the graph is cut as for gnnvc_create_multi; every part holds x (n x in_width), two ping-pong buffers of n x wmax floats
+ * (wmax: the widest intermediate stage output), scores and logits (n x out_width) — all reserved at hand-off, none inside a forward.
+ * Every stage s runs piece by piece through gnnvc_stage_forward_device on the part's slice (k_stage_any: heavy and giant rows
+ * included; the logits on the last stage), and after each piece of a stage that is not the last the piece's rows travel to every
+ * peer as FULL rows of the stage's output width (1 .. 64 floats: no live-column codec, no first forward that chooses one), straight
+ * into the peer's buffer of that stage: one kernel for all peers (gnnvc_push_rows; option "multi_push" 1, the default, and every
+ * pair of devices with peer access — parts that share a device always have it) or one hipMemcpyPeerAsync per peer, on a stream of
+ * its own under the next piece's kernels.  A graph stage waits for every peer's pieces of the stage before it; a dense stage 0
+ * (GNNVC_PATTERN_PROLOGUE) waits for nothing; a model without a graph stage exchanges nothing; empty parts and empty pieces launch
+ * and ship nothing.  Results are those of a single engine, bit for bit: a row is computed on one device in stored order.
+ * Options: "multi_pieces", "multi_push" and "multi_only_part" (no earlier forward needed) keep their meaning, "poison_features"
+ * fills n x wmax floats, "multi_pack" and "multi_announce" are accepted and change nothing.  gnnvc_forward_audited* audit every
+ * part's rows (gnnvc_audit_stage_device, k_audit_any, right behind each piece's stage call; a mismatch is reported as
+ * GNNVC_ERR_AUDIT once the job has drained; "audit_repair" is handed on); "audit_period" audits nothing on such a handle.
+ * gnnvc_get_info: "multi_generic" (1 on this route, 0 on a trained handle), "multi_exchanges" (the number of exchanged stages: 0 with
+ * one device), "multi_exchange_bytes_per_peer_stage<s>" (any exchanged stage s: the busiest part's rows x width x 4). */
+#define GNNVC_GENERIC_DEFAULT 0xFFFFFFFFu
+typedef struct gnnvc_generic_config {
+    uint32_t size;            /* sizeof(gnnvc_generic_config); anything else: GNNVC_ERR_INVALID */
+    uint32_t heavy_rows;      /* as gnnvc_set_generic_heavy_rows;  GNNVC_GENERIC_DEFAULT (0xFFFFFFFF) = leave the engine's default */
+    uint32_t giant_rows;      /* as gnnvc_set_generic_giant_rows;  GNNVC_GENERIC_DEFAULT = leave the default */
+    int32_t  giant_segments;  /* as that call's `segments`; -1 = its rule */
+    uint32_t big_stages_lds;  /* as gnnvc_set_generic_big_stages;    0 = off */
+    uint32_t feature_width;   /* as gnnvc_set_generic_feature_width; 0 = off */
+    uint32_t patterns;        /* as gnnvc_set_generic_patterns;      0 = off */
+} gnnvc_generic_config;
+int gnnvc_create_multi_generic(gnnvc_engine **out, const char *model_text, size_t len,
+                               const int *devices, int n_devices, const gnnvc_generic_config *cfg /* NULL = all defaults */);
+
 /* model::set_weight_scale (reference src/gnn_inference.cpp:83-90): sets
  * graph_layer::WEIGHT_SCALE of every graph layer (default 120). */
 int gnnvc_set_weight_scale(gnnvc_engine *e, float ws);
@@ -316,7 +365,8 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
  *                         "audit_repair", "audit_quiet", "audit_log" and "audit_flip_*" options and every "audit_*" read-out
  *                         apply to it).  gnnvc_stage_input_ready, the row codec (16-column rows) and
- *                         gnnvc_create_multi with several devices keep returning GNNVC_ERR_UNSUPPORTED for them.  On a
+ *                         gnnvc_create_multi with several devices keep returning GNNVC_ERR_UNSUPPORTED for them (several devices
+ *                         are a call of their own for them, with the opt-ins made at creation: gnnvc_create_multi_generic).  On a
  *                         multi-device handle the option is stored and changes nothing.  gnnvc_get_info: "generic_stages",
  *                         "generic_stages_model" (1 = a forward would run the generic kernel now), "generic_stages_active"
  *                         (1 = the last forward did), "generic_stage_layers_<s>" (the dense-layer count d of stage s;
@@ -646,6 +696,20 @@ int gnnvc_push_piece(gnnvc_engine *e, const float *d_region, uint32_t rows, uint
                      float *const *d_dst, void *hip_stream);
 int gnnvc_unpack_pieces(gnnvc_engine *e, const gnnvc_piece *pieces, uint32_t n_pieces, uint32_t exc_cap, uint32_t width, uint32_t mask,
                         uint32_t kp, float *d_feat);
+
+/* Full rows to several destinations in ONE launch (what gnnvc_create_multi_generic's devices exchange: rows of any width, no
+ * codec).  Rows [r0, r1) of a row-major n x f matrix are one run of (r1 - r0) * f floats at word offset r0 * f, so the run starts
+ * and ends at any 4-byte boundary.
+ *   gnnvc_push_rows      stores the `words` floats at d_src into each of d_dst[0 .. n_dst) (n_dst <= 64): device pointers this
+ *                        engine's device can store to — its own memory, or a peer's once peer access is enabled — on hip_stream
+ *                        (NULL = the engine's stream; the run must be complete in that stream's order).  Asynchronous.  Kernel
+ *                        k_push_rows: up to three head words as scalars until the source is 16-byte aligned, the body 16 bytes
+ *                        per lane, up to three tail words as scalars — where every destination has the source's 16-byte phase
+ *                        (pointer mod 16), as the same rows of equally wide, equally aligned matrices have; one destination of
+ *                        another phase sends the launch through a 4-bytes-per-lane instantiation, never a misaligned 16-byte
+ *                        store.  words = 0 or n_dst = 0: GNNVC_OK, nothing launched.  n_dst > 64, a null destination, a null
+ *                        source or a pointer that is not 4-byte aligned: GNNVC_ERR_INVALID, nothing launched. */
+int gnnvc_push_rows(gnnvc_engine *e, const float *d_src, uint64_t words, uint32_t n_dst, float *const *d_dst, void *hip_stream);
 
 /* A multi-GPU rank that computes rows [row_lo, row_hi) of `stage` (1 or 2) in several gnnvc_stage_forward_device
  * calls announces the stage's complete input once: "d_in is final and will not change until those calls are done".
