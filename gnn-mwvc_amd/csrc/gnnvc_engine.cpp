@@ -1760,6 +1760,7 @@ int gnnvc_attach_graph_slice(gnnvc_engine *e, uint32_t n_global, uint32_t row_lo
         e->have_graph = true;
         e->n_long = e->n_giant = 0;
         e->empty_slice = true;
+        reset_graph_state(e);   // (nothing of the previous graph's: its classing least of all — "generic_heavy_rows" reads it)
         return GNNVC_OK;
     }
     e->empty_slice = row_hi == row_lo;
@@ -1768,6 +1769,7 @@ int gnnvc_attach_graph_slice(gnnvc_engine *e, uint32_t n_global, uint32_t row_lo
         e->g.row_end = row_hi;
         e->have_graph = true;
         e->n_long = e->n_giant = 0;
+        reset_graph_state(e);
         return GNNVC_OK;
     }
     return attach_common(e, cand);

@@ -859,6 +859,10 @@ bool multi_is_generic(const MultiState *m) { return m && m->generic; }
 
 bool multi_sum_info(MultiState *m, const char *key, long *value) {
     long total = 0;
+    if (m->have_graph && m->n == 0) {   // (a graph of no vertices is attached to no part: they still hold the one before it)
+        *value = 0;
+        return true;
+    }
     for (const Part &p : m->parts) {
         long v = 0;
         if (gnnvc_get_info(p.eng, key, &v) != GNNVC_OK) return false;

@@ -44,10 +44,15 @@ def walk(om, name, g, ws=None, x=None, first=0, count=None):
     """An admitted member stage by stage through the oracle's own layer functions (weight scale ws, default g.ws):
     [(input rows, output rows, pre-activation of the stage's last linear layer)].  A dense stage has no graph layer; the last
     stage ends in the ReLU, the sigmoid or nothing (the output rows are then the pre-activation)."""
-    P = om.linear_params()
-    stages = mp.stages_of(name)
-    assert sum(len(s[2]) for s in stages) == len(P)
     h = mp.model_input(name, g) if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(g.n, -1)
+    return walk_stages(om, mp.stages_of(name), g, h, ws=ws, first=first, count=count)
+
+
+def walk_stages(om, stages, g, h, ws=None, first=0, count=None):
+    """walk for any stage list [(dense, f, widths, end code)] (tools/modelgen_patterns.stages_of's form), from the input rows h of
+    stage `first`: what tests/fuzz_harness.py walks its drawn models with."""
+    P = om.linear_params()
+    assert sum(len(s[2]) for s in stages) == len(P)
     i = sum(len(s[2]) for s in stages[:first])
     out = []
     for dense, f, widths, end in stages[first: None if count is None else first + count]:
