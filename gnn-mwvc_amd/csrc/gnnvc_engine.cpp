@@ -182,6 +182,7 @@ int plan_model(gnnvc_engine *e) {
 // admits that is stage_any_route's decision, like every bound.
 void plan_generic(gnnvc_engine *e) {
     e->gstages.clear();
+    e->live_seen.clear();   // ("generic_live_*_<s>" speak of the stages of the list that ran)
     std::vector<StagePlan> gs;
     bool gok = !e->layers.empty();
     int f = e->in_width;
@@ -755,7 +756,15 @@ int forward_unfused(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
 // k_any_giant_place, which leaves their sums where the listed rows' launch reads them — and k_any_heavy_sums skips them.  The
 // giant chain and then the heavy sums go to the side queue beside the light rows (fork / join as launch_side_rows) or ahead of
 // them on the main stream (heavy_overlap()); the listed rows' launch follows all of them.
-int run_generic_stage(gnnvc_engine *e, const StagePlan &sp, const float *in, float *out, float *logits, uint32_t lo, uint32_t hi) {
+// live_stage >= 0 (forward_generic only, for a stage live_eligible accepts): the stage's input is examined first — k_any_live_mask,
+// k_any_live_pack, on the main stream — and the all-rows / light-rows launch may gather from the table; the heavy and giant rows'
+// kernels, on whichever queue, read full rows as ever.
+static bool live_eligible(const gnnvc_engine *e, const StagePlan &sp) {
+    return e->live_percent != 0 && !sp.dense && sp.f >= 2 && sp.end != gnnvc::kEndNone;
+}
+
+int run_generic_stage(gnnvc_engine *e, const StagePlan &sp, const float *in, float *out, float *logits, uint32_t lo, uint32_t hi,
+                      int live_stage = -1) {
     if (sp.dense) {   // a dense stage (gnnvc_set_generic_patterns): no neighbour sums, so no row is classed and nothing is split — one launch
         HIP_TRY(e, gnnvc::launch_stage_any(stage_call(e, sp, in, out, logits, lo, hi)));
         return GNNVC_OK;
@@ -764,7 +773,12 @@ int run_generic_stage(gnnvc_engine *e, const StagePlan &sp, const float *in, flo
         const int rc = class_heavy_rows(e);
         if (rc) return rc;
     }
-    const gnnvc::StageCall call = stage_call(e, sp, in, out, logits, lo, hi);
+    gnnvc::StageCall call = stage_call(e, sp, in, out, logits, lo, hi);
+    if (live_stage >= 0) {
+        call.live_table = e->live_table.p;
+        call.live_desc = e->live_desc.p + 2 * (size_t)live_stage;
+        HIP_TRY(e, gnnvc::launch_any_live(call, e->live_percent));
+    }
     const gnnvc_engine::PerGraph &pg = e->pg;
     e->heavy_last_rows = pg.heavy_rows;
     e->ggiant_last_rows = pg.heavy_rows ? pg.giant_rows : 0;
@@ -821,13 +835,27 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
     for (size_t s = 0; s + 1 < st.size(); ++s) wmax = std::max(wmax, st[s].n3);
     if (st.size() > 1)
         for (auto &b : e->scratch) HIP_TRY(e, b.reserve(((size_t)n + 1) * (size_t)wmax));
+    // gnnvc_set_generic_live_columns: the table is as wide as the widest eligible stage input; the descriptors start from zero
+    // (live_seen[s] is set behind stage s's launches: a forward that fails part-way leaves the stages it never reached unexamined)
+    e->live_seen.assign(st.size(), 0);
+    int live_wmax = 0;
+    for (size_t s = 0; s < st.size(); ++s)
+        if (live_eligible(e, st[s])) live_wmax = std::max(live_wmax, st[s].f);
+    if (live_wmax) {   // (a descriptor is two 64-bit words of live_desc: sizeof(AnyLiveDesc) == 16, asserted beside the struct)
+        HIP_TRY(e, e->live_table.reserve((size_t)n * (size_t)live_wmax));
+        HIP_TRY(e, e->live_desc.reserve(2 * st.size()));
+        HIP_TRY(e, hipMemsetAsync(e->live_desc.p, 0, 2 * st.size() * sizeof(unsigned long long), e->stream));
+        if (e->opt.poison) HIP_TRY(e, hipMemsetAsync(e->live_table.p, 0xFF, (size_t)n * (size_t)live_wmax * sizeof(float), e->stream));
+    }
     const float *cur = d_x;
     for (size_t s = 0; s < st.size(); ++s) {
         const bool last = s + 1 == st.size();
         float *dst = last ? d_out : e->scratch[s & 1].p;
         {
-            const int rc = run_generic_stage(e, st[s], cur, dst, last ? d_logits : nullptr, 0, n);
+            const bool live = live_eligible(e, st[s]);
+            const int rc = run_generic_stage(e, st[s], cur, dst, last ? d_logits : nullptr, 0, n, live ? (int)s : -1);
             if (rc != GNNVC_OK) return rc;
+            e->live_seen[s] = live ? 1 : 0;
         }
         if (e->audit_now) {   // (gnnvc_forward_audited* only: "audit_period" never sets it for a generic-stage model)
             std::string plan = st[s].dense ? "k_stage_any (dense rows)"
@@ -835,6 +863,7 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
             if (!st[s].dense && e->ggiant_last_rows)
                 plan += e->ggiant_last_segmented ? " + k_any_giant_gather, k_giant_segsum, k_giant_segmap, k_giant_sum, k_any_giant_place"
                                                  : " + k_any_giant_gather, k_giant_sum, k_any_giant_place";
+            if (e->live_seen[s]) plan += " + k_any_live_mask, k_any_live_pack (the live-column table, where the device chose it)";
             const int rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan);
             if (rc != GNNVC_OK) return rc;
         }
@@ -1082,6 +1111,37 @@ static int set_patterns(gnnvc_engine *e, uint32_t mask) {
     return GNNVC_OK;
 }
 
+int gnnvc_set_generic_live_columns(gnnvc_engine *e, uint32_t max_percent) {
+    if (!e) return GNNVC_ERR_INVALID;
+    NOT_ON_MULTI(e, "gnnvc_set_generic_live_columns");
+    if (max_percent > 100u)
+        return fail(e, GNNVC_ERR_INVALID, "gnnvc_set_generic_live_columns: %u is not within 0 .. 100", max_percent);
+    e->live_percent = max_percent;   // (the next forward's; the stage list is not derived again: nothing is admitted or refused by it)
+    return GNNVC_OK;
+}
+
+// "generic_live_{kept,used,mask_lo,mask_hi}_<s>": stage s's descriptor of the last forward, copied back now — one copy and one
+// wait on the engine's stream; a forward itself copies nothing back.  A stage that forward did not examine: kept -1, used 0, mask 0.
+static int live_readout(const gnnvc_engine *e, long s, char what, long *value) {
+    unsigned long long d[2] = {0ull, 0ull};
+    const bool seen = (size_t)s < e->live_seen.size() && e->live_seen[(size_t)s] && e->live_desc.p;
+    if (seen) {
+        if (hipSetDevice(e->device) != hipSuccess ||
+            hipMemcpyAsync(d, e->live_desc.p + 2 * (size_t)s, sizeof d, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return GNNVC_ERR_DEVICE;
+        }
+    }
+    switch (what) {
+    case 'k': *value = seen ? (long)(uint32_t)d[1] : -1; break;
+    case 'u': *value = (long)(uint32_t)(d[1] >> 32); break;
+    case 'l': *value = (long)(uint32_t)d[0]; break;
+    default: *value = (long)(uint32_t)(d[0] >> 32); break;
+    }
+    return GNNVC_OK;
+}
+
 // gnnvc_create_multi with the generic opt-ins made at creation (the setters stay refused on the handle).  Everything that can be
 // refused without a device is refused before one is touched.
 int gnnvc_create_multi_generic(gnnvc_engine **out, const char *model_text, size_t len, const int *devices, int n_devices,
@@ -1181,6 +1241,16 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k == "generic_big_lds") *value = (long)e->big_lds;                       // gnnvc_set_generic_big_stages, as set
     else if (k == "generic_feature_width") *value = (long)e->feat_width;              // gnnvc_set_generic_feature_width, as set
     else if (k == "generic_patterns") *value = (long)e->patterns;                     // gnnvc_set_generic_patterns, as set
+    else if (k == "generic_live_columns") *value = (long)e->live_percent;             // gnnvc_set_generic_live_columns, as set
+    else if (k.rfind("generic_live_kept_", 0) == 0 || k.rfind("generic_live_used_", 0) == 0 || k.rfind("generic_live_mask_lo_", 0) == 0 ||
+             k.rfind("generic_live_mask_hi_", 0) == 0) {      // the last forward's verdict on stage s, read back from the device
+        const char what = k[13] == 'k' ? 'k' : k[13] == 'u' ? 'u' : k[18] == 'l' ? 'l' : 'h';
+        const size_t prefix = what == 'k' ? sizeof("generic_live_kept_") - 1 : what == 'u' ? sizeof("generic_live_used_") - 1
+                              : sizeof("generic_live_mask_lo_") - 1;   // (mask_lo and mask_hi: the same length)
+        const long s = generic_stage_index(e, k, prefix);
+        if (s < 0) return GNNVC_ERR_INVALID;
+        return live_readout(e, s, what, value);
+    }
     else if (k.rfind("generic_stage_dense_", 0) == 0) {       // "generic_stage_dense_<s>": 1 = stage s has no graph layer (a prologue)
         const long s = generic_stage_index(e, k, sizeof("generic_stage_dense_") - 1);
         if (s < 0) return GNNVC_ERR_INVALID;
@@ -1892,6 +1962,7 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     if (!e->have_graph) return fail(e, GNNVC_ERR_STATE, "no graph attached");
     const uint32_t n = e->g.n;
     e->ev_count = 0;
+    e->live_seen.clear();   // ("generic_live_*_<s>": what THIS forward examines, forward_generic)
     if (e->layers.empty()) return fail(e, GNNVC_ERR_STATE, "engine was created without a model");
     if (n == 0) return GNNVC_OK;
     if (e->g.sliced() || e->empty_slice)
@@ -2097,7 +2168,10 @@ static int forward_host(gnnvc_engine *e, const float *x, float *scores, float *l
     const uint32_t n = e->g.n;
     if (e->layers.empty()) return fail(e, GNNVC_ERR_STATE, "engine was created without a model");
     if (audited && e->stage_list().empty()) return fail(e, GNNVC_ERR_UNSUPPORTED, "model is not fused into stages: there is nothing to audit");
-    if (n == 0) return GNNVC_OK;
+    if (n == 0) {
+        e->live_seen.clear();   // (a forward that examined no stage: "generic_live_*_<s>")
+        return GNNVC_OK;
+    }
     // (before the copy below: a sliced engine has no feature buffers of its own — e->x may be null or sized for an earlier graph)
     if (e->g.sliced() || e->empty_slice)
         return fail(e, GNNVC_ERR_STATE, "this engine holds a slice of the graph: run it stage by stage (gnnvc_stage_forward_device)");

@@ -70,6 +70,14 @@ struct gnnvc_engine {
     // gnnvc_set_generic_patterns: 0 = off, else the mask of GNNVC_PATTERN_PROLOGUE | GNNVC_PATTERN_OPEN_END (a dense stage in front
     // of the first graph layer; a model that ends in a ReLU or in its bare linear layer); carried by every plan in gstages too
     uint32_t patterns = 0;
+    // gnnvc_set_generic_live_columns: 0 = off, else 1 .. 100 — inside a whole forward a graph stage with f >= 2 that does not end in
+    // its bare linear layer gathers from the compact table of its input's live columns iff kept * 100 <= live_percent * f, decided
+    // on the device (k_any_live_mask, k_any_live_pack).  Not carried by the plans: it changes no admission.  live_table = the
+    // table (n x the widest eligible f, an engine buffer of its own), live_desc = a 16-byte descriptor per stage, zeroed by each
+    // such forward, live_seen[s] = the last forward examined stage s (what the "generic_live_*_<s>" read-outs copy back).
+    // (the buffers themselves are declared with the feature buffers below, behind the streams)
+    uint32_t live_percent = 0;
+    std::vector<uint8_t> live_seen;
     bool generic_on() const { return !gstages.empty() && (opt.generic == 2 || (opt.generic == 1 && stages.empty())); }
     const std::vector<StagePlan> &stage_list() const { return generic_on() ? gstages : stages; }   // what the ABI reports and runs
     // Heavy rows of generic stages (gnnvc_set_generic_heavy_rows): rows of at least heavy_from entries (0: none) get a workgroup
@@ -152,6 +160,8 @@ struct gnnvc_engine {
     // feature buffers
     DevBuf<float> x, h[2], scores, logits;
     DevBuf<float> scratch[2];  // layer-level entry points / unfused path / generic stages (ping-pong rows of up to 32 columns)
+    DevBuf<float> live_table;                 // gnnvc_set_generic_live_columns: the compact table (above)
+    DevBuf<unsigned long long> live_desc;     // ... and two words per generic stage: {mask, kept | used << 32}
 
     // column-blocked plan of the F = 1 stage (built per graph, see gnnvc_kernels.hip)
     uint32_t blk_count = 0, blk_cols = 0;

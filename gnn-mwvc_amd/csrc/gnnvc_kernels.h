@@ -128,6 +128,10 @@ struct StageCall {
     hipStream_t stream = nullptr;
     uint32_t skip = 0;               // bits of sp->skip_ok the kernels may act on (option "dense_skip_zeros"): bit 0 = the first
                                      // layer's known zeros (k_dense_f16's routes A / B), bits 1, 2 = dense_live in layers 2, 3
+    // gnnvc_set_generic_live_columns (a generic graph stage inside a whole forward; both null = off): the engine's table of the
+    // live columns of `in` (g->n rows of at most f floats) and this stage's 16-byte descriptor {mask, kept, used} on the device
+    float *live_table = nullptr;
+    void *live_desc = nullptr;
 };
 
 // Producer side of the compact-table plan: a stage kernel whose dense layers run on the VALU can count the
@@ -252,6 +256,11 @@ struct AnyHeavyRows {
 enum class AnyRows { kAll, kLight, kListed };
 hipError_t launch_stage_any(const StageCall &c, AnyRows rows = AnyRows::kAll, const AnyHeavyRows &hr = AnyHeavyRows());
 hipError_t launch_any_heavy_sums(const StageCall &c, const AnyHeavyRows &hr);
+// Live columns of a generic graph stage's input (gnnvc_set_generic_live_columns; f >= 2, whole graph, c.live_desc zeroed by the
+// caller): k_any_live_mask ORs the columns that hold anything but +-0.0 into the descriptor, k_any_live_pack derives kept and
+// used (kept * 100 <= max_percent * f) on the device and, when used, writes the n x kept table.  launch_stage_any then launches
+// the LIVE instantiations for the all-rows and light-rows launches of a call that carries both pointers.
+hipError_t launch_any_live(const StageCall &c, uint32_t max_percent);
 
 // a whole stage (variants 0, 1, 2) on WIDE tiles — a workgroup per 64-vertex tile, the tile's gather and each dense layer's outputs
 // split over its four waves (k_stage_w1 / k_stage_w16): graphs with fewer tiles than the chip has SIMDs, no long rows

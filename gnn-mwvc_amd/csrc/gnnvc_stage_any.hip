@@ -307,10 +307,25 @@ __device__ __forceinline__ float any_gather1(const uint32_t *__restrict__ col, c
 // VGPRs and 2 % of a forward on an Erdős–Rényi graph, which has no heavy row (profiles/generic_stages/README.md, "Heavy rows");
 // kAnyAll is the kernel as it was.
 enum { kAnyAll = 0, kAnyLight = 1, kAnyListed = 2, kAnyDense = 3 };
+// the descriptor of a stage's live columns (gnnvc_set_generic_live_columns; the LIVE form below): two 64-bit words on the device
+struct AnyLiveDesc {
+    unsigned long long mask;   // bit c: column c of the stage's input has a word other than +-0.0
+    uint32_t kept, used;       // popcount(mask); 1 = this forward's launches gather from the table
+};
+static_assert(sizeof(AnyLiveDesc) == 16, "the engine keeps two 64-bit words per stage");
+// The two pointers mean one thing to the listed-rows launch (list, hsum) and another to a LIVE all-rows or light-rows launch
+// (live, live_table), which reads neither list nor sums: one slot each, named for both, so that the kernel's arguments — and with
+// them every instantiation that was there — stay what they were.
 struct AnyRowSel {
     uint32_t from, nlist;
-    const uint32_t *list;
-    const float *hsum;
+    union {
+        const uint32_t *list;          // kAnyListed: the listed rows
+        const AnyLiveDesc *live;       // LIVE: the stage's descriptor
+    };
+    union {
+        const float *hsum;             // kAnyListed: their sums
+        const float *live_table;       // LIVE: the compact table of the live columns
+    };
 };
 
 // The BIG form (gnnvc_set_generic_big_stages; BIG = true) is the same source with two more template arguments: BLOCK = 256, 512 or
@@ -327,7 +342,16 @@ struct AnyRowSel {
 //
 // The OPEN form (gnnvc_set_generic_patterns) is the same source once more for a stage that ends in its bare linear layer — and for
 // every dense stage, whose instantiations are new anyway: any_last<T, true> knows the third ending.
-template <int MODE, int BLOCK = kAnyBlock, bool BIG = false, bool FEAT = false, bool OPEN = MODE == 3 /* kAnyDense */>
+//
+// The LIVE form (gnnvc_set_generic_live_columns; kAnyAll and kAnyLight only, OPEN = false) is the same source for a stage whose
+// input may have dead columns (+-0.0 in every row): R.live is the stage's AnyLiveDesc {mask, kept, used} and R.live_table the compact
+// table of the live columns (n rows of `kept` floats, k_any_live_pack below) — they share their slots with the listed rows' list
+// and sums, which an all-rows or light-rows launch never reads, and the kernel's arguments stay what they were.  The descriptor is wave-uniform.  used == 0: today's gather
+// on `in` with f.  used != 0: the SAME gather functions on the table with `kept` in the place of f (none at all for kept == 0,
+// whose f - 1u clamps would underflow), columns [0, f) of vector A zeroed, and lane j's sums stored at the positions of the
+// (j + 16 t)-th set bits of the mask, computed once per kernel.  A dead column's chain is +0.0f for every row and a live column's
+// chain is the one it was ("Live columns").  Everything it adds sits behind `if constexpr (LIVE)`.
+template <int MODE, int BLOCK = kAnyBlock, bool BIG = false, bool FEAT = false, bool OPEN = MODE == 3 /* kAnyDense */, bool LIVE = false>
 __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const float *__restrict__ P, const float *__restrict__ in,
                                                         float *__restrict__ out, float *__restrict__ logits, uint32_t lo, uint32_t hi,
                                                         AnyShape S, int sig, AnyRowSel R) {
@@ -357,6 +381,21 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
     const int lane = threadIdx.x & 63, j = lane & 15, grp = threadIdx.x >> 4, gbase = lane & 48;
     float *xs = lds + L.grp + grp * L.gs;   // the group's vector A; B follows at L.hb
     constexpr bool listed = MODE == kAnyListed;
+    static_assert(!LIVE || MODE == kAnyAll || MODE == kAnyLight, "the table serves the all-rows and light-rows launches only");
+    [[maybe_unused]] uint32_t live_used = 0u, live_kept = 0u;
+    [[maybe_unused]] int live_pos[FEAT ? 4 : 2];   // where lane j's sums go: the (j + 16 t)-th live column, -1 = the lane has none
+    if constexpr (LIVE) {
+        const AnyLiveDesc *ld = R.live;
+        live_used = ld->used;
+        live_kept = ld->kept;
+        const unsigned long long mask = ld->mask;
+#pragma unroll
+        for (int t = 0; t < (FEAT ? 4 : 2); ++t) {
+            unsigned long long m = mask;
+            for (int i = 0; i < j + 16 * t && m; ++i) m &= m - 1ull;   // (drop the lower set bits)
+            live_pos[t] = (live_used && m && (uint32_t)(j + 16 * t) < live_kept) ? __ffsll((long long)m) - 1 : -1;
+        }
+    }
     // (the walk is over rows, or over positions of the list)
     const uint64_t walk_lo = listed ? 0u : (uint64_t)lo, walk_hi = listed ? (uint64_t)R.nlist : (uint64_t)hi;
     for (uint64_t base = walk_lo + (uint64_t)blockIdx.x * ROWS; base < walk_hi; base += (uint64_t)gridDim.x * ROWS) {
@@ -376,7 +415,30 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
             if (MODE == kAnyLight && re - rs >= R.from) continue;   // a heavy row: the listed-rows launch has it
             float s0 = 0.0f, s1 = 0.0f;
             [[maybe_unused]] float s2 = 0.0f, s3 = 0.0f;   // (FEAT: columns j + 32, j + 48)
-            if (listed) {
+            if constexpr (LIVE) {
+                // the table's rows are `kept` floats (used), or the input's own f (not used): one dispatch over (gin, gf)
+                const float *__restrict__ gin = live_used ? R.live_table : in;
+                const uint32_t gf = live_used ? live_kept : (uint32_t)f;
+                if (gf == 0u) {
+                    // no live column: nothing to gather, every sum is the empty chain's +0.0f
+                } else if (FEAT && gf > 32u) {
+                    if constexpr (FEAT) {
+                        float sn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                        if (gf <= 48u) any_gather_n<3>(g.col, gin, rs, re, gf, j, gbase, sn);
+                        else any_gather_n<4>(g.col, gin, rs, re, gf, j, gbase, sn);
+                        s0 = sn[0];
+                        s1 = sn[1];
+                        s2 = sn[2];
+                        s3 = sn[3];
+                    }
+                } else if (gf == 1u) {
+                    s0 = any_gather1(g.col, gin, rs, re, j, gbase);
+                } else if (gf <= 16u) {
+                    any_gather<false>(g.col, gin, rs, re, gf, j, gbase, s0, s1);
+                } else {
+                    any_gather<true>(g.col, gin, rs, re, gf, j, gbase, s0, s1);
+                }
+            } else if (listed) {
                 const float *hs = R.hsum + (size_t)u64 * (uint32_t)f;
                 s0 = hs[min(j, f - 1)];
                 s1 = hs[min(j + 16, f - 1)];
@@ -404,12 +466,23 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
             const float deg = (float)(re - rs), wv = (float)g.w[u] / ws, nwv = (float)g.nw[u] / ws;
             for (int c = j; c < k1; c += 16) {
                 float v = 0.0f;
-                if (c < f) v = c < 16 ? s0 : (!FEAT || c < 32) ? s1 : (c < 48 ? s2 : s3);
+                if (c < f) v = (LIVE && live_used) ? 0.0f : c < 16 ? s0 : (!FEAT || c < 32) ? s1 : (c < 48 ? s2 : s3);
                 else if (c < 2 * f) v = in[(size_t)u * (uint32_t)f + (uint32_t)(c - f)];
                 if (c == f + 1) v = deg;
                 if (c == f + 2) v = wv;
                 if (c == f + 3) v = nwv;
                 xs[c] = v;
+            }
+            if constexpr (LIVE) {
+                if (live_used) {   // (wave-uniform) the sums over the zeros, at their columns' places — all below f, so never on degree, W or NW
+                    wave_lds_sync();
+                    if (live_pos[0] >= 0) xs[live_pos[0]] = s0;
+                    if (live_pos[1] >= 0) xs[live_pos[1]] = s1;
+                    if constexpr (FEAT) {
+                        if (live_pos[2] >= 0) xs[live_pos[2]] = s2;
+                        if (live_pos[3] >= 0) xs[live_pos[3]] = s3;
+                    }
+                }
             }
         }
         wave_lds_sync();
@@ -441,6 +514,104 @@ __global__ __launch_bounds__(BLOCK) void k_stage_any(AnyGraph g, float ws, const
         else if (n_out <= 48) any_last<3, OPEN>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
         else any_last<4, OPEN>(src, K, wt, any_pitch(K), bl, n_out, j, sig, out_row, logit_row);
         wave_lds_sync();   // (the group's LDS is rewritten by its next row)
+    }
+}
+
+// ---- live columns (gnnvc_set_generic_live_columns): which columns of a stage's input (n x f floats, f <= 64) hold anything but
+// +-0.0, and the compact table of those columns.  Both kernels run on the forward's stream ahead of the stage's launches; the
+// descriptor was zeroed by the forward's one hipMemsetAsync.
+//
+// k_any_live_mask: one pass over the n f words.  A thread ORs 1 << column for every word with a bit set below the sign; the
+// masks are reduced over the wave (shuffles), over the workgroup (LDS) and leave with ONE 64-bit atomicOr per workgroup.  The
+// body takes 16-byte loads from the first 16-byte boundary on (stage 0's input is the caller's, at any 4-byte alignment); the
+// words in front of it and behind the last whole 16 bytes are taken one by one by the grid's first threads.
+constexpr int kLiveBlock = 256;
+constexpr uint32_t kLivePackRows = 256;   // k_any_live_pack: rows per workgroup and pass
+
+__device__ __forceinline__ uint32_t live_wrap(uint32_t c, uint32_t f) {   // c < f + 4, f >= 2 -> c mod f
+    c -= c >= f ? f : 0u;
+    c -= c >= f ? f : 0u;
+    return c;
+}
+
+__global__ __launch_bounds__(kLiveBlock) void k_any_live_mask(const float *__restrict__ in, uint64_t total, uint32_t f,
+                                                             AnyLiveDesc *__restrict__ desc) {
+    __shared__ unsigned long long wave_mask[kLiveBlock / 64];
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(in);
+    const uint64_t head = std::min<uint64_t>(total, (uint64_t)((4u - (uint32_t)((reinterpret_cast<uintptr_t>(in) >> 2) & 3u)) & 3u));
+    const uint64_t nvec = (total - head) / 4u, tail0 = head + 4u * nvec;
+    const uint32_t tid = blockIdx.x * kLiveBlock + threadIdx.x, nthr = gridDim.x * kLiveBlock;   // (the grid is at most 2048 workgroups)
+    unsigned long long m = 0ull;
+    if (tid < head && (w[tid] & 0x7fffffffu)) m |= 1ull << (tid % f);
+    if (tid < total - tail0 && (w[tail0 + tid] & 0x7fffffffu)) m |= 1ull << (uint32_t)((tail0 + tid) % f);
+    const uint4 *v = reinterpret_cast<const uint4 *>(w + head);
+    // The threads that take 16-byte pieces step by a multiple of f words (the grid has at least 256 >= f threads): a thread's four
+    // columns never change, so the loop is a load and four ORs, four loads in flight, and the columns are looked at once, behind it.
+    const uint32_t stride = nthr / f * f;
+    if (tid < stride) {
+        uint32_t a0 = 0u, a1 = 0u, a2 = 0u, a3 = 0u;
+        uint64_t i = tid;
+        for (; i + 3ull * stride < nvec; i += 4ull * stride) {
+            const uint4 q0 = v[i], q1 = v[i + stride], q2 = v[i + 2ull * stride], q3 = v[i + 3ull * stride];
+            a0 |= q0.x | q1.x | q2.x | q3.x;
+            a1 |= q0.y | q1.y | q2.y | q3.y;
+            a2 |= q0.z | q1.z | q2.z | q3.z;
+            a3 |= q0.w | q1.w | q2.w | q3.w;
+        }
+        for (; i < nvec; i += stride) {
+            const uint4 q = v[i];
+            a0 |= q.x;
+            a1 |= q.y;
+            a2 |= q.z;
+            a3 |= q.w;
+        }
+        const uint32_t c = ((uint32_t)head + 4u * tid) % f;     // the column of the first word of this thread's 16 bytes
+        if (a0 & 0x7fffffffu) m |= 1ull << c;
+        if (a1 & 0x7fffffffu) m |= 1ull << live_wrap(c + 1u, f);
+        if (a2 & 0x7fffffffu) m |= 1ull << live_wrap(c + 2u, f);
+        if (a3 & 0x7fffffffu) m |= 1ull << live_wrap(c + 3u, f);
+    }
+    uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        lo |= (uint32_t)__shfl_xor((int)lo, o);
+        hi |= (uint32_t)__shfl_xor((int)hi, o);
+    }
+    if ((threadIdx.x & 63u) == 0u) wave_mask[threadIdx.x >> 6] = ((unsigned long long)hi << 32) | lo;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        unsigned long long all = 0ull;
+#pragma unroll
+        for (int i = 0; i < kLiveBlock / 64; ++i) all |= wave_mask[i];
+        if (all) atomicOr(&desc->mask, all);
+    }
+}
+
+// k_any_live_pack: every workgroup reads the mask and derives kept = popcount and used = (kept * 100 <= max_percent * f);
+// workgroup 0 writes them beside the mask.  Not used: nothing else happens.  Used: table[u * kept + r] = in[u * f + column_r],
+// column_r the r-th set bit (a list in LDS), a workgroup per kLivePackRows rows and pass — the index within the pass stays
+// below 2^14, everything that scales with n is 64-bit.  The table's row pitch is exactly `kept` floats.
+__global__ __launch_bounds__(kLiveBlock) void k_any_live_pack(const float *__restrict__ in, float *__restrict__ table, uint32_t n, uint32_t f,
+                                                             uint32_t max_percent, AnyLiveDesc *__restrict__ desc) {
+    __shared__ uint32_t cols[64];
+    const unsigned long long mask = desc->mask;
+    const uint32_t kept = (uint32_t)__popcll(mask), used = kept * 100u <= max_percent * f ? 1u : 0u;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) {
+        desc->kept = kept;
+        desc->used = used;
+    }
+    if (!used || kept == 0u) return;   // (block-uniform)
+    const uint32_t inv = (uint32_t)(((1ull << 32) + kept - 1u) / kept);   // ceil(2^32 / kept), kept >= 2 (kept == 1: not used)
+    if (threadIdx.x < 64u && ((mask >> threadIdx.x) & 1ull)) cols[__popcll(mask & ((1ull << threadIdx.x) - 1ull))] = threadIdx.x;
+    __syncthreads();
+    for (uint64_t base = (uint64_t)blockIdx.x * kLivePackRows; base < (uint64_t)n; base += (uint64_t)gridDim.x * kLivePackRows) {
+        const uint32_t rows = (uint32_t)std::min<uint64_t>(kLivePackRows, (uint64_t)n - base), cells = rows * kept;
+        const float *src = in + base * f;
+        float *dst = table + base * kept;
+        for (uint32_t t = threadIdx.x; t < cells; t += kLiveBlock) {
+            const uint32_t u = kept > 1u ? __umulhi(t, inv) : t, r = t - u * kept;   // t / kept: exact for t < 2^14, kept <= 64
+            dst[t] = src[(size_t)u * f + cols[r]];
+        }
     }
 }
 
@@ -717,13 +888,20 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
     const AnyRoute route = stage_any_route(sp);
     if (!route.ok || c.row_hi > g.hi() || c.row_lo < g.lo()) return hipErrorInvalidValue;
     if (sp.dense && rows != AnyRows::kAll) return hipErrorInvalidValue;   // (a dense stage has no heavy or giant split)
-    AnyRowSel sel{0u, 0u, nullptr, nullptr};
-    if (rows == AnyRows::kLight) {
-        sel = AnyRowSel{hr.from, 0u, nullptr, nullptr};
-    } else if (rows == AnyRows::kListed) {
+    // the LIVE instantiations (gnnvc_set_generic_live_columns): an all-rows or light-rows launch of a graph stage with f >= 2 that does
+    // not end in its bare linear layer, when the call carries the stage's descriptor and table — in the two fields of the row
+    // selection that such a launch does not otherwise read
+    const bool live = c.live_desc && c.live_table && rows != AnyRows::kListed && !sp.dense && sp.f >= 2 && sp.end != kEndNone;
+    AnyRowSel sel{0u, 0u, {nullptr}, {nullptr}};
+    if (rows == AnyRows::kLight) sel.from = hr.from;
+    if (live) {
+        sel.live = reinterpret_cast<const AnyLiveDesc *>(c.live_desc);   // (StageCall carries it untyped: the struct is this file's)
+        sel.live_table = c.live_table;
+    }
+    if (rows == AnyRows::kListed) {
         if (hr.n == 0) return hipSuccess;
         if (!hr.list || !hr.hsum) return hipErrorInvalidValue;
-        sel = AnyRowSel{hr.from, hr.n, hr.list, hr.hsum};
+        sel = AnyRowSel{hr.from, hr.n, {hr.list}, {hr.hsum}};
     }
     const AnyGraph plain = sp.dense ? AnyGraph{nullptr, nullptr, nullptr, nullptr} : AnyGraph{g.rowptr, g.col, g.w, g.nw};   // (a dense stage reads none of it)
     const AnyShape S = any_shape(sp);
@@ -738,30 +916,35 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
 #define GNNVC_ANY_ARGS                                                                                                        \
     grid, block, lds, c.stream, plain, c.ws, c.params + sp.param_offset, c.in, c.out, sp.sigmoid_last ? c.logits : nullptr, \
         c.row_lo, c.row_hi, S, sp.end, sel
-#define GNNVC_ANY_FORMS(MODE_, OPEN_)                                                       \
+#define GNNVC_ANY_FORMS(MODE_, OPEN_, LIVE_)                                                \
     do {                                                                                    \
         if (route.feat) {   /* (also within the default LDS bound: the 256-thread form) */  \
-            if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, true, OPEN_>), GNNVC_ANY_ARGS);     \
-            else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, true, OPEN_>), GNNVC_ANY_ARGS);  \
-            else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, true, OPEN_>), GNNVC_ANY_ARGS); \
+            if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, true, OPEN_, LIVE_>), GNNVC_ANY_ARGS);     \
+            else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, true, OPEN_, LIVE_>), GNNVC_ANY_ARGS);  \
+            else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, true, OPEN_, LIVE_>), GNNVC_ANY_ARGS); \
         }                                                                                   \
-        else if (!route.big) hipLaunchKernelGGL((k_stage_any<MODE_, kAnyBlock, false, false, OPEN_>), GNNVC_ANY_ARGS);      \
-        else if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, false, OPEN_>), GNNVC_ANY_ARGS); \
-        else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, false, OPEN_>), GNNVC_ANY_ARGS);   \
-        else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, false, OPEN_>), GNNVC_ANY_ARGS);           \
+        else if (!route.big) hipLaunchKernelGGL((k_stage_any<MODE_, kAnyBlock, false, false, OPEN_, LIVE_>), GNNVC_ANY_ARGS);      \
+        else if (route.threads == 1024) hipLaunchKernelGGL((k_stage_any<MODE_, 1024, true, false, OPEN_, LIVE_>), GNNVC_ANY_ARGS); \
+        else if (route.threads == 512) hipLaunchKernelGGL((k_stage_any<MODE_, 512, true, false, OPEN_, LIVE_>), GNNVC_ANY_ARGS);   \
+        else hipLaunchKernelGGL((k_stage_any<MODE_, 256, true, false, OPEN_, LIVE_>), GNNVC_ANY_ARGS);           \
     } while (0)
-    // (OPEN: only a stage that ends in its bare linear layer leaves the instantiations that were there; a dense stage's are OPEN)
-#define GNNVC_ANY_LAUNCH(MODE_)                              \
-    do {                                                     \
-        if (sp.end == kEndNone) GNNVC_ANY_FORMS(MODE_, true); \
-        else GNNVC_ANY_FORMS(MODE_, false);                  \
+    // (OPEN: only a stage that ends in its bare linear layer leaves the instantiations that were there; a dense stage's are OPEN.
+    // LIVE: never OPEN, never the listed rows — fourteen instantiations beside the others)
+#define GNNVC_ANY_LAUNCH(MODE_)                                     \
+    do {                                                            \
+        if (sp.end == kEndNone) GNNVC_ANY_FORMS(MODE_, true, false); \
+        else GNNVC_ANY_FORMS(MODE_, false, false);                  \
     } while (0)
     switch (rows) {
     case AnyRows::kAll:
-        if (sp.dense) GNNVC_ANY_FORMS(kAnyDense, true);
+        if (sp.dense) GNNVC_ANY_FORMS(kAnyDense, true, false);
+        else if (live) GNNVC_ANY_FORMS(kAnyAll, false, true);
         else GNNVC_ANY_LAUNCH(kAnyAll);
         break;
-    case AnyRows::kLight: GNNVC_ANY_LAUNCH(kAnyLight); break;
+    case AnyRows::kLight:
+        if (live) GNNVC_ANY_FORMS(kAnyLight, false, true);
+        else GNNVC_ANY_LAUNCH(kAnyLight);
+        break;
     case AnyRows::kListed: GNNVC_ANY_LAUNCH(kAnyListed); break;
     }
 #undef GNNVC_ANY_FORMS
@@ -775,27 +958,48 @@ hipError_t launch_stage_any(const StageCall &c, AnyRows rows, const AnyHeavyRows
 // The FEAT instantiations likewise (a wide stage may be a big one too), by gnnvc_set_generic_feature_width.
 template <bool FEAT>
 static hipError_t allow_stage_forms() {
-    static std::atomic<uint64_t> done[21];
+    static std::atomic<uint64_t> done[27];
     hipError_t rc = hipSuccess;
     int i = 0;
-#define GNNVC_ANY_ALLOW(MODE_, BLOCK_, OPEN_)                                                                                                  \
+#define GNNVC_ANY_ALLOW(MODE_, BLOCK_, OPEN_, LIVE_)                                                                                           \
     if (rc == hipSuccess)                                                                                                               \
-        rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_stage_any<MODE_, BLOCK_, true, FEAT, OPEN_>), (int)kAnyBigLdsBytes, done[i]);  \
+        rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_stage_any<MODE_, BLOCK_, true, FEAT, OPEN_, LIVE_>), (int)kAnyBigLdsBytes, done[i]);  \
     ++i
-#define GNNVC_ANY_ALLOW3(MODE_, OPEN_) GNNVC_ANY_ALLOW(MODE_, 256, OPEN_); GNNVC_ANY_ALLOW(MODE_, 512, OPEN_); GNNVC_ANY_ALLOW(MODE_, 1024, OPEN_)
-    GNNVC_ANY_ALLOW3(kAnyAll, false);
-    GNNVC_ANY_ALLOW3(kAnyLight, false);
-    GNNVC_ANY_ALLOW3(kAnyListed, false);
-    GNNVC_ANY_ALLOW3(kAnyAll, true);      // (gnnvc_set_generic_patterns: a last stage that ends in its bare linear layer)
-    GNNVC_ANY_ALLOW3(kAnyLight, true);
-    GNNVC_ANY_ALLOW3(kAnyListed, true);
-    GNNVC_ANY_ALLOW3(kAnyDense, true);    // (... and a dense stage)
+#define GNNVC_ANY_ALLOW3(MODE_, OPEN_, LIVE_) \
+    GNNVC_ANY_ALLOW(MODE_, 256, OPEN_, LIVE_); GNNVC_ANY_ALLOW(MODE_, 512, OPEN_, LIVE_); GNNVC_ANY_ALLOW(MODE_, 1024, OPEN_, LIVE_)
+    GNNVC_ANY_ALLOW3(kAnyAll, false, false);
+    GNNVC_ANY_ALLOW3(kAnyLight, false, false);
+    GNNVC_ANY_ALLOW3(kAnyListed, false, false);
+    GNNVC_ANY_ALLOW3(kAnyAll, true, false);      // (gnnvc_set_generic_patterns: a last stage that ends in its bare linear layer)
+    GNNVC_ANY_ALLOW3(kAnyLight, true, false);
+    GNNVC_ANY_ALLOW3(kAnyListed, true, false);
+    GNNVC_ANY_ALLOW3(kAnyDense, true, false);    // (... and a dense stage)
+    GNNVC_ANY_ALLOW3(kAnyAll, false, true);      // (gnnvc_set_generic_live_columns: the launches that may gather from the table)
+    GNNVC_ANY_ALLOW3(kAnyLight, false, true);
 #undef GNNVC_ANY_ALLOW3
 #undef GNNVC_ANY_ALLOW
     return rc;
 }
 hipError_t allow_big_stages() { return allow_stage_forms<false>(); }
 hipError_t allow_feat_stages() { return allow_stage_forms<true>(); }
+
+hipError_t launch_any_live(const StageCall &c, uint32_t max_percent) {
+    const StagePlan &sp = *c.sp;
+    const GraphDev &g = *c.g;
+    const uint32_t n = g.n;
+    if (n == 0) return hipSuccess;
+    if (sp.dense || sp.f < 2 || sp.f > kAnyFeatMax || max_percent < 1 || max_percent > 100 || !c.live_desc || !c.live_table || !c.in || g.sliced())
+        return hipErrorInvalidValue;
+    AnyLiveDesc *desc = reinterpret_cast<AnyLiveDesc *>(c.live_desc);
+    const uint64_t total = (uint64_t)n * (uint64_t)sp.f;
+    const unsigned mask_need = (unsigned)std::min<uint64_t>((total / 4u + kLiveBlock - 1) / kLiveBlock + 1u, 256u * 8u);
+    hipLaunchKernelGGL(k_any_live_mask, dim3(mask_need), dim3(kLiveBlock), 0, c.stream, c.in, total, (uint32_t)sp.f, desc);
+    hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess) return rc;
+    const unsigned pack_need = (unsigned)std::min<uint64_t>(((uint64_t)n + kLivePackRows - 1) / kLivePackRows, 256u * 8u);
+    hipLaunchKernelGGL(k_any_live_pack, dim3(pack_need), dim3(kLiveBlock), 0, c.stream, c.in, c.live_table, n, (uint32_t)sp.f, max_percent, desc);
+    return hipGetLastError();
+}
 
 hipError_t launch_any_heavy_sums(const StageCall &c, const AnyHeavyRows &hr) {
     if (c.row_hi <= c.row_lo || hr.n == 0) return hipSuccess;

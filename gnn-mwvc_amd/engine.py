@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "gnnvc_abi_version", "gnnvc_strerror", "gnnvc_last_error", "gnnvc_create", "gnnvc_create_multi", "gnnvc_create_multi_generic", "gnnvc_destroy",
     "gnnvc_set_weight_scale", "gnnvc_set_stream", "gnnvc_set_option", "gnnvc_get_info", "gnnvc_set_generic_heavy_rows",
     "gnnvc_set_generic_giant_rows", "gnnvc_set_generic_big_stages", "gnnvc_set_generic_feature_width",
-    "gnnvc_set_generic_patterns",
+    "gnnvc_set_generic_patterns", "gnnvc_set_generic_live_columns",
     "gnnvc_num_layers", "gnnvc_is_fused",
     "gnnvc_in_width", "gnnvc_out_width", "gnnvc_upload_graph", "gnnvc_attach_graph_device", "gnnvc_attach_graph_slice",
     "gnnvc_graph_staging", "gnnvc_staged_columns_ready", "gnnvc_commit_staged_graph",
@@ -132,6 +132,7 @@ def load_library():
     L.gnnvc_set_generic_big_stages.argtypes = [vp, u32]
     L.gnnvc_set_generic_feature_width.argtypes = [vp, u32]
     L.gnnvc_set_generic_patterns.argtypes = [vp, u32]
+    L.gnnvc_set_generic_live_columns.argtypes = [vp, u32]
     for name in ("gnnvc_num_layers", "gnnvc_is_fused", "gnnvc_in_width", "gnnvc_out_width",
                  "gnnvc_num_stages", "gnnvc_synchronize"):
         getattr(L, name).argtypes = [vp]
@@ -308,6 +309,18 @@ class Engine:
         multi-device handle.  get_info: "generic_patterns", "generic_stage_dense_<s>", "generic_stage_end_<s>" (0 ReLU, 1 sigmoid,
         2 none)."""
         self._check(self._L.gnnvc_set_generic_patterns(self._h, mask))
+
+    def set_generic_live_columns(self, max_percent: int):
+        """Opt-in: generic graph stages gather only the live columns of their input (gnnvc_set_generic_live_columns).  0 = off, the
+        default.  1 .. 100: inside a whole forward every graph stage with f >= 2 that does not end in its bare linear layer has
+        its input examined on the device — a column is dead when it is +-0.0 in every row — and gathers from a compact table of
+        the `kept` live columns iff kept * 100 <= max_percent * f (100: always; kept == 0: always, and nothing is gathered).
+        Same bits for every value.  Takes effect at the next forward; changes no admission; independent of the other
+        set_generic_* calls; stage-by-stage calls, dense stages, f == 1, sliced engines and multi-device handles are as without
+        it.  Raises GnnvcError -1 above 100, -5 on a multi-device handle.  get_info: "generic_live_columns" and, from the last
+        forward, "generic_live_kept_<s>" (-1 = not examined), "generic_live_used_<s>", "generic_live_mask_lo_<s>",
+        "generic_live_mask_hi_<s>" (one copy and one wait on the engine's stream per key)."""
+        self._check(self._L.gnnvc_set_generic_live_columns(self._h, max_percent))
 
     def audit_report(self) -> dict:
         """The on-device audit's counters and its last failure (option "audit_period"), key -> value."""

@@ -359,7 +359,10 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  *                         "generic_stage_threads_<s>"), and gnnvc_set_generic_feature_width (below) input and last widths up
  *                         to 64 (key "generic_feature_width"), and gnnvc_set_generic_patterns (below) a dense stage in front
  *                         of the first graph layer and a model that ends in a ReLU or in a bare linear layer (keys
- *                         "generic_patterns", "generic_stage_dense_<s>", "generic_stage_end_<s>").  "audit_period" audits nothing on
+ *                         "generic_patterns", "generic_stage_dense_<s>", "generic_stage_end_<s>"), and gnnvc_set_generic_live_columns
+ *                         (below) a gather from the compact table of a stage input's live columns, same bits (keys
+ *                         "generic_live_columns", "generic_live_kept_<s>", "generic_live_used_<s>", "generic_live_mask_lo_<s>",
+ *                         "generic_live_mask_hi_<s>").  "audit_period" audits nothing on
  *                         them, as on an unfused model: they are audited on demand, by gnnvc_forward_audited,
  *                         gnnvc_forward_audited_device and gnnvc_audit_stage_device (kernel k_audit_any: a wave per row, the
  *                         weights read as the model stores them — an implementation that shares nothing with k_stage_any; the
@@ -509,6 +512,39 @@ int gnnvc_set_generic_feature_width(gnnvc_engine *e, uint32_t max_width);
 #define GNNVC_PATTERN_PROLOGUE 1u
 #define GNNVC_PATTERN_OPEN_END 2u
 int gnnvc_set_generic_patterns(gnnvc_engine *e, uint32_t mask);
+
+/* Live columns of generic stages (option "generic_stages", kernel k_stage_any), opt-in.  After a ReLU many columns of a stage's
+ * input are +-0.0 in every row, and k_stage_any's gather loads them all the same, f floats per adjacency entry.  With this call
+ * a graph stage gathers from a compact table of the LIVE columns instead:
+ *   max_percent 0         off (the default): the engine launches exactly what it launches without this call;
+ *   max_percent 1 .. 100  on.  Inside a whole forward every graph stage with f >= 2 has its input examined on the device
+ *                         (k_any_live_mask: column c is dead iff (bits & 0x7fffffff) == 0 in all n rows — a denormal, or a value in a
+ *                         row no edge refers to, makes it live), and gathers from the table (k_any_live_pack: n rows of `kept`
+ *                         floats, kept = the number of live columns) iff kept * 100 <= max_percent * f.  The decision is the
+ *                         device's, per forward and stage: nothing is copied back and nothing is waited for.  100 uses the
+ *                         table for every such stage, also at kept == f; kept == 0 uses it under every value and gathers nothing;
+ *   anything else         GNNVC_ERR_INVALID, the engine unchanged.
+ * Results are bit-identical under every value: a neighbour sum is one fp32 add chain from +0.0f, a chain value is never -0.0f, and
+ * adding +-0.0 to it returns the same bits — so a dead column's sum is +0.0f for every row and the live columns' chains are the ones
+ * they were ("Live columns").  A row's own features, degree, W and NW are read as before.
+ * It applies to gnnvc_forward, gnnvc_forward_device, gnnvc_forward_audited and gnnvc_forward_audited_device on a single engine whose
+ * model runs as generic stages (the trained model under "generic_stages" 2 included); k_audit_any recomputes from the full rows, so an
+ * audited forward checks the table's route independently.  It does NOT apply — same launches and bits as without it — to dense
+ * stages, stages with f == 1, a last stage that ends in its bare linear layer, gnnvc_stage_forward_device and
+ * gnnvc_audit_stage_device (d_in is the caller's, per range), sliced engines, and gnnvc_create_multi_generic.  Heavy and giant rows
+ * (gnnvc_set_generic_heavy_rows, gnnvc_set_generic_giant_rows) keep reading full rows; the all-rows and light-rows launches read the
+ * table.  The table is a buffer of the engine's own, n x the widest such f floats.
+ * The call takes effect at the next forward.  It does not derive the stage list anew, so nothing is admitted or refused by it, and it
+ * is independent of gnnvc_set_generic_big_stages, gnnvc_set_generic_feature_width and gnnvc_set_generic_patterns.  On a model without a
+ * generic stage list the value is stored and does nothing.  A multi-device handle: GNNVC_ERR_UNSUPPORTED; a null engine:
+ * GNNVC_ERR_INVALID.
+ * gnnvc_get_info: "generic_live_columns" (the value in force) and, per stage and from the LAST forward, "generic_live_kept_<s>" (live
+ * columns of its input), "generic_live_used_<s>" (1 = its launches gathered from the table), "generic_live_mask_lo_<s>" and
+ * "generic_live_mask_hi_<s>" (the 64-bit column mask in two halves).  A stage the last forward did not examine — the call is off, the
+ * stage is not one of those above, no forward yet, n == 0 — reads kept -1, used 0, mask 0.  The values live on the device: asking for
+ * one of these keys costs one copy and one wait on the engine's stream.  The per-stage keys follow "generic_stage_layers_<s>":
+ * GNNVC_ERR_INVALID for a stage that does not exist or while the model is not generic. */
+int gnnvc_set_generic_live_columns(gnnvc_engine *e, uint32_t max_percent);
 
 /* Model introspection (what model::layers holds). */
 int gnnvc_num_layers(const gnnvc_engine *e);
