@@ -5928,10 +5928,13 @@ hipError_t launch_zero_pad_row(float *buf, uint32_t n, uint32_t width, hipStream
 }  // namespace gnnvc
 
 // Debugging aid, not part of include/gnnvc.h.  (nullptr, gnnvc::kProbeLiveObjects): the number of device / page-locked
-// allocations, events and streams this library holds in the process (gnnvc_device_mem.h; tests/test_gpu_lifetime.py).  Any other
+// allocations, events and streams this library holds in the process (gnnvc_device_mem.h; tests/test_gpu_lifetime.py).  (nullptr,
+// kProbeGuardsOn .. kProbeGuardsHitBandEnd): the guard bands of those allocations (tests/test_gpu_guard_bands.py).  Any other
 // kind: where the phase probe of a -DGNNVC_PHASE_PROBE=1 build writes its clock stamps (-3 in an ordinary build).
 extern "C" int gnnvc_debug_probe(void *buf, int kind) {
     if (kind == gnnvc::kProbeLiveObjects) return (int)gnnvc::g_live_objects.load();
+    if (kind >= gnnvc::kProbeGuardsOn && kind <= gnnvc::kProbeGuardsHitBandEnd)
+        return gnnvc::g_guards<gnnvc::mem_detail::HipRuntime>.probe(kind);
 #if GNNVC_PHASE_PROBE
     if (hipMemcpyToSymbol(HIP_SYMBOL(gnnvc::gnnvc_probe_buf), &buf, sizeof buf) != hipSuccess) return -1;
     if (hipMemcpyToSymbol(HIP_SYMBOL(gnnvc::gnnvc_probe_kind), &kind, sizeof kind) != hipSuccess) return -2;

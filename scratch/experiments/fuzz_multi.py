@@ -1,7 +1,12 @@
 """Randomised fuzz of the multi-device handle (gnnvc_create_multi, all "devices" = GPU 0): random graphs x parts x exchange
 options (pieces, packing, push, announcements) x plan options, both host hand-off routes, several forwards with the INPUT changing
 in the middle (another scale, an input that is no k / ws, arbitrary values) and a second graph on the same handle — logits against
-the oracle bit for bit.  python scratch/experiments/fuzz_multi.py [cases=100] [seed0=0]"""
+the oracle bit for bit.  python scratch/experiments/fuzz_multi.py [cases=100] [seed0=0]
+
+Two GPU tests load this file by its path and call one_case: tests/test_gpu_fuzz.py::test_multi_device_handle_fuzz_slice
+(one_case(case)) and tests/test_gpu_guard_bands.py::test_trained_model_on_several_parts (one_case(232, override=..., parts_override=...),
+which relies on case 232's draws — two hub graphs, the arbitrary-valued seventh input — overflowing the packed exchange).  Keep
+one_case's signature, the order of its rng draws and the module-level `om` as they are, or change those tests with them."""
 import sys, pathlib, time
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent.parent))
 import numpy as np

@@ -211,6 +211,25 @@ def test_the_cases_reach_every_specialisation():
     assert not missing, "classes that the fuzz does not reach:\n  " + "\n  ".join(missing)
 
 
+def test_the_cases_run_under_guard_bands_reach_what_they_are_pinned_for():
+    """tests/test_gpu_guard_bands.py runs a short list of these cases, and of tests/test_gpu_fuzz.py's, with guard bands around
+    every engine buffer: the lists are chosen for the kernels and list sizes they reach, which their records show here."""
+    from tests import test_gpu_guard_bands as gb
+    assert len(gb.GENERIC_CASES) <= 24 and len(set(gb.GENERIC_CASES)) == len(gb.GENERIC_CASES)
+    assert all(0 <= i < mz.N for i in gb.GENERIC_CASES)
+    reached = set().union(*(gb.generic_case_covers(i) for i in gb.GENERIC_CASES))
+    want = ({"BIG 256", "BIG 512", "BIG 1024", "FEAT", "OPEN", "dense prologue", "heavy 1", "heavy 17", "heavy 512",
+             "giant 1024 with segments 1", "not admitted"} | {f"graph {name}" for name in mz.GRAPH_NAMES})
+    assert not want - reached, sorted(want - reached)
+    assert len(gb.GENERIC_MULTI) == 6 and set(gb.GENERIC_MULTI) <= set(gb.GENERIC_CASES) & set(ADMITTED)
+    assert len(gb.PLAN_CASES) == 8 and len(gb.PLAN_STAGE_CASES) == 4 and set(gb.PLAN_STAGE_CASES) <= set(gb.PLAN_CASES)
+    assert {case: gb.plan_case_covers(case) for case in gb.PLAN_CASES} == gb.PLAN_COVERS   # what the list says of each case
+    reached = set().union(*gb.PLAN_COVERS.values())
+    want = {"plan_chunk_rows 16", "plan_chunk_rows 48", "giant_segments 1", "lds_table_skewed_rows > 0", "compact_gather 1",
+            "table_tiles 1 at table_tiles_min_n 0", "mfma_dense 0", "mfma_dense 1", "mfma_dense 2"}
+    assert not want - reached, sorted(want - reached)
+
+
 # ---------------------------------------------------------------- e. the restatement of the route
 
 def test_the_route_restatement_gives_the_agreed_figures():
