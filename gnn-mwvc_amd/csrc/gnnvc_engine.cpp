@@ -340,7 +340,10 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
             // are launched one round (256 chunks) at a time and the dense kernel of round k goes to the aux stream,
             // under the sums of round k + 1.  Metric graph: 1.71 -> 1.58 ms.  (Not for the feature stages: their dense
             // kernels store 64-byte rows and slow the co-running sums by more than is gained.)
-            c.rounds = e->opt.overlap && sp.variant == 2 && e->opt.mfma != 1;
+            // (a call of more rounds than there are round counters — "plan_chunk_rows" 16 on 300 K rows: 74 — runs its sums in
+            // one launch, as with "overlap_dense" 0: it used to be refused by launch_main, tools/optionflips.py random_2)
+            const uint32_t nrounds = ((hi - 1 - e->c4_base) / e->c4_rows - (lo - e->c4_base) / e->c4_rows) / 256u + 1u;
+            c.rounds = e->opt.overlap && sp.variant == 2 && e->opt.mfma != 1 && nrounds <= gnnvc::compact_rounds();
             c.emit = may_emit;   // this stage's own (aggregate-only, VALU) kernel produces for the next one
         }
     }

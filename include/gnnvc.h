@@ -161,7 +161,13 @@ int gnnvc_set_stream(gnnvc_engine *e, void *hip_stream);
  * work behind the engine's asynchronous calls with it. */
 int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
 
-/* Tuning options (take effect at the next graph upload / attach):
+/* Tuning options.  What a key decides about the graph itself — its row classes and thresholds, which plans it gets — is decided
+ * when a graph is handed over (upload / staged commit / attach) and holds until the next one; what a key decides about the
+ * launches — queues, kernel variants, when a plan that is still due is built — is read by the forward or stage call that follows.
+ * A key may be set at any time, also under a resident graph with plans in force: every call that follows gives the same bits,
+ * and the next hand-off leaves the engine as one that had the key set before its first graph — but for the table tiles' choice
+ * of columns, which an engine carries from graph to graph and which changes time only (tests/test_gpu_option_flips.py
+ * holds every key below to both, but the "audit_*" keys, "generic_stages" and "poison_features", which have tests of their own):
  *   "plans_at_handoff" 0|1|2  WHEN the per-graph plans below are built.  The reference's driver hands predict a new graph every
  *                         call and scores it once (src/GNN_VC.cpp:171-192), so what depends on the graph alone is built when
  *                         the graph is handed over (upload / staged commit / attach), not inside a later forward: 1 (default) =

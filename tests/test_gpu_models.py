@@ -53,19 +53,23 @@ def other_input(g):
     return (g.x() * np.float32(0.37)).astype(np.float32)
 
 
-def want_of(name, gname, what="logits"):
+def want_of(name, gname, what="logits", scale=1):
     """The oracle's logits (for g.x(), or "other": the other input), "h1" or "h2" of a family member on a named graph, computed
-    once: one walk through the oracle's layers gives all three (tests/test_modelgen.py checks that walk against predict)."""
-    if ("want", name, gname, what) not in _cache:
+    once: one walk through the oracle's layers gives all three (tests/test_modelgen.py checks that walk against predict).
+    scale: the weight scale is scale * g.ws instead of the driver's g.ws, the inputs stay the same (tests/flip_harness.py)."""
+    at = () if scale == 1 else (scale,)
+    if ("want", name, gname, what) + at not in _cache:
         g, om = graph_of(gname), oracle_of(name)
-        om.set_weight_scale(g.ws)
+        ws = float(np.float32(g.ws * scale))
+        om.set_weight_scale(ws)
         if what == "other":
-            _cache["want", name, gname, what] = om.logits(g, other_input(g))
+            _cache[("want", name, gname, what) + at] = om.logits(g, other_input(g))
         else:
-            pre = layer_outputs(om, g)
+            pre = layer_outputs(om, g, ws=ws)
             for k, v in (("h1", oracle_py.relu(pre[2])), ("h2", oracle_py.relu(pre[5])), ("logits", pre[8][:, 0].copy())):
-                _cache["want", name, gname, k] = v
-    return _cache["want", name, gname, what]
+                _cache[("want", name, gname, k) + at] = v
+        om.set_weight_scale(g.ws)
+    return _cache[("want", name, gname, what) + at]
 
 
 def open_engine(name, g, opts=(), devices=None):

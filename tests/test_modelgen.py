@@ -24,13 +24,14 @@ def graphs():
     return {k: f() for k, f in GRAPHS.items()}
 
 
-def layer_outputs(om, g, x=None):
-    """[pre-activation of linear layer i for i in 0 .. 8] through the oracle's own layer functions (ws = g.ws)."""
+def layer_outputs(om, g, x=None, ws=None):
+    """[pre-activation of linear layer i for i in 0 .. 8] through the oracle's own layer functions (ws = g.ws unless given)."""
     h = np.ascontiguousarray(g.x() if x is None else x, dtype=np.float32).reshape(g.n, 1)
+    ws = g.ws if ws is None else ws
     pre = []
     for i, (W, b) in enumerate(om.linear_params()):
         if i % 3 == 0:
-            h = oracle_py.graph_layer(g, g.ws, h)
+            h = oracle_py.graph_layer(g, ws, h)
         h = oracle_py.linear_layer(h, W, b)
         pre.append(h)
         if i < 8:
