@@ -104,6 +104,18 @@ __device__ __forceinline__ float relu_ref(float x) { return (x < 0.0f) ? 0.0f : 
 // in fp64 (expf_glibc.h): same bits as the host libm the reference links.
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf_glibc(-x)); }
 
+// relu_ref() that also records whether the unit can be non-zero anywhere in the wave: the compare that drives the select is
+// balloted, and "!(t < 0) in some lane" is shifted into `live` through SCC — two scalar instructions a unit, no VALU beyond
+// the ReLU's own compare and select.  Unit j of an N-wide layer ends up at bit N - 1 - j (each push shifts the earlier ones
+// up).  The mask is a superset of "non-zero in some lane": it also holds a unit that is exactly +-0 in some lanes and negative
+// in the others (and a NaN unit: !(NaN < 0)).  EVERY lane of the wave must be active (the ballot sees active lanes only).
+__device__ __forceinline__ float relu_live(float t, uint32_t &live) {
+    const bool keep = !(t < 0.0f);
+    const unsigned long long m = __ballot(keep);
+    asm("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, %0" : "+s"(live) : "s"(m) : "scc");
+    return keep ? t : 0.0f;
+}
+
 // out[j] = act( fma-chain_k( in[k] * W[k][j] ) + b[j] ): per output one
 // sequential-k chain from +0.0f (what cblas_sgemm computes at these sizes),
 // then a separately rounded bias add.  W and b are wave-uniform addresses, so
@@ -138,12 +150,26 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // One test per term whatever `skip` says: the input's bits without the sign, or'ed with a uniform 1 when nothing is to be
 // skipped (NaNs count as non-zero: their terms stay).  The inputs are pinned in VGPRs first: otherwise the compiler computes
 // each of them just ahead of its test, from the previous layer's weights parked in VGPR lanes (hundreds of v_readlane).
-template <int K, int N, int ACT>
-__device__ __forceinline__ void dense_live(float (&in)[K], float (&out)[N], const float *__restrict__ W,
-                                           const float *__restrict__ b, bool skip) {
+// FROM_MASK: the inputs come straight out of an in-kernel ReLU whose compares already said which units can be non-zero
+// (`live_in`: relu_live's mask of a K-wide layer, unit k at bit K - 1 - k).  Term k then runs iff its bit is set — one scalar
+// bit test ahead of the branch, no VALU — and with `skip` off every bit is set.  The mask holds every unit the test above would
+// run, and a few more (relu_live): running a term is what the reference does, leaving one out rests on the argument above.
+// Returns the liveness mask of its own outputs (ACT == 0; unused, it costs nothing).
+template <int K, int N, int ACT, bool FROM_MASK = false>
+__device__ __forceinline__ uint32_t dense_live(float (&in)[K], float (&out)[N], const float *__restrict__ W,
+                                               const float *__restrict__ b, bool skip, uint32_t live_in = 0) {
+    static_assert(K <= 32 && N <= 32, "one 32-bit liveness mask a layer");
     const uint32_t all = skip ? 0u : 1u;
+    const uint32_t live = skip ? live_in : 0xFFFFFFFFu;
+    // (pinned two to a register pair: v_pk_fma_f32 takes its broadcast input as the low or the high half of an aligned pair, and
+    // an input pinned alone gets a pair to itself — 64 VGPRs for 32 inputs, which cost k_dense_f16 its fifth wave per SIMD)
+    static_assert(K % 2 == 0, "inputs in pairs");
+    f32x2 pin[K / 2];
 #pragma unroll
-    for (int k = 0; k < K; ++k) asm volatile("" : "+v"(in[k]));
+    for (int k = 0; k < K / 2; ++k) {
+        pin[k] = f32x2{in[2 * k], in[2 * k + 1]};
+        asm volatile("" : "+v"(pin[k]));
+    }
     // the chains as pairs (v_pk_fma_f32: two fmas, each rounded once, as two __builtin_fmaf): written out, because across
     // these branches the compiler pairs out[1] with out[2] and pays for it in register moves
     static_assert(N % 2 == 0, "outputs in pairs");
@@ -152,18 +178,20 @@ __device__ __forceinline__ void dense_live(float (&in)[K], float (&out)[N], cons
     for (int j = 0; j < N / 2; ++j) acc[j] = f32x2{0.0f, 0.0f};
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const float a = in[k];
-        if (__any(((__float_as_uint(a) << 1) | all) != 0u)) {   // (uniform)
+        const float a = pin[k / 2][k % 2];
+        if (FROM_MASK ? (live >> (K - 1 - k) & 1u) != 0u : (bool)__any(((__float_as_uint(a) << 1) | all) != 0u)) {   // (uniform)
             const f32x2 aa = {a, a};
 #pragma unroll
             for (int j = 0; j < N / 2; ++j) acc[j] = __builtin_elementwise_fma(aa, f32x2{W[k * N + 2 * j], W[k * N + 2 * j + 1]}, acc[j]);
         }
     }
+    uint32_t live_out = 0;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         const float t = acc[j / 2][j % 2] + b[j];
-        out[j] = (ACT == 0) ? relu_ref(t) : t;
+        out[j] = (ACT == 0) ? relu_live(t, live_out) : t;
     }
+    return live_out;
 }
 
 // XCD-aware tile mapping.  Workgroups are dealt round-robin over the 8 XCDs
@@ -388,6 +416,64 @@ __device__ __forceinline__ void c4_emit(const float *trow, uint32_t nz, uint32_t
     const uint32_t ok = spec[0];
     c4_emit_with(trow, nz, u, mine, lane, ok, ok == 1u ? spec[1] : 0u, ok == 1u ? spec[2] : 0u, ok == 1u ? spec[3] : 0u,
                  ok == 1u ? spec[4] : 0u, table, counts);
+}
+
+// c4_emit for a kernel that still holds the row in registers (k_stage_f1, k_dense_f16): same counts, same table row.  The sixteen
+// compares x[j] != 0 go straight into scalar masks (no per-lane non-zero word to build and take apart again); a column's count
+// is a scalar popcount written into its lane; the stray flag is the OR of the masks of the columns outside the table (a bit mask
+// of the spec's columns, built once), read per lane with one shift.  The table values come from the LDS tile row, as in c4_emit.
+// EVERY lane of the wave must be active at the call.
+template <int LANE>
+__device__ __forceinline__ uint32_t put_lane(uint32_t v, uint32_t s /* uniform */) {   // v with lane LANE's value replaced by s
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "n"(LANE));
+    return v;
+}
+template <int J>
+__device__ __forceinline__ void c4_count_cols(const float (&x)[16], unsigned long long mm, uint32_t tcols, uint32_t &my,
+                                              unsigned long long &stray) {
+    if constexpr (J < 16) {
+        const unsigned long long nzj = __ballot(x[J] != 0.0f);
+        my = put_lane<J>(my, (uint32_t)__popcll(nzj & mm));
+        stray |= (tcols >> J & 1u) ? 0ull : nzj;
+        c4_count_cols<J + 1>(x, mm, tcols, my, stray);
+    }
+}
+__device__ __forceinline__ void c4_emit_regs(const float (&x)[16], const float *trow, uint32_t u, bool mine, int lane,
+                                             const uint32_t *__restrict__ spec, c4row *__restrict__ table,
+                                             unsigned long long *__restrict__ counts) {
+    const uint32_t ok = spec[0];
+    const uint32_t s0 = ok == 1u ? spec[1] : 0u, s1 = ok == 1u ? spec[2] : 0u, s2 = ok == 1u ? spec[3] : 0u, s3 = ok == 1u ? spec[4] : 0u;
+    const uint32_t tcols = (1u << (s0 & 31u)) | (1u << (s1 & 31u)) | (1u << (s2 & 31u)) | (1u << (s3 & 31u));
+    const unsigned long long mm = __ballot(mine);
+    unsigned long long stray = 0;
+    uint32_t my = 0;
+    c4_count_cols<0>(x, mm, tcols, my, stray);   // (unrolled by hand: the lane of a v_writelane is an immediate)
+    my = put_lane<16>(my, (uint32_t)__popcll(mm));
+    if (lane <= 16 && my) atomicAdd(&counts[(blockIdx.x & (kEmitSlots - 1)) * kEmitStride + lane], (unsigned long long)my);
+    if (ok == 1u && mine) {   // (a plan of several passes writes its tables in k_c4_compact)
+        const float a = trow[s0], b = trow[s1], c = trow[s2], d = trow[s3];
+        c4row out = {a == 0.0f ? 0.0f : a, b == 0.0f ? 0.0f : b, c == 0.0f ? 0.0f : c, d == 0.0f ? 0.0f : d};
+        const bool odd = !(a >= 0.0f) || !(b >= 0.0f) || !(c >= 0.0f) || !(d >= 0.0f);   // (see c4_emit_with)
+        if (odd || (stray >> lane & 1ull)) out[0] = __uint_as_float(__float_as_uint(out[0]) | 0x80000000u);   // stray non-zeros: flag the vertex
+        if (odd) out[1] = __uint_as_float(__float_as_uint(out[1]) | 0x80000000u);
+        table[u] = out;
+    }
+}
+
+#ifndef GNNVC_EMIT_REGS
+#define GNNVC_EMIT_REGS 1   // k_stage_f1 and k_dense_f16 emit from the registers (A/B: 0 = through the per-lane non-zero word)
+#endif
+__device__ __forceinline__ void c4_emit_row(const float (&x)[16], const float *trow, uint32_t u, bool mine, int lane,
+                                            const uint32_t *__restrict__ spec, c4row *__restrict__ table,
+                                            unsigned long long *__restrict__ counts) {
+    if constexpr (GNNVC_EMIT_REGS) {
+        c4_emit_regs(x, trow, u, mine, lane, spec, table, counts);
+    } else {
+        uint32_t nz = 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) nz |= (x[j] != 0.0f ? 1u : 0u) << j;
+        c4_emit(trow, nz, u, mine, lane, spec, table, counts);
+    }
 }
 
 // AGGONLY (compact-table plan): every row's aggregate arrives ready-made — four sums in acc4 for clean rows, the
@@ -723,9 +809,23 @@ __device__ __forceinline__ void fma_term(f32x2 (&acc)[N / 2], float a, const flo
     for (int j = 0; j < N / 2; ++j) acc[j] = __builtin_elementwise_fma(aa, f32x2{Wrow[2 * j], Wrow[2 * j + 1]}, acc[j]);
 }
 template <int N>
-__device__ __forceinline__ void bias_relu(const f32x2 (&acc)[N / 2], float (&out)[N], const float *__restrict__ b) {
+__device__ __forceinline__ uint32_t bias_relu(const f32x2 (&acc)[N / 2], float (&out)[N], const float *__restrict__ b) {
+    uint32_t live = 0;   // (the layer's liveness mask, for the dense_live that takes `out`: relu_live)
 #pragma unroll
-    for (int j = 0; j < N; ++j) out[j] = relu_ref(acc[j / 2][j % 2] + b[j]);
+    for (int j = 0; j < N; ++j) out[j] = relu_live(acc[j / 2][j % 2] + b[j], live);
+    return live;
+}
+// dense<K, K, N, 0>() that also hands out its liveness mask: every term runs, the chains as the same explicit pairs (with the
+// ballots in its tail the vectoriser no longer pairs the plain form's fmas by itself)
+template <int K, int N>
+__device__ __forceinline__ uint32_t dense_relu_live(const float (&in)[K], float (&out)[N], const float *__restrict__ W,
+                                                    const float *__restrict__ b) {
+    f32x2 acc[N / 2];
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) acc[j] = f32x2{0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < K; ++k) fma_term<N>(acc, in[k], W + k * N);
+    return bias_relu<N>(acc, out, b);
 }
 
 template <int N1, int N2, int N3, bool SIGMOID>
@@ -757,6 +857,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
     const float *W2 = b1 + N1, *b2 = W2 + N1 * N2;
     const float *W3 = b2 + N2, *b3 = W3 + N2 * N3;
     float x1[N1];
+    uint32_t live1;   // which of x1's units can be non-zero in this wave, from the first layer's ReLU compares (relu_live)
     // k_c4_choose writes the table's columns in ascending order, the slots without a column (0xFFFFFFFF) last; route B walks them
     // in that order, and a descriptor that is not so sends its dirty waves to route C, which asks nothing of it (a guard only:
     // k_c4_choose is the one writer of these words, so no input reaches it and no test can)
@@ -810,7 +911,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
                 if (__any((__float_as_uint(v[k]) << 1) != 0u)) fma_term<N1>(acc, v[k], W1 + k * N1);   // (uniform)
         }
         own_terms();
-        bias_relu<N1>(acc, x1, b1);
+        live1 = bias_relu<N1>(acc, x1, b1);
     } else {                   // (C)
         const float4 h0 = fin[(size_t)u * 4], h1 = fin[(size_t)u * 4 + 1], h2 = fin[(size_t)u * 4 + 2], h3 = fin[(size_t)u * 4 + 3];
         // first-layer inputs in k order: 0..15 aggregate, 16 = h[0], 17 = degree, 18 = W/ws, 19 = NW/ws, 20..31 = h[4..15]
@@ -841,12 +942,14 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
         x0[28] = h3.x; x0[29] = h3.y; x0[30] = h3.z; x0[31] = h3.w;
         // rows 32..34 of W1 meet exact zeros; of the 32 others, the terms that are zero in the whole wave go where the layer's
         // weights allow it (skip bit 0; without it, and under dense_skip_zeros = 0, every term runs)
-        dense_live<32, N1, 0>(x0, x1, W1, b1, (skip & 1u) != 0);
+        live1 = dense_live<32, N1, 0>(x0, x1, W1, b1, (skip & 1u) != 0);   // (x0 is no ReLU's output: the test stays)
     }
     float x2[N2], x3[N3];
-    dense_live<N1, N2, 0>(x1, x2, W2, b2, (skip & 2u) != 0);
+    // the feature stage takes its hidden layers' liveness from the ReLU compares of the layer before (relu_live); the last stage
+    // keeps the test of the values: its kernel was measured no faster with the mask (profiles/dense_bookkeeping)
+    const uint32_t live2 = dense_live<N1, N2, 0, !SIGMOID>(x1, x2, W2, b2, (skip & 2u) != 0, live1);
     if constexpr (SIGMOID) dense<N2, N2, N3, 1>(x2, x3, W3, b3);   // (16 -> 1: one fma per term is not worth a branch)
-    else dense_live<N2, N3, 0>(x2, x3, W3, b3, (skip & 4u) != 0);
+    else dense_live<N2, N3, 0, true>(x2, x3, W3, b3, (skip & 4u) != 0, live2);
     if constexpr (SIGMOID) {
         if (mine) {
             if (logits) logits[u] = x3[0];
@@ -855,13 +958,9 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
     } else {
         // the wave's 64 x 16 outputs through LDS: every global store instruction writes 16 full rows
         float *T = lds[threadIdx.x >> 6];
-        uint32_t nz = 0;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            T[lane * kOutPitch + j] = x3[j];
-            nz |= (x3[j] != 0.0f ? 1u : 0u) << j;
-        }
-        if (emit_counts) c4_emit(&T[lane * kOutPitch], nz, u, mine, lane, emit_spec, emit_table, emit_counts);
+        for (int j = 0; j < 16; ++j) T[lane * kOutPitch + j] = x3[j];
+        if (emit_counts) c4_emit_row(x3, &T[lane * kOutPitch], u, mine, lane, emit_spec, emit_table, emit_counts);
         wave_lds_sync();
         const int q = lane >> 2, c = lane & 3;
 #pragma unroll
@@ -1510,7 +1609,9 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
     const float *W2 = b1 + N1, *b2 = W2 + N1 * N2;
     const float *W3 = b2 + N2, *b3 = W3 + N2 * N3;
     float x1[N1];
-    dense<5, 5, N1, 0>(x0, x1, W1, b1);   // 5 -> 32 stays on the VALU (K = 5 is not matrix-shaped)
+    uint32_t live1 = 0;   // (VALU layers: which of x1's units can be non-zero in this wave, from the ReLU's compares)
+    if constexpr (MFMA) dense<5, 5, N1, 0>(x0, x1, W1, b1);   // 5 -> 32 stays on the VALU (K = 5 is not matrix-shaped)
+    else live1 = dense_relu_live<5, N1>(x0, x1, W1, b1);
     static_assert(N3 == 16, "feature stages emit 16 floats per vertex");
     const int q = lane >> 2, c = lane & 3;
     wave_lds_sync();  // index stage is dead; reuse the region
@@ -1541,15 +1642,12 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
             for (int r = 0; r < 8; ++r) T[(32 * vt + v) * kOutPitch + mfma_feat(r, h)] = d[vt][r];
     } else {
         float x2[N2], x3[N3];
-        dense_live<N1, N2, 0>(x1, x2, W2, b2, (skip & 2u) != 0);
-        dense_live<N2, N3, 0>(x2, x3, W3, b3, (skip & 4u) != 0);
-        uint32_t nz = 0;
+        // each hidden layer's liveness comes out of the ReLU compares of the layer before it (relu_live), not from a test of its own
+        const uint32_t live2 = dense_live<N1, N2, 0, true>(x1, x2, W2, b2, (skip & 2u) != 0, live1);
+        dense_live<N2, N3, 0, true>(x2, x3, W3, b3, (skip & 4u) != 0, live2);
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            T[lane * kOutPitch + j] = x3[j];
-            nz |= (x3[j] != 0.0f ? 1u : 0u) << j;
-        }
-        if (emit_counts) c4_emit(&T[lane * kOutPitch], nz, u, mine, lane, emit_spec, emit_table, emit_counts);
+        for (int j = 0; j < 16; ++j) T[lane * kOutPitch + j] = x3[j];
+        if (emit_counts) c4_emit_row(x3, &T[lane * kOutPitch], u, mine, lane, emit_spec, emit_table, emit_counts);
     }
     wave_lds_sync();
 #pragma unroll
