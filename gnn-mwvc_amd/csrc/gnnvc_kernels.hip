@@ -219,11 +219,17 @@ __device__ __forceinline__ uint32_t tile_for_wave(uint32_t ntiles, bool interlea
 #ifndef GNNVC_SORTED_MIX
 #define GNNVC_SORTED_MIX 1   // degree-sorted tiles are dispatched alternating between the two ends of the list (A/B: 0)
 #endif
-constexpr int kRegionFloats = 2112;          // 8448 B per wave, 33 KiB per workgroup
+constexpr int kRegionFloats = 2112;          // 8448 B per wave, 33 KiB per workgroup: four workgroups a CU, four waves per SIMD
 constexpr int kInPitch = 33;                 // 32 inputs in k order; odd pitch: conflict-free ds_read_b32 down a column
 constexpr int kOutPitch = 17;
 constexpr uint32_t kStageCap = 1792 - 4;     // most col entries a tile may stage (7 x 256 minus alignment slack)
 static_assert(kWave * kInPitch <= kRegionFloats && 1792 <= kRegionFloats, "region too small");
+// A kernel that neither stages column indices (use 1) nor takes the matrix cores' input tile (use 2) needs the output tile alone:
+// 4352 B per wave, 17 KiB per workgroup, and the LDS no longer sets its waves per SIMD (k_stage_f1<.., SLIM>).
+constexpr int kSlimRegionFloats = kWave * kOutPitch;
+#ifndef GNNVC_STAGE0_SLIM
+#define GNNVC_STAGE0_SLIM 1   // the LDS-table plan's VALU stage kernel takes the slim region (A/B: 0 = the 33 KiB region and staging)
+#endif
 
 // Stage col[c0, c1) of this wave's tile into LDS.  Returns the entry index that
 // LDS slot 0 corresponds to (c0 rounded down to a 16-byte boundary).
@@ -827,7 +833,36 @@ __device__ __forceinline__ uint32_t dense_relu_live(const float (&in)[K], float 
     for (int k = 0; k < K; ++k) fma_term<N>(acc, in[k], W + k * N);
     return bias_relu<N>(acc, out, b);
 }
+// K consecutive terms of a chain that is carried in `acc`, each behind dense_live's wave-uniform value test (`all`: 1 = run every
+// term, 0 = leave out a term whose input is +-0 in all 64 lanes; NaNs stay).  The K inputs are pinned in pairs first, as there.
+template <int K, int N>
+__device__ __forceinline__ void live_terms(f32x2 (&acc)[N / 2], const float (&in)[K], const float *__restrict__ W, uint32_t all) {
+    static_assert(K % 2 == 0, "inputs in pairs");
+    f32x2 pin[K / 2];
+#pragma unroll
+    for (int k = 0; k < K / 2; ++k) {
+        pin[k] = f32x2{in[2 * k], in[2 * k + 1]};
+        asm volatile("" : "+v"(pin[k]));
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float a = pin[k / 2][k % 2];
+        if (__any(((__float_as_uint(a) << 1) | all) != 0u)) fma_term<N>(acc, a, W + k * N);   // (uniform)
+        // the pairs named as pairs at every join (no instruction): without it the optimiser carries the 32 halves that bias_relu
+        // reads up through these branches beside the pairs, and the allocator keeps two and three copies of the accumulators
+        // (98 and 128 VGPRs with the pairs named once at the end and not at all)
+#pragma unroll
+        for (int j = 0; j < N / 2; ++j) asm volatile("" : "+v"(acc[j]));
+    }
+}
+#ifndef GNNVC_ROUTE_C_GROUPS
+#define GNNVC_ROUTE_C_GROUPS 1   // k_dense_f16's route C carries its accumulators over three groups of terms (A/B: 0 = all 32 inputs at once)
+#endif
 
+// Route C and the registers: with all 32 inputs pinned in pairs beside the 32 accumulators, the own row's four float4 and a dirty
+// row's sixteen sums, route C's peak set the allocation of EVERY wave at 82 / 81 VGPRs, one granule above the 80 that a sixth wave
+// per SIMD needs, though one wave in a hundred of the metric graph takes the route.  In groups (0..15 | 16..19 | 20..31) the peak
+// is 32 accumulators and 16 inputs, below routes A and B's.
 template <int N1, int N2, int N3, bool SIGMOID>
 __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, const float4 *__restrict__ fin, float *__restrict__ fout,
                                                       float *__restrict__ logits, const float *__restrict__ P, uint32_t row_lo,
@@ -912,7 +947,48 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
         }
         own_terms();
         live1 = bias_relu<N1>(acc, x1, b1);
-    } else {                   // (C)
+    } else if constexpr (GNNVC_ROUTE_C_GROUPS) {   // (C)
+        // the 32-term chain in three groups of ascending k over ONE set of accumulator pairs, each group's inputs fetched and
+        // pinned just ahead of it: never 32 inputs, 32 accumulators and the source rows alive together (see above the kernel)
+        const uint32_t all = (skip & 1u) ? 0u : 1u;   // (without skip bit 0, and under dense_skip_zeros = 0, every term runs)
+        f32x2 acc[N1 / 2];
+        {   // k = 0 .. 15: the sums, a clean row's from the passes' acc4, a dirty row's from agg16
+            float s[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) s[k] = 0.0f;
+            for (uint32_t qp = 0; qp < npass; ++qp) {   // (uniform)
+                const uint32_t *dc = c4desc + (qp == 0 ? 1 : 4 + 4 * qp);
+                const uint32_t e0 = dc[0], e1 = dc[1], e2 = dc[2], e3 = dc[3];
+                const float4 aq = qp == 0 ? a : acc4[(size_t)qp * g.n + u];
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    s[k] = ((uint32_t)k == e0) ? aq.x : ((uint32_t)k == e1) ? aq.y : ((uint32_t)k == e2) ? aq.z : ((uint32_t)k == e3) ? aq.w : s[k];
+            }
+            if (__any(dirty)) {
+                const size_t slot = dirty ? (size_t)__float_as_uint(a.y) : 0;
+                const float4 g0 = agg16[slot * 4], g1 = agg16[slot * 4 + 1], g2 = agg16[slot * 4 + 2], g3 = agg16[slot * 4 + 3];
+                const float gg[16] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w, g3.x, g3.y, g3.z, g3.w};
+#pragma unroll
+                for (int k = 0; k < 16; ++k) s[k] = dirty ? gg[k] : s[k];
+            }
+#pragma unroll
+            for (int j = 0; j < N1 / 2; ++j) acc[j] = f32x2{0.0f, 0.0f};
+            live_terms<16, N1>(acc, s, W1, all);
+        }
+        size_t own = (size_t)u * 4;
+        {   // k = 16 .. 19: h[0], degree, W/ws, NW/ws
+            float s[4] = {fin[own].x, f_deg, f_w, f_nw};
+            live_terms<4, N1>(acc, s, W1 + 16 * N1, all);
+        }
+        {   // k = 20 .. 31: h[4..15], fetched only now (the row's index goes through a register the compiler cannot see through,
+            // behind the pins of the groups before it: nothing hoists these loads over the first twenty terms)
+            asm volatile("" : "+v"(own));
+            const float4 h1 = fin[own + 1], h2 = fin[own + 2], h3 = fin[own + 3];
+            float s[12] = {h1.x, h1.y, h1.z, h1.w, h2.x, h2.y, h2.z, h2.w, h3.x, h3.y, h3.z, h3.w};
+            live_terms<12, N1>(acc, s, W1 + 20 * N1, all);
+        }
+        live1 = bias_relu<N1>(acc, x1, b1);   // (rows 32..34 of W1 meet exact zeros)
+    } else {                   // (C, the form before GNNVC_ROUTE_C_GROUPS: all 32 inputs built first, then one dense_live)
         const float4 h0 = fin[(size_t)u * 4], h1 = fin[(size_t)u * 4 + 1], h2 = fin[(size_t)u * 4 + 2], h3 = fin[(size_t)u * 4 + 3];
         // first-layer inputs in k order: 0..15 aggregate, 16 = h[0], 17 = degree, 18 = W/ws, 19 = NW/ws, 20..31 = h[4..15]
         float x0[32];
@@ -1525,7 +1601,11 @@ __global__ __launch_bounds__(kBlock) void k_stage_w1(GraphDev g, float ws, const
 // (ep = g.rowptr, ecol = g.col, acc_in = nullptr) or, in the column-blocked plan,
 // the rows' entries of the LAST column block with the partial sums of the earlier
 // blocks arriving in acc_in (same add sequence as the unblocked loop).
-template <int N1, int N2, int N3, int S, bool MFMA>
+// SLIM (the LDS-table plan's VALU launch): the sums arrive complete in acc_in and the gather loop runs no trip, so the region
+// is the output tile alone (kSlimRegionFloats) and seven waves fit a SIMD where the 33 KiB region holds four.  A forward whose
+// input does not match the table (*acc_bad != 0) gathers here with its indices straight from `ecol`, as tiles above kStageCap
+// do in the full form: the engine drops the plan after three such forwards.
+template <int N1, int N2, int N3, int S, bool MFMA, bool SLIM = false>
 __global__ __launch_bounds__(kBlock) void k_stage_f1(
         GraphDev g, float ws, const float *__restrict__ xin, float *__restrict__ fout,
         const float *__restrict__ P, uint32_t row_lo, uint32_t row_hi,
@@ -1539,7 +1619,8 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
     // to add; != 0 -> the plan did not apply to this input, acc_in is ignored and every entry is gathered here.
     // srt_vertex (skewed graphs): tiles of 64 vertices of similar degree from the degree-sorted list (see
     // k_stage_f16) instead of 64 consecutive rows, so a tile's gather rounds are not set by one heavy row.
-    __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock][kRegionFloats];
+    static_assert(!(SLIM && MFMA), "the matrix cores' input tile needs the full region");
+    __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock][SLIM ? kSlimRegionFloats : kRegionFloats];
     const bool acc_full = acc_bad && *acc_bad == 0;
     if (acc_bad && !acc_full) acc_in = nullptr;
     const bool sorted = srt_vertex != nullptr;   // uniform
@@ -1576,9 +1657,11 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
         re = (mine && !acc_full) ? ep[uc + 1] : rs;
         const uint32_t c0 = __builtin_amdgcn_readfirstlane(rs);
         const uint32_t vend = (v0 + kWave < row_hi) ? v0 + kWave : row_hi;
-        const uint32_t c1 = acc_full ? c0 : ep[vend];   // wave-uniform: end of the tile's last valid row
-        staged = (c1 - c0) <= kStageCap;
-        if (staged) sbase = stage_cols(ecol, c0, c1, stage, lane);
+        if constexpr (!SLIM) {
+            const uint32_t c1 = acc_full ? c0 : ep[vend];   // wave-uniform: end of the tile's last valid row
+            staged = (c1 - c0) <= kStageCap;
+            if (staged) sbase = stage_cols(ecol, c0, c1, stage, lane);
+        }
         f_w = (float)g.w[uc] / ws;
         f_nw = (float)g.nw[uc] / ws;
     }
@@ -1592,7 +1675,7 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const uint32_t ee = eb + s;
-            const uint32_t cv = staged ? stage[ee - sbase] : ecol[ee];
+            const uint32_t cv = (!SLIM && staged) ? stage[ee - sbase] : ecol[ee];
             const float v = xin[(ee < re) ? cv : uc];
             xs[s] = (ee < re) ? v : 0.0f;  // agg is never -0.0f, so + 0.0f is exact
         }
@@ -5563,7 +5646,7 @@ hipError_t launch_stage0_lds_table(const StageCall &c, const LdsTablePlan &lp, u
                            (const uint32_t *)nullptr, (c4row *)nullptr, (unsigned long long *)nullptr,
                            (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u, c.skip);
     else
-        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.params + sp.param_offset,
+        GNNVC_LAUNCH((k_stage_f1<32, 32, 16, 4, false, GNNVC_STAGE0_SLIM != 0>), grid, block, 0, c.stream, g, c.ws, c.in, c.out, c.params + sp.param_offset,
                            c.row_lo, c.row_hi, g.rowptr, g.col, acc, a.long_thresh, a.interleave ? 1 : 0, (const uint32_t *)bad,
                            a.emit.spec, reinterpret_cast<c4row *>(a.emit.table), a.emit.counts,
                            (const uint32_t *)nullptr, (const uint4 *)nullptr, 0u, c.skip);
