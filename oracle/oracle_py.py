@@ -137,6 +137,16 @@ class OracleModel:
                 out.append((W, b))
         return out
 
+    def widest_output(self, in_width: int) -> int:
+        """The widest row any layer writes for an input of in_width columns (at least 2 in_width + 3, and never
+        under 35): what predict sizes its buffer by, whichever layer it stops after."""
+        wd, widest = in_width, max(2 * in_width + 3, 35)
+        for i in range(self.n_layers):
+            l = self._m.contents.layers[i]
+            wd = l.m if l.kind == 0 else 2 * wd + 3 if l.kind == 1 else wd
+            widest = max(widest, wd)
+        return widest
+
     def set_weight_scale(self, ws: float):
         lib().oracle_model_set_weight_scale(self._m, C.c_float(ws))
 
@@ -144,10 +154,10 @@ class OracleModel:
         """Returns the [n, width] output after layer `stop_after` (-1 = all).  as_shipped: the reference's
         threading (products through the cblas_sgemm set with use_openblas(), everything else serial)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
-        x = x.reshape(g.n, x.size // g.n if g.n else 1)
+        if not (x.ndim == 2 and x.shape[0] == g.n and x.shape[1] > 0):   # (an n x w array keeps its width, also for n = 0)
+            x = x.reshape(g.n, x.size // g.n if g.n else 1)
         gs, keep = _graph_struct(g)
-        out = np.empty((max(g.n, 1), 35 if x.shape[1] <= 16 else 2 * x.shape[1] + 3),
-                       dtype=np.float32)
+        out = np.empty((max(g.n, 1), self.widest_output(x.shape[1])), dtype=np.float32)
         wd = C.c_uint32(0)
         rc = lib().oracle_predict(self._m, C.byref(gs), x.shape[1], _ptr(x), _ptr(out),
                                   C.byref(wd), stop_after, (1 if parallel_agg else 0) | (2 if as_shipped else 0))

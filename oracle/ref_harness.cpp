@@ -26,6 +26,22 @@ reduction_graph<uint32_t, uint32_t> make_graph(uint32_t n, const uint64_t *rowpt
             if (col[e] > u) edges.push_back({u, col[e]});
     return reduction_graph<uint32_t, uint32_t>(weights, edges);  // sorted by construction
 }
+
+// the reference's parser on the model text; n_layers_keep >= 0 truncates the text's layer count first
+void parse_model(gnn::model &m, const char *model_text, int n_layers_keep, float ws) {
+    std::string text(model_text);
+    if (n_layers_keep >= 0) {
+        // header is "<name> <n> Layers": rewrite the count; the parser stops after that many records
+        std::istringstream hs(text);
+        std::string name, cnt;
+        hs >> name >> cnt;
+        const size_t pos = text.find(cnt, text.find(name) + name.size());
+        text.replace(pos, cnt.size(), std::to_string(n_layers_keep));
+    }
+    std::istringstream is(text);
+    is >> m;
+    m.set_weight_scale(ws);
+}
 }  // namespace
 
 extern "C" {
@@ -35,19 +51,8 @@ extern "C" {
 // layer count (e.g. 20 of 21 drops the final sigmoid -> logits).
 int ref_predict(const char *model_text, int n_layers_keep, float ws, uint32_t n, const uint64_t *rowptr,
                 const uint32_t *col, const uint32_t *w, const float *x, float *out, uint32_t *out_width) {
-    std::string text(model_text);
-    if (n_layers_keep >= 0) {
-        // header is "<name> <n> Layers": rewrite the count; the parser stops after that many records
-        std::istringstream hs(text);
-        std::string name, cnt;
-        hs >> name >> cnt;
-        const size_t pos = text.find(cnt, name.size());
-        text.replace(pos, cnt.size(), std::to_string(n_layers_keep));
-    }
     gnn::model m;
-    std::istringstream is(text);
-    is >> m;
-    m.set_weight_scale(ws);
+    parse_model(m, model_text, n_layers_keep, ws);
     auto g = make_graph(n, rowptr, col, w);
     matrix in(n, 1), res;
     for (uint32_t u = 0; u < n; ++u) in(u, 0) = x[u];
@@ -55,6 +60,28 @@ int ref_predict(const char *model_text, int n_layers_keep, float ws, uint32_t n,
     *out_width = (uint32_t)res.get_width();
     for (size_t i = 0; i < res.get_height(); ++i)
         for (size_t j = 0; j < res.get_width(); ++j) out[i * res.get_width() + j] = res(i, j);
+    return 0;
+}
+
+// reference gnn::model::predict on an n x in_width input (row-major); out holds out_capacity floats.  Returns 0 and the
+// result's width in *out_width; where n * width floats do not fit it returns 1 with the width set and nothing written.
+// n_layers_keep as ref_predict's (at least one layer must stay: predict asserts that).
+int ref_predict_wide(const char *model_text, int n_layers_keep, float ws, uint32_t n, const uint64_t *rowptr,
+                     const uint32_t *col, const uint32_t *w, uint32_t in_width, const float *x, float *out,
+                     uint64_t out_capacity, uint32_t *out_width) {
+    if (n_layers_keep == 0 || in_width == 0) return 2;
+    gnn::model m;
+    parse_model(m, model_text, n_layers_keep, ws);
+    auto g = make_graph(n, rowptr, col, w);
+    matrix in(n, in_width), res;
+    for (uint32_t u = 0; u < n; ++u)
+        for (uint32_t j = 0; j < in_width; ++j) in(u, j) = x[(size_t)u * in_width + j];
+    m.predict(in, res, g);
+    const size_t wd = res.get_width();
+    *out_width = (uint32_t)wd;
+    if ((uint64_t)n * wd > out_capacity) return 1;
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j < wd; ++j) out[i * wd + j] = res(i, j);
     return 0;
 }
 

@@ -26,18 +26,8 @@ def oracle_at(name, ws):
 
 
 def predict(om, g, x, stop_after=-1):
-    """oracle_predict through its C entry point with an output buffer as wide as the model's widest layer (OracleModel.predict
-    sizes its buffer for 35 columns, or 2 w + 3 for a wide input)."""
-    import ctypes as C
-    x = np.ascontiguousarray(x, dtype=np.float32).reshape(g.n, -1)
-    gs, keep = oracle_py._graph_struct(g)
-    widest = max([2 * x.shape[1] + 3, 35] + [2 * max(W.shape) + 3 for W, _ in om.linear_params()])
-    out = np.empty((max(g.n, 1), widest), dtype=np.float32)
-    wd = C.c_uint32(0)
-    rc = oracle_py.lib().oracle_predict(om._m, C.byref(gs), x.shape[1], oracle_py._ptr(x), oracle_py._ptr(out), C.byref(wd), stop_after, 0)
-    assert rc == 0, rc
-    del keep
-    return out.reshape(-1)[: g.n * wd.value].reshape(g.n, wd.value).copy()
+    """OracleModel.predict, which sizes its output buffer by the model's widest layer: the name this family's tests call it by."""
+    return om.predict(g, np.ascontiguousarray(x, dtype=np.float32).reshape(g.n, -1), stop_after=stop_after)
 
 
 def walk(om, name, g, ws=None, x=None, first=0, count=None):

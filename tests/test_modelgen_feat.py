@@ -20,18 +20,8 @@ LINEAR, GRAPH, RELU, SIGMOID = 0, 1, 2, 3
 
 
 def predict(om, g, x, stop_after=-1):
-    """oracle_predict through its C entry point with an output buffer of the model's own width: OracleModel.predict sizes its
-    buffer for outputs of at most 35 columns (2 w + 3 for an input of w > 16), which out64's 64 scores a vertex do not fit."""
-    import ctypes as C
-    x = np.ascontiguousarray(x, dtype=np.float32).reshape(g.n, -1)
-    gs, keep = oracle_py._graph_struct(g)
-    widest = max([x.shape[1]] + [max(W.shape) for W, _ in om.linear_params()])
-    out = np.empty((max(g.n, 1), widest), dtype=np.float32)
-    wd = C.c_uint32(0)
-    rc = oracle_py.lib().oracle_predict(om._m, C.byref(gs), x.shape[1], oracle_py._ptr(x), oracle_py._ptr(out), C.byref(wd), stop_after, 0)
-    assert rc == 0, rc
-    del keep
-    return out.reshape(-1)[: g.n * wd.value].reshape(g.n, wd.value).copy()
+    """OracleModel.predict: its output buffer is as wide as the model's widest layer (out64's 64 scores a vertex fit)."""
+    return om.predict(g, x, stop_after=stop_after)
 
 # member -> SHA-256 of its text
 DIGESTS = {
