@@ -269,48 +269,48 @@ struct StageChoice {
 
 int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float *in, const float *out, bool in_forward,
                  StageChoice &c) {
-    const bool longs = e->n_long > 0;
+    const bool longs = e->pg.rows.n_long > 0;
     const gnnvc::StagePlan &sp = e->stages[stage];
     // An announcement (gnnvc_stage_input_ready) covers the calls for ITS stage that follow it.  A call for any other
     // stage means the caller has moved on — the next forward has begun, or the announced buffer is about to be
     // rewritten — and a call that writes into the announced buffer ends it too: the table must never outlive its input.
-    if (e->pg.c4_prepared_stage != -1 && (stage != e->pg.c4_prepared_stage || out == e->c4_prepared_in)) e->pg.c4_prepared_stage = -1;
+    if (e->pg.c4.prepared_stage != -1 && (stage != e->pg.c4.prepared_stage || out == e->pg.c4.prepared_in)) e->pg.c4.prepared_stage = -1;
     // Producer side of the compact-table plan: inside a whole forward (engine-owned feature buffers nobody else
     // writes) the stage kernel that produces the next 16-wide stage's input also counts its non-zeros and writes
     // its compact rows, so that stage can skip its two passes over the input.  Only the VALU variants emit.
-    const int fused_in = in_forward ? e->c4_fused_for : -1;   // is THIS stage's input covered by the previous kernel?
-    e->c4_fused_for = -1;
-    const bool may_emit = in_forward && e->pg.c4_ready && !e->pg.c4_range_mode && e->c4_base == 0 && e->c4_end == e->g.n && !longs &&
+    const int fused_in = in_forward ? e->call.c4_fused_for : -1;   // is THIS stage's input covered by the previous kernel?
+    e->call.c4_fused_for = -1;
+    const bool may_emit = in_forward && e->pg.c4.ready && !e->pg.c4.range_mode && e->pg.c4.base == 0 && e->pg.c4.end == e->g.n && !longs &&
                           (size_t)stage + 1 < e->stages.size() && e->stages[stage + 1].f == 16 && lo == 0 && hi == e->g.n &&
-                          e->opt.mfma != 1 && !e->pg.c4_stage_off[stage + 1];
-    c.long_thresh = (sp.f == 16) ? e->thresh_f16 : e->long_thresh;
+                          e->opt.mfma != 1 && !e->pg.c4.stage_off[stage + 1];
+    c.long_thresh = (sp.f == 16) ? e->pg.rows.thresh_f16 : e->pg.rows.long_thresh;
     c.mfma = e->opt.mfma == 1 || (e->opt.mfma == 2 && sp.f == 16);
-    const bool t4 = in_forward && e->t4_now && lo == 0 && hi == e->g.n;   // table tiles: whole forwards on a graph that qualifies
+    const bool t4 = in_forward && e->call.t4_now && lo == 0 && hi == e->g.n;   // table tiles: whole forwards on a graph that qualifies
     c.emit_t4 = t4 && (size_t)stage + 1 < e->stages.size();
     if (stage == 0) {
         // The LDS-table plan works in chunks of ~19.5 K rows, one workgroup each: a call that covers fewer than
         // three quarters of a GPU's worth of chunks (the pieces of a pipelined multi-GPU run) would leave most CUs
         // idle for the time one chunk takes — such calls use the column-blocked plan instead.
-        if (e->pg.graph_uses >= 1 && !e->pg.lt_tried) {
+        if (e->pg.graph_uses >= 1 && !e->pg.lt.tried) {
             int rc = build_lds_table(e);
             if (rc) return rc;
         }
         // (a skewed graph's plan sums all of its rows at once: whole-graph calls only)
         // (consecutive-row layout: any call that covers at least three quarters of the chunks a full GPU takes — or of the plan's
         // own, where the plan is a rank's slice of fewer)
-        const uint32_t lt_need = std::min(192u, e->lt_chunks - e->lt_chunks / 4u);
-        const bool lt_fits = e->pg.lt_ready && !e->pg.lt_off && hi > lo &&
-                             (e->lt_mapped ? (lo == 0 && hi == e->g.n)
-                                           : (lo >= e->lt_base && hi <= e->lt_end &&
-                                              ((hi - 1 - e->lt_base) / e->lt_rows - (lo - e->lt_base) / e->lt_rows + 1) >= lt_need));
-        if (e->pg.graph_uses >= 1 && !lt_fits && !e->pg.blocked_tried) {
+        const uint32_t lt_need = std::min(192u, e->pg.lt.chunks - e->pg.lt.chunks / 4u);
+        const bool lt_fits = e->pg.lt.ready && !e->pg.lt.off && hi > lo &&
+                             (e->pg.lt.mapped ? (lo == 0 && hi == e->g.n)
+                                           : (lo >= e->pg.lt.base && hi <= e->pg.lt.end &&
+                                              ((hi - 1 - e->pg.lt.base) / e->pg.lt.rows - (lo - e->pg.lt.base) / e->pg.lt.rows + 1) >= lt_need));
+        if (e->pg.graph_uses >= 1 && !lt_fits && !e->pg.blk.tried) {
             int rc = build_blocked(e);
             if (rc) return rc;
         }
         ++e->pg.graph_uses;
-        c.sums = lt_fits ? StageChoice::kLdsTable : (e->pg.blocked_ready ? StageChoice::kBlocked : StageChoice::kGather);
-        if (lt_fits && in_forward) e->pg.lt_used = true;
-        if (lt_fits && e->lt_mapped) c.long_thresh = e->lt_plan_thresh;   // the plan holds every row below the giant ones
+        c.sums = lt_fits ? StageChoice::kLdsTable : (e->pg.blk.ready ? StageChoice::kBlocked : StageChoice::kGather);
+        if (lt_fits && in_forward) e->pg.lt.used = true;
+        if (lt_fits && e->pg.lt.mapped) c.long_thresh = e->pg.lt.plan_thresh;   // the plan holds every row below the giant ones
         c.emit = may_emit;
         if (c.sums != StageChoice::kGather) return GNNVC_OK;   // (those two bring their own tile order)
     } else if (sp.f == 16 && t4) {
@@ -319,19 +319,19 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
         // (the second forward on a graph builds the plan; a graph whose plain 16-wide stages cost well above the build — the
         // option's bound — builds it in its first, which is all a score-once caller ever runs)
         const bool first_too = e->opt.compact_first_entries && e->g.nnz >= e->opt.compact_first_entries && lo == 0 && hi == e->g.n && in_forward;
-        if (!e->pg.c4_range_mode && (e->pg.graph_uses >= 2 || first_too) && !e->pg.c4_tried) {
+        if (!e->pg.c4.range_mode && (e->pg.graph_uses >= 2 || first_too) && !e->pg.c4.tried) {
             int rc = build_compact(e);
             if (rc) return rc;
         }
-        const bool whole_plan = e->pg.c4_ready && e->c4_base == 0 && e->c4_end == e->g.n && !e->pg.c4_stage_off[stage];
-        const bool prepared = e->pg.c4_ready && e->pg.c4_prepared_stage == stage && e->c4_prepared_in == in &&
-                              lo >= e->c4_base && hi <= e->c4_end && hi > lo;
+        const bool whole_plan = e->pg.c4.ready && e->pg.c4.base == 0 && e->pg.c4.end == e->g.n && !e->pg.c4.stage_off[stage];
+        const bool prepared = e->pg.c4.ready && e->pg.c4.prepared_stage == stage && e->pg.c4.prepared_in == in &&
+                              lo >= e->pg.c4.base && hi <= e->pg.c4.end && hi > lo;
         if (prepared && !longs) {
             // gnnvc_stage_input_ready wrote the table for this input: any call that fills at least half the
             // GPU with chunks takes the sums from it (smaller ones would leave most CUs idle for a chunk's time)
-            const uint32_t nchunks = (hi - 1 - e->c4_base) / e->c4_rows - (lo - e->c4_base) / e->c4_rows + 1;
+            const uint32_t nchunks = (hi - 1 - e->pg.c4.base) / e->pg.c4.rows - (lo - e->pg.c4.base) / e->pg.c4.rows + 1;
             if (nchunks >= 128u) c.sums = StageChoice::kCompactPrepared;
-        } else if (!e->pg.c4_range_mode && whole_plan && !longs && (uint64_t)(hi - lo) * 2 >= e->g.n) {
+        } else if (!e->pg.c4.range_mode && whole_plan && !longs && (uint64_t)(hi - lo) * 2 >= e->g.n) {
             // worth its fixed cost (count + compact the whole input) only when this call covers most of the rows
             c.sums = StageChoice::kCompactWhole;
             c.fused_counts = fused_in == stage;
@@ -342,7 +342,7 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
             // kernels store 64-byte rows and slow the co-running sums by more than is gained.)
             // (a call of more rounds than there are round counters — "plan_chunk_rows" 16 on 300 K rows: 74 — runs its sums in
             // one launch, as with "overlap_dense" 0: it used to be refused by launch_main, tools/optionflips.py random_2)
-            const uint32_t nrounds = ((hi - 1 - e->c4_base) / e->c4_rows - (lo - e->c4_base) / e->c4_rows) / 256u + 1u;
+            const uint32_t nrounds = ((hi - 1 - e->pg.c4.base) / e->pg.c4.rows - (lo - e->pg.c4.base) / e->pg.c4.rows) / 256u + 1u;
             c.rounds = e->opt.overlap && sp.variant == 2 && e->opt.mfma != 1 && nrounds <= gnnvc::compact_rounds();
             c.emit = may_emit;   // this stage's own (aggregate-only, VALU) kernel produces for the next one
         }
@@ -350,10 +350,10 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
     // degree-sorted tiles on skewed graphs (every stage; the list is cached per row range)
     int rc = ensure_sorted(e, lo, hi);
     if (rc) return rc;
-    if (e->srt_cur >= 0 && e->srt[e->srt_cur].use) {
-        c.sorted.n = e->srt[e->srt_cur].n;
-        c.sorted.vertex = e->srt[e->srt_cur].vertex.p;
-        c.sorted.meta = e->srt[e->srt_cur].meta.p;
+    if (e->call.srt_cur >= 0 && e->pg.sorted[e->call.srt_cur].use) {
+        c.sorted.n = e->pg.sorted[e->call.srt_cur].n;
+        c.sorted.vertex = e->srt.range[e->call.srt_cur].vertex.p;
+        c.sorted.meta = e->srt.range[e->call.srt_cur].meta.p;
         c.rounds = false;   // (the plan forced onto a graph with sorted tiles: the gathering kernel does the stage)
     }
     return GNNVC_OK;
@@ -374,28 +374,28 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
     // then they run ahead of the tile kernel on the main queue instead: power-law 1 M 0.89 ms (long rows beside the giant
     // walk: 1.15), R-MAT-22 2.62 ms (long rows on the main queue: 2.79).
     const bool side = e->opt.side_streams != 0;
-    const bool long_on_main = side && (e->opt.long_on_main < 0 ? (e->n_giant != 0 && e->giant_walk_bound) : e->opt.long_on_main != 0);
+    const bool long_on_main = side && (e->opt.long_on_main < 0 ? (e->pg.rows.n_giant != 0 && e->pg.rows.giant_walk_bound) : e->opt.long_on_main != 0);
     const bool side_long = side && !long_on_main;
     hipStream_t s_long = side_long ? e->long_stream : e->stream;
     hipStream_t s_giant = !side ? e->stream : (long_on_main ? e->giant_stream : e->long_stream);
-    e->side_join = !side ? 0 : (long_on_main ? 2 : 1);
+    e->call.side_join = !side ? 0 : (long_on_main ? 2 : 1);
     // rows from this degree on go the giant way in this stage
-    const uint32_t giant_from = call.sp->f == 16 ? e->giant_f16() : e->giant_thresh;
+    const uint32_t giant_from = call.sp->f == 16 ? e->giant_f16() : e->pg.rows.giant_thresh;
     gnnvc::StageCall giant = call;   // (on the main queue until the fork; the pruned view only where the option asks for it)
     if (!e->opt.prune_giant) giant.g = &e->g;
     gnnvc::GiantRows gr;
     bool gather_first = false;
-    if (e->n_giant) {
-        gr.n = e->n_giant;
-        gr.blocks = e->giant_blocks;
-        gr.meta = e->gi_meta.p;
-        gr.off = e->gi_off.p;
-        gr.slab = e->gi_slab.p;
-        gr.agg = e->gi_agg.p;
-        if (e->gi_maxseg > 1) {
-            gr.segsum = e->gi_segsum.p;
-            gr.segmap = e->gi_segmap.p;
-            gr.maxseg = e->gi_maxseg;
+    if (e->pg.rows.n_giant) {
+        gr.n = e->pg.rows.n_giant;
+        gr.blocks = e->pg.rows.giant_blocks;
+        gr.meta = e->gi.meta.p;
+        gr.off = e->gi.off.p;
+        gr.slab = e->gi.slab.p;
+        gr.agg = e->gi.agg.p;
+        if (e->pg.rows.maxseg > 1) {
+            gr.segsum = e->gi.segsum.p;
+            gr.segmap = e->gi.segmap.p;
+            gr.maxseg = e->pg.rows.maxseg;
         }
         // The giant rows' gather on the main queue, ahead of the fork (see launch_giant_stage) — where it is small (a throughput
         // kernel that delays the tile kernel by what it takes alone: R-MAT-22's 7.5 M giant entries 0.03 - 0.05 ms, R-MAT-24's
@@ -405,7 +405,7 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
         // ... or, however large, in an F = 1 stage that has no plan (a graph's first forward): every long row's chain is on the
         // side queue there and the gather at its head waited for slots for as long as the tile kernel ran (R-MAT-24: 3.1 ms
         // for a kernel that takes 0.6 alone; the stage 6.1 ms against the tile kernel's 3.3)
-        gather_first = side && (e->opt.giant_gather_first < 0 ? (!long_on_main && (e->giant_entries <= (16ull << 20) || plain_f1))
+        gather_first = side && (e->opt.giant_gather_first < 0 ? (!long_on_main && (e->pg.rows.giant_entries <= (16ull << 20) || plain_f1))
                                                                : e->opt.giant_gather_first != 0);
         if (gather_first) HIP_TRY(e, gnnvc::launch_giant_stage(giant, gr, giant_from, gnnvc::GiantPart::kGather));
     }
@@ -413,7 +413,7 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
         HIP_TRY(e, hipEventRecord(e->ev_fork, e->stream));
         if (side_long) HIP_TRY(e, hipStreamWaitEvent(e->long_stream, e->ev_fork, 0));
     }
-    if (e->n_giant) {   // the heaviest rows: beside the tile kernel
+    if (e->pg.rows.n_giant) {   // the heaviest rows: beside the tile kernel
         if (long_on_main) HIP_TRY(e, hipStreamWaitEvent(e->giant_stream, e->ev_fork, 0));
         giant.stream = s_giant;
         HIP_TRY(e, gnnvc::launch_giant_stage(giant, gr, giant_from, gather_first ? gnnvc::GiantPart::kAfterGather : gnnvc::GiantPart::kAll));
@@ -421,10 +421,10 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
     }
     // (with rows classed by the entries they have left, k_long_* takes rows from gv.eff_thresh entries on whatever their degree)
     const uint32_t long_from = gv.prune_eff ? std::min(thr, gv.eff_thresh) : thr;
-    if ((e->n_giant < e->n_long || giant_from > e->giant_thresh) && long_from < giant_from) {   // (equal: a plan or the giant kernels have every row in between)
+    if ((e->pg.rows.n_giant < e->pg.rows.n_long || giant_from > e->pg.rows.giant_thresh) && long_from < giant_from) {   // (equal: a plan or the giant kernels have every row in between)
         gnnvc::StageCall lng = call;
         lng.stream = s_long;
-        HIP_TRY(e, gnnvc::launch_long_stage(lng, {.list = e->long_list.p, .n = e->n_long, .min_deg = thr, .max_deg = giant_from}));
+        HIP_TRY(e, gnnvc::launch_long_stage(lng, {.list = e->long_list.p, .n = e->pg.rows.n_long, .min_deg = thr, .max_deg = giant_from}));
     }
     if (side_long) HIP_TRY(e, hipEventRecord(e->ev_long, e->long_stream));
     return GNNVC_OK;
@@ -444,16 +444,16 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     // by a memset here otherwise)
     auto arm_emit = [&]() -> int {
         if (!c.emit) return GNNVC_OK;
-        const bool zero = e->c4_emit_zero;
-        e->c4_emit_zero = false;   // (the kernel armed here counts into them)
+        const bool zero = e->call.c4_emit_zero;
+        e->call.c4_emit_zero = false;   // (the kernel armed here counts into them)
         if (!zero) {
-            ++e->plan_memsets;
-            HIP_TRY(e, hipMemsetAsync(e->c4_emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
+            ++e->pg.plan_memsets;
+            HIP_TRY(e, hipMemsetAsync(e->c4.emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
         }
-        emit.spec = e->c4_desc.p + gnnvc_engine::kDescWords * stage;   // consumer stage `stage + 1`: its descriptor words
-        emit.table = e->c4_table.p;
-        emit.counts = e->c4_emit_counts.p;
-        e->c4_fused_for = stage + 1;
+        emit.spec = e->c4.desc.p + gnnvc_engine::kDescWords * stage;   // consumer stage `stage + 1`: its descriptor words
+        emit.table = e->c4.table.p;
+        emit.counts = e->c4.emit_counts.p;
+        e->call.c4_fused_for = stage + 1;
         return GNNVC_OK;
     };
     // First use of the compact-table plan on this graph: no earlier forward has said which four columns the NEXT stage's
@@ -463,42 +463,42 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     // run, which then writes the table on its way.  The consumer's k_c4_choose still decides from the counts of ALL rows
     // and has the table rewritten if the pilot chose otherwise: the pilot changes time, never a result.
     auto pilot = [&]() -> int {
-        if (!c.emit || e->pg.c4_seeded[stage + 1] || !e->opt.pilot_rows) return GNNVC_OK;
-        e->pg.c4_seeded[stage + 1] = true;
+        if (!c.emit || e->pg.c4.seeded[stage + 1] || !e->opt.pilot_rows) return GNNVC_OK;
+        e->pg.c4.seeded[stage + 1] = true;
         const uint32_t rows = std::min(e->opt.pilot_rows, hi - lo);
         if ((uint64_t)rows * 8 > (uint64_t)(hi - lo)) return GNNVC_OK;   // (a graph this small is its own pilot: not worth a launch)
-        uint32_t *cons = e->c4_desc.p + gnnvc_engine::kDescWords * stage;   // consumer stage `stage + 1`
-        e->c4_emit_zero = false;
-        ++e->plan_memsets;
-        HIP_TRY(e, hipMemsetAsync(e->c4_emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
+        uint32_t *cons = e->c4.desc.p + gnnvc_engine::kDescWords * stage;   // consumer stage `stage + 1`
+        e->call.c4_emit_zero = false;
+        ++e->pg.plan_memsets;
+        HIP_TRY(e, hipMemsetAsync(e->c4.emit_counts.p, 0, gnnvc::kEmitCounters * sizeof(unsigned long long), e->stream));
         gnnvc::EmitArgs pe;
-        pe.spec = e->c4_desc.p + 2 * gnnvc_engine::kDescWords + 4;   // a word that is always 0: count, do not write table rows
-        pe.table = e->c4_table.p;
-        pe.counts = e->c4_emit_counts.p;
+        pe.spec = e->c4.desc.p + 2 * gnnvc_engine::kDescWords + 4;   // a word that is always 0: count, do not write table rows
+        pe.table = e->c4.table.p;
+        pe.counts = e->c4.emit_counts.p;
         gnnvc::StageCall first = plain;   // (every row of them on VALU tiles, no logits)
         first.row_hi = lo + rows;
         first.logits = nullptr;
         HIP_TRY(e, gnnvc::launch_stage(first, {.interleave = true, .emit = pe}));
-        HIP_TRY(e, gnnvc::compact_choose(e->c4_emit_counts.p, 64, rows, cons, 1u, e->stream, /*clear_counts=*/true));
-        e->c4_emit_zero = true;
+        HIP_TRY(e, gnnvc::compact_choose(e->c4.emit_counts.p, 64, rows, cons, 1u, e->stream, /*clear_counts=*/true));
+        e->call.c4_emit_zero = true;
         return GNNVC_OK;
     };
     if (c.emit_t4) {   // this stage's epilogue counts its output's columns and writes the next stage's table (for that stage's last choice)
         const int cons = stage + 1;
-        emit.spec = e->t4_desc_of(cons, e->t4_parity);
-        emit.table = e->t4_table[cons - 1].p;
-        emit.counts = e->t4_counts_of(cons, e->t4_parity);   // (cleared by the consumer's launch of the previous forward: k_stage_t4)
+        emit.spec = e->t4.desc_of(cons, e->t4.parity);
+        emit.table = e->t4.table[cons - 1].p;
+        emit.counts = e->t4.counts_of(cons, e->t4.parity);   // (cleared by the consumer's launch of the previous forward: k_stage_t4)
     }
     if (c.sums == StageChoice::kTableTiles) {
-        uint32_t *d_in = e->t4_desc_of(stage, e->t4_parity), *d_out = e->t4_desc_of(stage, e->t4_parity ^ 1u);
-        const bool solo = e->t4_fit_seen[stage] && e->opt.t4_solo;
-        HIP_TRY(e, gnnvc::launch_stage_t4(plain, {.table_in = e->t4_table[stage - 1].p,
-                                                  .counts_in = e->t4_counts_of(stage, e->t4_parity),
-                                                  .counts_zero = e->t4_counts_of(stage, e->t4_parity ^ 1u),
-                                                  .desc_in = d_in, .desc_out = d_out, .emit = emit, .interleave = e->interleave, .solo = solo}));
+        uint32_t *d_in = e->t4.desc_of(stage, e->t4.parity), *d_out = e->t4.desc_of(stage, e->t4.parity ^ 1u);
+        const bool solo = e->pg.t4.fit_seen[stage] && e->opt.t4_solo;
+        HIP_TRY(e, gnnvc::launch_stage_t4(plain, {.table_in = e->t4.table[stage - 1].p,
+                                                  .counts_in = e->t4.counts_of(stage, e->t4.parity),
+                                                  .counts_zero = e->t4.counts_of(stage, e->t4.parity ^ 1u),
+                                                  .desc_in = d_in, .desc_out = d_out, .emit = emit, .interleave = e->pg.rows.interleave, .solo = solo}));
         if (solo) return GNNVC_OK;
         // ... and the gathering kernel, which leaves at once when the table tiles did the rows (d_out[8]: decided on the device)
-        return hip_rc(e, gnnvc::launch_stage(call, {.long_thresh = c.long_thresh, .mfma = c.mfma, .interleave = e->interleave,
+        return hip_rc(e, gnnvc::launch_stage(call, {.long_thresh = c.long_thresh, .mfma = c.mfma, .interleave = e->pg.rows.interleave,
                                                     .skip_flag = d_out + 8}));
     }
     if (c.sums == StageChoice::kLdsTable || c.sums == StageChoice::kBlocked) {
@@ -508,37 +508,37 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         if (rc) return rc;
     }
     if (c.sums == StageChoice::kLdsTable) {   // (the sums share the blocked plan's buffer)
-        ++e->plan_memsets;   // (the flag "this input does not match the table": cleared by a memset ahead of k_lt_bytes_x)
-        return hip_rc(e, gnnvc::launch_stage0_lds_table(plain, lds_table_plan(e), e->lt_bytes.p, e->blk_acc.p, e->lt_bad.p,
+        ++e->pg.plan_memsets;   // (the flag "this input does not match the table": cleared by a memset ahead of k_lt_bytes_x)
+        return hip_rc(e, gnnvc::launch_stage0_lds_table(plain, lds_table_plan(e), e->lt.bytes.p, e->blk.acc.p, e->lt.bad.p,
                                                         {.long_thresh = c.long_thresh, .mfma = e->opt.mfma == 1,
-                                                         .interleave = e->interleave, .emit = emit}));
+                                                         .interleave = e->pg.rows.interleave, .emit = emit}));
     }
     if (c.sums == StageChoice::kBlocked)
         return hip_rc(e, gnnvc::launch_stage0_blocked(plain,
-                                                      {.nblocks = e->blk_count, .bp = e->blk_ptr.p, .colb = e->blk_col.p, .acc = e->blk_acc.p},
-                                                      {.long_thresh = e->long_thresh, .mfma = e->opt.mfma == 1,
-                                                       .interleave = e->interleave, .emit = emit}));
+                                                      {.nblocks = e->pg.blk.count, .bp = e->blk.ptr.p, .colb = e->blk.col.p, .acc = e->blk.acc.p},
+                                                      {.long_thresh = e->pg.rows.long_thresh, .mfma = e->opt.mfma == 1,
+                                                       .interleave = e->pg.rows.interleave, .emit = emit}));
     gnnvc::CompactSums sums;   // (all null: the compact-table plan is not in this call)
     uint32_t *desc = nullptr;
     if (c.sums == StageChoice::kCompactPrepared || c.sums == StageChoice::kCompactWhole) {
-        desc = e->c4_desc.p + gnnvc_engine::kDescWords * (stage - 1);
-        e->c4_last_desc = gnnvc_engine::kDescWords * (stage - 1);
-        if (c.sums == StageChoice::kCompactWhole) e->pg.fit_used[stage] = true;
-        sums = {.acc4 = e->c4_acc.p, .c4desc = desc, .agg16 = e->c4_agg16.p, .table_in = (call.skip & 1u) ? e->c4_table.p : nullptr};   // (without the table: route C, the full chain)
+        desc = e->c4.desc.p + gnnvc_engine::kDescWords * (stage - 1);
+        e->pg.c4.last_desc = gnnvc_engine::kDescWords * (stage - 1);
+        if (c.sums == StageChoice::kCompactWhole) e->pg.c4.fit_used[stage] = true;
+        sums = {.acc4 = e->c4.acc.p, .c4desc = desc, .agg16 = e->c4.agg16.p, .table_in = (call.skip & 1u) ? e->c4.table.p : nullptr};   // (without the table: route C, the full chain)
         const bool whole = c.sums == StageChoice::kCompactWhole;
-        if (whole && !c.fused_counts) HIP_TRY(e, gnnvc::column_counts(in, e->g.n, e->c4_counts.p, e->stream));
+        if (whole && !c.fused_counts) HIP_TRY(e, gnnvc::column_counts(in, e->g.n, e->c4.counts.p, e->stream));
         const bool fused = whole && c.fused_counts;
         // what: 1 = choose the columns + write the table, 2 = the sums; the prepared table only needs its sums, a call
         // that runs its sums round by round (below) only the preparation
         const int what = !whole ? 2 : (c.rounds ? 1 : 3);
         // (its k_c4_choose clears what this stage counts into: desc[5], the rounds' counters, and the producer's counters
         // where it is the one that reads them)
-        if (fused) e->c4_emit_zero = false;
-        if (!(what & 1)) ++e->plan_memsets;   // (no k_c4_choose in this call: launch_compact_gather clears desc[5] with a memset)
-        HIP_TRY(e, gnnvc::launch_compact_gather(e->g, compact_plan(e), in, fused ? e->c4_emit_counts.p : e->c4_counts.p, fused ? 64 : 1,
-                                                desc, e->c4_table.p, e->c4_acc.p, lo, hi, e->c4_dirty.p, e->c4_dirty_cap,
-                                                e->c4_agg16.p, e->stream, what, c.rounds ? e->c4_round_counts.p : nullptr, 256u * e->c4_rows, fused));
-        if (fused) e->c4_emit_zero = true;
+        if (fused) e->call.c4_emit_zero = false;
+        if (!(what & 1)) ++e->pg.plan_memsets;   // (no k_c4_choose in this call: launch_compact_gather clears desc[5] with a memset)
+        HIP_TRY(e, gnnvc::launch_compact_gather(e->g, compact_plan(e), in, fused ? e->c4.emit_counts.p : e->c4.counts.p, fused ? 64 : 1,
+                                                desc, e->c4.table.p, e->c4.acc.p, lo, hi, e->c4.dirty.p, e->pg.c4.dirty_cap,
+                                                e->c4.agg16.p, e->stream, what, c.rounds ? e->c4.round_counts.p : nullptr, 256u * e->pg.c4.rows, fused));
+        if (fused) e->call.c4_emit_zero = true;
     }
     if (c.sums != StageChoice::kLdsTable && c.sums != StageChoice::kBlocked) {
         int rc = pilot();
@@ -549,18 +549,18 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     const gnnvc::SortedOrder *sop = c.sorted.n ? &c.sorted : nullptr;
     // Wide tiles (k_stage_w*): a graph with fewer tiles than the chip has SIMDs — the reference CLI's later predict calls — and
     // nothing but the plain gather to run (no plan, no long rows, no pruned adjacency, nothing to emit): a workgroup per tile
-    if (c.sums == StageChoice::kGather && e->opt.wide && e->g.n <= (sp.f == 16 ? e->opt.wide_max_n16 : e->opt.wide_max_n) && !e->g.sliced() && e->n_long == 0 && !sop &&
+    if (c.sums == StageChoice::kGather && e->opt.wide && e->g.n <= (sp.f == 16 ? e->opt.wide_max_n16 : e->opt.wide_max_n) && !e->g.sliced() && e->pg.rows.n_long == 0 && !sop &&
         !sums.acc4 && !emit.counts && gv.prune_bad == nullptr && gv.zero_bits == nullptr && sp.variant >= 0 && sp.variant <= 2) {
         e->pg.wide_used = true;
-        e->stage_wide = true;
+        e->call.stage_wide = true;
         return hip_rc(e, gnnvc::launch_stage_wide(plain));
     }
-    HIP_TRY(e, gnnvc::launch_stage(call, {.long_thresh = c.long_thresh, .mfma = c.mfma, .so = sop, .interleave = e->interleave,
+    HIP_TRY(e, gnnvc::launch_stage(call, {.long_thresh = c.long_thresh, .mfma = c.mfma, .so = sop, .interleave = e->pg.rows.interleave,
                                           .sums = sums, .mfma_agg = e->opt.mfma == 1, .emit = emit, .dense_part = !c.rounds,
                                           .so_pruned = so_p.vertex ? &so_p : nullptr}));
     if (!c.rounds) return GNNVC_OK;
     // (desc[5] is zero and each round's counter at the round's first slot: k_c4_choose, what = 1 above)
-    const uint32_t rows = e->c4_rows, c0 = (lo - e->c4_base) / rows, c1 = (hi - 1 - e->c4_base) / rows;
+    const uint32_t rows = e->pg.c4.rows, c0 = (lo - e->pg.c4.base) / rows, c1 = (hi - 1 - e->pg.c4.base) / rows;
     const uint32_t nrounds = (c1 - c0) / 256u + 1u;
     if (nrounds > gnnvc::compact_rounds()) return fail(e, GNNVC_ERR_UNSUPPORTED, "too many rounds of the compact-table plan");
     {
@@ -569,13 +569,13 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
     }
     for (uint32_t k = 0; k < nrounds; ++k) {
         const uint32_t ca = c0 + 256u * k, cb = std::min(c1 + 1u, ca + 256u);
-        const uint32_t ra = std::max(lo, e->c4_base + ca * rows);
-        const uint32_t rb = (uint32_t)std::min<uint64_t>(hi, (uint64_t)e->c4_base + (uint64_t)cb * rows);
+        const uint32_t ra = std::max(lo, e->pg.c4.base + ca * rows);
+        const uint32_t rb = (uint32_t)std::min<uint64_t>(hi, (uint64_t)e->pg.c4.base + (uint64_t)cb * rows);
         // round k hands out its dirty-row slots from word k, which starts at its first chunk's row offset within the call:
         // rows are done by whole chunks, so the round's dirty rows fit below the next round's first slot, and below c4_dirty_cap
-        uint32_t *const count = e->c4_round_counts.p + k;
+        uint32_t *const count = e->c4.round_counts.p + k;
         const uint32_t slot_base = 256u * k * rows;
-        HIP_TRY(e, gnnvc::compact_sums(e->g, compact_plan(e), desc, e->c4_table.p, e->c4_acc.p, ra, rb, e->c4_dirty.p, e->c4_dirty_cap,
+        HIP_TRY(e, gnnvc::compact_sums(e->g, compact_plan(e), desc, e->c4.table.p, e->c4.acc.p, ra, rb, e->c4.dirty.p, e->pg.c4.dirty_cap,
                                        e->stream, count));
         const bool last = k + 1 == nrounds;
         hipStream_t ds = last ? e->stream : e->aux_stream;
@@ -583,7 +583,7 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
             HIP_TRY(e, hipEventRecord(e->round_ev[k], e->stream));
             HIP_TRY(e, hipStreamWaitEvent(e->aux_stream, e->round_ev[k], 0));
         }
-        HIP_TRY(e, gnnvc::compact_fix(e->g, in, desc, e->c4_dirty.p, e->c4_dirty_cap, e->c4_agg16.p, count, slot_base, ds,
+        HIP_TRY(e, gnnvc::compact_fix(e->g, in, desc, e->c4.dirty.p, e->pg.c4.dirty_cap, e->c4.agg16.p, count, slot_base, ds,
                                       /*blocks=*/64));
         gnnvc::StageCall round = plain;
         round.row_lo = ra;
@@ -603,26 +603,26 @@ std::string describe_stage(const gnnvc_engine *e, const StageChoice &c, const Gr
     static const char *const kSums[] = {"gather", "lds_table", "blocked", "compact_prepared", "compact_whole", "table_tiles"};
     char buf[320];
     int at = snprintf(buf, sizeof buf, "sums=%s%s mfma=%d sorted_tiles=%d rounds=%d emit=%d pruned=%d filtered=%d short_lists=%d",
-                      kSums[c.sums], e->stage_wide ? " (wide tiles)" : "", c.mfma ? 1 : 0, c.sorted.n ? 1 : 0, c.rounds ? 1 : 0,
+                      kSums[c.sums], e->call.stage_wide ? " (wide tiles)" : "", c.mfma ? 1 : 0, c.sorted.n ? 1 : 0, c.rounds ? 1 : 0,
                       (c.emit || c.emit_t4) ? 1 : 0, gv.prune_bad ? 1 : 0, gv.zero_bits ? 1 : 0, gv.short_col ? 1 : 0);
-    if (e->n_long > 0 && at > 0 && at < (int)sizeof buf) {
+    if (e->pg.rows.n_long > 0 && at > 0 && at < (int)sizeof buf) {
         // (launch_side_rows: side_join 0 = everything on the main queue, 1 = long and giant rows on the side queue, 2 = long rows
         // on the main queue, giant rows on a queue of their own)
-        const char *lq = e->side_join == 1 ? "side" : "main";
-        const char *gq = e->side_join == 0 ? "main" : (e->side_join == 1 ? "side" : "giant");
-        at += snprintf(buf + at, sizeof buf - at, " long_rows=%u (from degree %u, %s queue)", e->n_long, c.long_thresh, lq);
-        if (e->n_giant && at < (int)sizeof buf) snprintf(buf + at, sizeof buf - at, " giant_rows=%u (%s queue)", e->n_giant, gq);
+        const char *lq = e->call.side_join == 1 ? "side" : "main";
+        const char *gq = e->call.side_join == 0 ? "main" : (e->call.side_join == 1 ? "side" : "giant");
+        at += snprintf(buf + at, sizeof buf - at, " long_rows=%u (from degree %u, %s queue)", e->pg.rows.n_long, c.long_thresh, lq);
+        if (e->pg.rows.n_giant && at < (int)sizeof buf) snprintf(buf + at, sizeof buf - at, " giant_rows=%u (%s queue)", e->pg.rows.n_giant, gq);
     }
     return buf;
 }
 
 int run_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float *in, float *out, float *logits,
               bool in_forward = false, std::string *plan = nullptr) {
-    e->stage_wide = false;
+    e->call.stage_wide = false;
     StageChoice c;
     int rc = choose_stage(e, stage, lo, hi, in, out, in_forward, c);
     if (rc) return rc;
-    const bool longs = e->n_long > 0;
+    const bool longs = e->pg.rows.n_long > 0;
     GraphDev gv;   // (the check behind a pruned adjacency is queued before the fork to the side streams)
     gnnvc::SortedOrder so_p;
     rc = gather_view(e, stage, lo, hi, in, c.sums == StageChoice::kGather, c.sorted.n != 0, gv, so_p, c.mfma, c.long_thresh);
@@ -635,9 +635,9 @@ int run_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float 
     }
     rc = launch_main(e, c, call, so_p, stage);
     if (rc) return rc;
-    if (longs && e->side_join) {   // join: the side queue's last kernel of this stage
-        if (e->side_join == 1) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_long, 0));
-        else if (e->n_giant) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_giant, 0));
+    if (longs && e->call.side_join) {   // join: the side queue's last kernel of this stage
+        if (e->call.side_join == 1) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_long, 0));
+        else if (e->pg.rows.n_giant) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->ev_giant, 0));
     }
     // (every writer of out / logits is now ordered before whatever follows on e->stream: the side queues through the join above,
     // the rounds' dense kernels on the aux stream through launch_main's wait on ev_join)
@@ -658,7 +658,7 @@ bool audit_tick(gnnvc_engine *e) {
 int audit_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const float *in, float *out, float *logits, std::string &plan,
                 bool hook = true) {
     const std::vector<StagePlan> &st = e->stage_list();
-    const size_t slot = e->audit_pending.size();
+    const size_t slot = e->call.audit_pending.size();
     if (slot == 0) {   // the call's first check: its records
         HIP_TRY(e, e->audit_rec.reserve(std::max<size_t>(st.size(), 1) * gnnvc::kAuditWords));
         HIP_TRY(e, hipMemsetAsync(e->audit_rec.p, 0, e->audit_rec.cap * sizeof(unsigned long long), e->stream));
@@ -671,16 +671,16 @@ int audit_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const floa
     unsigned long long *rec = e->audit_rec.p + slot * gnnvc::kAuditWords;
     if (e->generic_on()) HIP_TRY(e, gnnvc::launch_audit_any(call, rec, /*repair=*/e->opt.audit_repair != 0));
     else HIP_TRY(e, gnnvc::launch_audit_stage(call, rec, /*repair=*/e->opt.audit_repair != 0));
-    e->audit_pending.push_back(gnnvc_engine::AuditCheck{stage, lo, hi, std::move(plan)});
+    e->call.audit_pending.push_back(gnnvc_engine::AuditCheck{stage, lo, hi, std::move(plan)});
     return GNNVC_OK;
 }
 
 // end of an audited call: one read-back of the records, one stream synchronisation, the verdict
 int audit_finish(gnnvc_engine *e, int rc) {
-    if (!e->audit_now) return rc;
-    e->audit_now = false;
+    if (!e->call.audit_now) return rc;
+    e->call.audit_now = false;
     std::vector<gnnvc_engine::AuditCheck> checks;
-    checks.swap(e->audit_pending);
+    checks.swap(e->call.audit_pending);
     if (rc != GNNVC_OK || checks.empty()) return rc;
     const size_t words = checks.size() * gnnvc::kAuditWords;
     HIP_TRY(e, e->audit_pin.reserve(std::max(e->stage_list().size(), checks.size()) * gnnvc::kAuditWords));
@@ -783,38 +783,38 @@ int run_generic_stage(gnnvc_engine *e, const StagePlan &sp, const float *in, flo
         HIP_TRY(e, gnnvc::launch_any_live(call, e->live_percent));
     }
     const gnnvc_engine::PerGraph &pg = e->pg;
-    e->heavy_last_rows = pg.heavy_rows;
-    e->ggiant_last_rows = pg.heavy_rows ? pg.giant_rows : 0;
-    e->ggiant_last_segmented = e->ggiant_last_rows && pg.giant_maxseg > 1;
-    if (!pg.heavy_rows) {
+    e->call.heavy_last_rows = pg.heavy.rows;
+    e->call.ggiant_last_rows = pg.heavy.rows ? pg.ggiant.rows : 0;
+    e->call.ggiant_last_segmented = e->call.ggiant_last_rows && pg.ggiant.maxseg > 1;
+    if (!pg.heavy.rows) {
         HIP_TRY(e, gnnvc::launch_stage_any(call));
         return GNNVC_OK;
     }
-    const gnnvc::AnyHeavyRows hr{.list = e->heavy_list.p, .n = pg.heavy_rows, .from = pg.heavy_thresh, .hsum = e->heavy_sum.p,
-                                 .below = pg.giant_rows ? pg.giant_min : 0xFFFFFFFFu};
+    const gnnvc::AnyHeavyRows hr{.list = e->heavy_list.p, .n = pg.heavy.rows, .from = pg.heavy.thresh, .hsum = e->heavy_sum.p,
+                                 .below = pg.ggiant.rows ? pg.ggiant.min : 0xFFFFFFFFu};
     const bool side = heavy_overlap() && e->aux_stream;
     gnnvc::StageCall sums = call;
     gnnvc::AnyGiantRows ar;
-    if (pg.giant_rows) {
-        ar.gr.n = pg.giant_rows;
-        ar.gr.blocks = pg.giant_blocks;
+    if (pg.ggiant.rows) {
+        ar.gr.n = pg.ggiant.rows;
+        ar.gr.blocks = pg.ggiant.blocks;
         ar.gr.meta = e->ag_meta.p;
         ar.gr.off = e->ag_off.p;
         ar.gr.slab = e->ag_slab.p;
         ar.gr.agg = e->ag_agg.p;
-        ar.gr.segsum = pg.giant_maxseg > 1 ? e->ag_segsum.p : nullptr;
-        ar.gr.segmap = pg.giant_maxseg > 1 ? e->ag_segmap.p : nullptr;
-        ar.gr.maxseg = pg.giant_maxseg;
+        ar.gr.segsum = pg.ggiant.maxseg > 1 ? e->ag_segsum.p : nullptr;
+        ar.gr.segmap = pg.ggiant.maxseg > 1 ? e->ag_segmap.p : nullptr;
+        ar.gr.maxseg = pg.ggiant.maxseg;
         ar.pos = e->ag_pos.p;
     }
-    const bool gather_first = side && pg.giant_rows && giant_gather_first();   // (the gather on the main stream, ahead of the fork)
+    const bool gather_first = side && pg.ggiant.rows && giant_gather_first();   // (the gather on the main stream, ahead of the fork)
     if (gather_first) HIP_TRY(e, gnnvc::launch_any_giant(call, ar, hr.hsum, gnnvc::AnyGiantPart::kGather));
     if (side) {
         HIP_TRY(e, hipEventRecord(e->ev_fork, e->stream));
         HIP_TRY(e, hipStreamWaitEvent(e->aux_stream, e->ev_fork, 0));
         sums.stream = e->aux_stream;
     }
-    if (pg.giant_rows) {
+    if (pg.ggiant.rows) {
         if (!gather_first) HIP_TRY(e, gnnvc::launch_any_giant(sums, ar, hr.hsum, gnnvc::AnyGiantPart::kGather));
         HIP_TRY(e, gnnvc::launch_giant_sums(ar.gr, (uint32_t)sp.f, lo, hi, sums.stream));
         HIP_TRY(e, gnnvc::launch_any_giant(sums, ar, hr.hsum, gnnvc::AnyGiantPart::kPlace));
@@ -860,11 +860,11 @@ int forward_generic(gnnvc_engine *e, const float *d_x, float *d_out, float *d_lo
             if (rc != GNNVC_OK) return rc;
             e->live_seen[s] = live ? 1 : 0;
         }
-        if (e->audit_now) {   // (gnnvc_forward_audited* only: "audit_period" never sets it for a generic-stage model)
+        if (e->call.audit_now) {   // (gnnvc_forward_audited* only: "audit_period" never sets it for a generic-stage model)
             std::string plan = st[s].dense ? "k_stage_any (dense rows)"
-                               : e->heavy_last_rows ? "k_stage_any (light rows, listed rows) + k_any_heavy_sums" : "k_stage_any";
-            if (!st[s].dense && e->ggiant_last_rows)
-                plan += e->ggiant_last_segmented ? " + k_any_giant_gather, k_giant_segsum, k_giant_segmap, k_giant_sum, k_any_giant_place"
+                               : e->call.heavy_last_rows ? "k_stage_any (light rows, listed rows) + k_any_heavy_sums" : "k_stage_any";
+            if (!st[s].dense && e->call.ggiant_last_rows)
+                plan += e->call.ggiant_last_segmented ? " + k_any_giant_gather, k_giant_segsum, k_giant_segmap, k_giant_sum, k_any_giant_place"
                                                  : " + k_any_giant_gather, k_giant_sum, k_any_giant_place";
             if (e->live_seen[s]) plan += " + k_any_live_mask, k_any_live_pack (the live-column table, where the device chose it)";
             const int rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan);
@@ -1018,11 +1018,11 @@ int gnnvc_set_option(gnnvc_engine *e, const char *key, long value) {
     }
     uint32_t fx = 0;   // (the keys, their clamps and their effects: gnnvc_options.h)
     if (!gnnvc::apply_option(e->opt, key, value, &fx)) return fail(e, GNNVC_ERR_INVALID, "unknown option '%s'", key);
-    if (fx & gnnvc::kFxShortLists) e->pg.short_from = 0;
+    if (fx & gnnvc::kFxShortLists) e->pg.filter.short_from = 0;
     if (fx & gnnvc::kFxForgetPruned)
-        for (auto &pp : e->prune) pp.forget();
+        for (auto &pp : e->pg.prune) pp = {};
     if (fx & gnnvc::kFxSortedStale)
-        for (auto &r : e->srt) r.valid = false;
+        for (auto &r : e->pg.sorted) r.valid = false;
     if (fx & gnnvc::kFxAuditRestart) e->audit_calls = 0;
     return (fx & gnnvc::kFxForward) && e->multi ? gnnvc::multi_set_option(e->multi, key, value) : GNNVC_OK;
 }
@@ -1068,7 +1068,7 @@ static int set_big_stages(gnnvc_engine *e, uint32_t lds_bytes) {
     }
     e->big_lds = lds_bytes;
     plan_generic(e);                // (at once, as option "generic_stages": the stage list and everything the ABI reports of it)
-    e->pg.heavy_known = false;      // an attached graph is classed again by the next generic stage that runs (class_heavy_rows)
+    e->pg.heavy.known = false;      // an attached graph is classed again by the next generic stage that runs (class_heavy_rows)
     return GNNVC_OK;
 }
 
@@ -1093,7 +1093,7 @@ static int set_feature_width(gnnvc_engine *e, uint32_t max_width) {
     }
     e->feat_width = max_width;
     plan_generic(e);                // (at once, as gnnvc_set_generic_big_stages)
-    e->pg.heavy_known = false;      // an attached graph is classed again by the next generic stage that runs (class_heavy_rows): hsum and the giant slab follow the widest f
+    e->pg.heavy.known = false;      // an attached graph is classed again by the next generic stage that runs (class_heavy_rows): hsum and the giant slab follow the widest f
     return GNNVC_OK;
 }
 
@@ -1110,7 +1110,7 @@ static int set_patterns(gnnvc_engine *e, uint32_t mask) {
     if (mask == e->patterns) return GNNVC_OK;
     e->patterns = mask;             // (no LDS limit to raise: a dense stage outside the default bounds needs the big or feat call, which raise theirs)
     plan_generic(e);                // (at once, as gnnvc_set_generic_big_stages)
-    e->pg.heavy_known = false;      // an attached graph is classed again by the next generic graph stage that runs (class_heavy_rows)
+    e->pg.heavy.known = false;      // an attached graph is classed again by the next generic graph stage that runs (class_heavy_rows)
     return GNNVC_OK;
 }
 
@@ -1227,15 +1227,15 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     else if (k == "generic_stages_active") *value = e->generic_ran ? 1 : 0;   // did the last one
     else if (k == "generic_max_dense_layers") *value = gnnvc::kMaxDenseLayers;
     else if (k == "generic_heavy_from") *value = (long)e->heavy_from;                 // gnnvc_set_generic_heavy_rows
-    else if (k == "generic_heavy_rows") *value = (long)e->pg.heavy_rows;              // the attached graph's last classing
-    else if (k == "generic_heavy_entries") *value = (long)e->pg.heavy_entries;
-    else if (k == "generic_heavy_last_rows") *value = (long)e->heavy_last_rows;       // 0: the last call launched one kernel a stage
+    else if (k == "generic_heavy_rows") *value = (long)e->pg.heavy.rows;              // the attached graph's last classing
+    else if (k == "generic_heavy_entries") *value = (long)e->pg.heavy.entries;
+    else if (k == "generic_heavy_last_rows") *value = (long)e->call.heavy_last_rows;       // 0: the last call launched one kernel a stage
     else if (k == "generic_giant_from") *value = (long)e->ggiant_from;                // gnnvc_set_generic_giant_rows
     else if (k == "generic_giant_segments") *value = (long)e->ggiant_segments;        // as stored: -1 | 0 | 1 (or whatever was passed)
-    else if (k == "generic_giant_rows") *value = (long)e->pg.giant_rows;              // the attached graph's last classing
-    else if (k == "generic_giant_entries") *value = (long)e->pg.giant_entries;
-    else if (k == "generic_giant_last_rows") *value = (long)e->ggiant_last_rows;
-    else if (k == "generic_giant_last_segmented") *value = e->ggiant_last_segmented ? 1 : 0;
+    else if (k == "generic_giant_rows") *value = (long)e->pg.ggiant.rows;              // the attached graph's last classing
+    else if (k == "generic_giant_entries") *value = (long)e->pg.ggiant.entries;
+    else if (k == "generic_giant_last_rows") *value = (long)e->call.ggiant_last_rows;
+    else if (k == "generic_giant_last_segmented") *value = e->call.ggiant_last_segmented ? 1 : 0;
     else if (k.rfind("generic_stage_layers_", 0) == 0) {   // "generic_stage_layers_<s>": dense layers of stage s of a generic model
         const long s = generic_stage_index(e, k, sizeof("generic_stage_layers_") - 1);
         if (s < 0) return GNNVC_ERR_INVALID;
@@ -1292,21 +1292,21 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
         *value = 0;
         for (size_t s = 0; s < e->stages.size() && s < 10; ++s) *value |= (long)(e->stages[s].skip_ok & 7u) << (3 * s);
     }
-    else if (k == "compact_gather_active") *value = e->pg.c4_ready ? 1 : 0;
-    else if (k == "compact_gather_chunks") *value = e->pg.c4_ready ? (long)e->c4_chunks : 0;
-    else if (k == "compact_gather_block_cols") *value = e->pg.c4_ready ? (long)e->c4_block : 0;
-    else if (k == "compact_gather_rows_per_chunk") *value = e->pg.c4_ready ? (long)e->c4_rows : 0;
-    else if (k == "compact_gather_steps") *value = e->pg.c4_ready ? (long)e->c4_steps_total : 0;
-    else if (k == "pruned_stage1" || k == "pruned_stage2") *value = e->prune[k.back() - '0'].ready ? 1 : 0;
+    else if (k == "compact_gather_active") *value = e->pg.c4.ready ? 1 : 0;
+    else if (k == "compact_gather_chunks") *value = e->pg.c4.ready ? (long)e->pg.c4.chunks : 0;
+    else if (k == "compact_gather_block_cols") *value = e->pg.c4.ready ? (long)e->pg.c4.block : 0;
+    else if (k == "compact_gather_rows_per_chunk") *value = e->pg.c4.ready ? (long)e->pg.c4.rows : 0;
+    else if (k == "compact_gather_steps") *value = e->pg.c4.ready ? (long)e->pg.c4.steps_total : 0;
+    else if (k == "pruned_stage1" || k == "pruned_stage2") *value = e->pg.prune[k.back() - '0'].ready ? 1 : 0;
     else if (k == "side_queue_probes") *value = e->side_probes;
     else if (k == "side_queue_runs_beside") *value = e->side_beside ? 1 : 0;
-    else if (k == "long_entries_percent") *value = e->n_long && e->g.nnz ? (long)(e->long_entries * 100ull / e->g.nnz) : 0;
-    else if (k == "filtered_stage1" || k == "filtered_stage2") *value = e->filtered[k.back() - '0'] ? 1 : 0;
-    else if (k == "short_lists_stage1" || k == "short_lists_stage2") *value = e->short_used[k.back() - '0'] ? 1 : 0;
+    else if (k == "long_entries_percent") *value = e->pg.rows.n_long && e->g.nnz ? (long)(e->pg.rows.long_entries * 100ull / e->g.nnz) : 0;
+    else if (k == "filtered_stage1" || k == "filtered_stage2") *value = e->pg.filter.filtered[k.back() - '0'] ? 1 : 0;
+    else if (k == "short_lists_stage1" || k == "short_lists_stage2") *value = e->pg.filter.short_used[k.back() - '0'] ? 1 : 0;
     else if (k == "filter_mass_percent_stage1" || k == "filter_mass_percent_stage2") {   // (diagnostic: reads the device's counters back)
         const int st = k.back() - '0';
         *value = -1;
-        if (e->filtered[st] && e->filter_info.p && e->g.nnz) {
+        if (e->pg.filter.filtered[st] && e->filter_info.p && e->g.nnz) {
             unsigned long long info[2] = {0, 0};
             if (hipStreamSynchronize(e->stream) != hipSuccess ||
                 hipMemcpy(info, e->filter_info.p + 4 * st, sizeof info, hipMemcpyDeviceToHost) != hipSuccess)
@@ -1314,16 +1314,16 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
             *value = (long)(info[0] * 100ull / e->g.nnz);
         }
     }
-    else if (k == "pruned_vertices_stage1" || k == "pruned_vertices_stage2") *value = e->prune[k.back() - '0'].ready ? (long)e->prune[k.back() - '0'].members : 0;
-    else if (k == "pruned_entries_stage1" || k == "pruned_entries_stage2") *value = e->prune[k.back() - '0'].ready ? (long)e->prune[k.back() - '0'].kept : 0;
-    else if (k == "pruned_predicted_stage1") *value = e->prune[1].ready && e->prune[1].predicted ? 1 : 0;
-    else if (k == "pruned_borrowed_stage2") *value = e->borrowed[2] ? 1 : 0;
-    else if (k == "pruned_from_previous_stage2") *value = e->prune[2].ready && e->prune[2].from_prev ? 1 : 0;
+    else if (k == "pruned_vertices_stage1" || k == "pruned_vertices_stage2") *value = e->pg.prune[k.back() - '0'].ready ? (long)e->pg.prune[k.back() - '0'].members : 0;
+    else if (k == "pruned_entries_stage1" || k == "pruned_entries_stage2") *value = e->pg.prune[k.back() - '0'].ready ? (long)e->pg.prune[k.back() - '0'].kept : 0;
+    else if (k == "pruned_predicted_stage1") *value = e->pg.prune[1].ready && e->pg.prune[1].predicted ? 1 : 0;
+    else if (k == "pruned_borrowed_stage2") *value = e->pg.filter.borrowed[2] ? 1 : 0;
+    else if (k == "pruned_from_previous_stage2") *value = e->pg.prune[2].ready && e->pg.prune[2].from_prev ? 1 : 0;
     else if (k == "pruned_last_ok_stage1" || k == "pruned_last_ok_stage2") {
         // did the last call of that stage use its pruned adjacency?  (waits for the stream; tests and tools)
         const int st = k.back() - '0';
         *value = 0;
-        if (e->prune[st].ready || e->borrowed[st]) {
+        if (e->pg.prune[st].ready || e->pg.filter.borrowed[st]) {
             uint32_t bad = 1;
             if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
                 hipMemcpy(&bad, e->prune_flags.p + st, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess)
@@ -1332,70 +1332,70 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
         }
     }
     else if (k == "wide_tiles_used") *value = e->pg.wide_used ? 1 : 0;   // (did any stage since the graph was handed over run on wide tiles)
-    else if (k == "table_tiles_active") *value = e->t4_ok ? 1 : 0;
+    else if (k == "table_tiles_active") *value = e->pg.t4.ok ? 1 : 0;
     else if (k == "table_tiles_fit_stage1" || k == "table_tiles_fit_stage2") {   // did the last forward's stage run on the table?  (waits for the stream)
         *value = 0;
-        if (e->t4_ok && e->t4_desc.p) {
+        if (e->pg.t4.ok && e->t4.desc.p) {
             uint32_t fit = 0;
             gnnvc_engine *m = const_cast<gnnvc_engine *>(e);
             if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
-                hipMemcpy(&fit, m->t4_desc_of(k.back() - '0', e->t4_parity) + 8, sizeof fit, hipMemcpyDeviceToHost) != hipSuccess)
+                hipMemcpy(&fit, m->t4.desc_of(k.back() - '0', e->t4.parity) + 8, sizeof fit, hipMemcpyDeviceToHost) != hipSuccess)
                 return GNNVC_ERR_DEVICE;
             *value = (long)fit;
         }
     }
-    else if (k == "lds_table_off") *value = e->pg.lt_off ? 1 : 0;
-    else if (k == "lds_table_bits") *value = e->pg.lt_ready ? (long)e->lt_bits : 0;
-    else if (k == "compact_gather_off_stage1" || k == "compact_gather_off_stage2") *value = e->pg.c4_stage_off[k.back() - '0'] ? 1 : 0;
-    else if (k == "compact_gather_blocks") *value = e->pg.c4_ready ? (long)e->c4_nblocks : 0;
+    else if (k == "lds_table_off") *value = e->pg.lt.off ? 1 : 0;
+    else if (k == "lds_table_bits") *value = e->pg.lt.ready ? (long)e->pg.lt.bits : 0;
+    else if (k == "compact_gather_off_stage1" || k == "compact_gather_off_stage2") *value = e->pg.c4.stage_off[k.back() - '0'] ? 1 : 0;
+    else if (k == "compact_gather_blocks") *value = e->pg.c4.ready ? (long)e->pg.c4.nblocks : 0;
     else if (k == "compact_gather_last_ok" || k == "compact_gather_last_dirty" || k == "compact_gather_last_passes" ||
              k == "compact_table_written_by_producer") {
         // what the device decided at the last launch of the plan (waits for the stream; for tests and tools)
         *value = 0;
-        if (e->pg.c4_ready && e->c4_desc.p) {
+        if (e->pg.c4.ready && e->c4.desc.p) {
             uint32_t d[8] = {0};
             if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
-                hipMemcpy(d, e->c4_desc.p + e->c4_last_desc, sizeof d, hipMemcpyDeviceToHost) != hipSuccess)
+                hipMemcpy(d, e->c4.desc.p + e->pg.c4.last_desc, sizeof d, hipMemcpyDeviceToHost) != hipSuccess)
                 return GNNVC_ERR_DEVICE;
             if (k == "compact_table_written_by_producer") *value = (d[0] && !d[6]) ? 1 : 0;   // (no compaction pass was needed)
             else *value = k == "compact_gather_last_ok" ? (d[0] ? 1 : 0) : (k == "compact_gather_last_passes" ? (long)d[0] : (long)d[5]);
         }
     }
-    else if (k == "plan_memsets_last_forward") *value = (long)e->plan_memsets;
-    else if (k == "lds_table_active") *value = e->pg.lt_ready ? 1 : 0;
+    else if (k == "plan_memsets_last_forward") *value = (long)e->pg.plan_memsets;
+    else if (k == "lds_table_active") *value = e->pg.lt.ready ? 1 : 0;
     else if (k == "lds_table_last_ok") {   // did the last forward's input fit the table?  (waits for the stream; tests and tools)
         *value = 0;
-        if (e->pg.lt_ready && e->lt_bad.p) {
+        if (e->pg.lt.ready && e->lt.bad.p) {
             uint32_t bad = 1;
             if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
-                hipMemcpy(&bad, e->lt_bad.p, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess)
+                hipMemcpy(&bad, e->lt.bad.p, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess)
                 return GNNVC_ERR_DEVICE;
             *value = bad == 0 ? 1 : 0;
         }
     }
-    else if (k == "lds_table_mapped") *value = e->pg.lt_ready && e->lt_mapped ? 1 : 0;
-    else if (k == "lds_table_blocks") *value = e->pg.lt_ready ? (long)e->lt_blocks : 0;
-    else if (k == "lds_table_chunks") *value = e->pg.lt_ready ? (long)e->lt_chunks : 0;
-    else if (k == "lds_table_steps") *value = e->pg.lt_ready ? (long)e->lt_steps_total : 0;
-    else if (k == "blocked_stage0_active") *value = e->pg.blocked_ready ? 1 : 0;
-    else if (k == "blocked_blocks") *value = e->pg.blocked_ready ? (long)e->blk_count : 0;
-    else if (k == "block_cols") *value = e->pg.blocked_ready ? (long)e->blk_cols : 0;
-    else if (k == "long_rows") *value = (long)e->n_long;
+    else if (k == "lds_table_mapped") *value = e->pg.lt.ready && e->pg.lt.mapped ? 1 : 0;
+    else if (k == "lds_table_blocks") *value = e->pg.lt.ready ? (long)e->pg.lt.blocks : 0;
+    else if (k == "lds_table_chunks") *value = e->pg.lt.ready ? (long)e->pg.lt.chunks : 0;
+    else if (k == "lds_table_steps") *value = e->pg.lt.ready ? (long)e->pg.lt.steps_total : 0;
+    else if (k == "blocked_stage0_active") *value = e->pg.blk.ready ? 1 : 0;
+    else if (k == "blocked_blocks") *value = e->pg.blk.ready ? (long)e->pg.blk.count : 0;
+    else if (k == "block_cols") *value = e->pg.blk.ready ? (long)e->pg.blk.cols : 0;
+    else if (k == "long_rows") *value = (long)e->pg.rows.n_long;
     else if (k == "plan_build_us") *value = (long)(e->pg.plan_build_ms * 1000.0);
-    else if (k == "handoff_build_us") *value = (long)(e->handoff_build_ms * 1000.0);
+    else if (k == "handoff_build_us") *value = (long)(e->pg.handoff_build_ms * 1000.0);
     else if (k == "handoff_early_us") *value = (long)(e->pg.early_ms * 1000.0);
     else if (k == "graph_uses") *value = (long)e->pg.graph_uses;
-    else if (k == "slice_rows") *value = e->empty_slice ? 0 : (long)(e->g.hi() - e->g.lo());
+    else if (k == "slice_rows") *value = e->pg.empty_slice ? 0 : (long)(e->g.hi() - e->g.lo());
     else if (k == "slice_entries") *value = (long)e->g.nnz;
-    else if (k == "giant_rows") *value = (long)e->n_giant;
-    else if (k == "giant_segments") *value = e->n_giant ? (long)e->gi_maxseg : 0;
-    else if (k == "giant_entries") *value = (long)e->giant_entries;
-    else if (k == "giant_row_threshold") *value = e->n_giant ? (long)e->giant_thresh : 0;
-    else if (k == "sorted_tiles_active") *value = e->sorted_wanted ? 1 : 0;
-    else if (k == "tile_waste_x100") *value = (long)(e->srt_waste * 100.0);
-    else if (k == "heavy_tail_x1000") *value = (long)(e->srt_tail * 1000.0);
-    else if (k == "interleaved_tiles") *value = e->interleave ? 1 : 0;
-    else if (k == "long_row_threshold") *value = e->n_long ? (long)e->long_thresh : 0;
+    else if (k == "giant_rows") *value = (long)e->pg.rows.n_giant;
+    else if (k == "giant_segments") *value = e->pg.rows.n_giant ? (long)e->pg.rows.maxseg : 0;
+    else if (k == "giant_entries") *value = (long)e->pg.rows.giant_entries;
+    else if (k == "giant_row_threshold") *value = e->pg.rows.n_giant ? (long)e->pg.rows.giant_thresh : 0;
+    else if (k == "sorted_tiles_active") *value = e->pg.rows.sorted_wanted ? 1 : 0;
+    else if (k == "tile_waste_x100") *value = (long)(e->pg.rows.waste * 100.0);
+    else if (k == "heavy_tail_x1000") *value = (long)(e->pg.rows.tail * 1000.0);
+    else if (k == "interleaved_tiles") *value = e->pg.rows.interleave ? 1 : 0;
+    else if (k == "long_row_threshold") *value = e->pg.rows.n_long ? (long)e->pg.rows.long_thresh : 0;
     else return GNNVC_ERR_INVALID;
     return GNNVC_OK;
 }
@@ -1436,11 +1436,11 @@ static uint32_t slices_arrived(const gnnvc_engine::PlanBuild &pb, const RP *rp, 
 extern "C++" {
 template <class RP>
 static int handoff_progress(gnnvc_engine *e, const RP *rp, uint32_t n, uint64_t sent) {
-    if (!e->early_open || (!e->lt_pb.open && !e->c4_pb.open)) return GNNVC_OK;
+    if (!e->early_open || (!e->pg.lt.pb.open && !e->pg.c4.pb.open)) return GNNVC_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    const uint32_t lt_to = e->lt_pb.open ? slices_arrived(e->lt_pb, rp, n, sent) : 0u;
-    const uint32_t c4_to = e->c4_pb.open ? slices_arrived(e->c4_pb, rp, n, sent) : 0u;
-    if ((e->lt_pb.open && lt_to > e->lt_pb.done) || (e->c4_pb.open && c4_to > e->c4_pb.done)) {
+    const uint32_t lt_to = e->pg.lt.pb.open ? slices_arrived(e->pg.lt.pb, rp, n, sent) : 0u;
+    const uint32_t c4_to = e->pg.c4.pb.open ? slices_arrived(e->pg.c4.pb, rp, n, sent) : 0u;
+    if ((e->pg.lt.pb.open && lt_to > e->pg.lt.pb.done) || (e->pg.c4.pb.open && c4_to > e->pg.c4.pb.done)) {
         HIP_TRY(e, hipEventRecord(e->ev_piece, e->stream));
         HIP_TRY(e, hipStreamWaitEvent(e->aux_stream, e->ev_piece, 0));
         int rc = lt_advance(e, lt_to, e->aux_stream);
@@ -1461,8 +1461,8 @@ static int adopt_uploaded(gnnvc_engine *e, uint32_t n, uint64_t nnz) {
         const GraphDev cand{n, nnz, e->rowptr.p, e->col.p, e->w.p, e->nw.p};
         uint32_t bad = 0;
         if (e->early_open) {   // (the graph was classed when its row pointers arrived: only the checks are left)
-            HIP_TRY(e, gnnvc::validate_graph(cand, e->blk_flag.p, e->stream));
-            HIP_TRY(e, hipMemcpyAsync(&bad, e->blk_flag.p, sizeof bad, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(e, gnnvc::validate_graph(cand, e->blk.flag.p, e->stream));
+            HIP_TRY(e, hipMemcpyAsync(&bad, e->blk.flag.p, sizeof bad, hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(e, hipStreamSynchronize(e->stream));
         } else {
             const int rc0 = classify_hand_off(e, cand, bad);
@@ -1482,8 +1482,8 @@ static int adopt_uploaded(gnnvc_engine *e, uint32_t n, uint64_t nnz) {
     e->early_open = false;
     e->g = GraphDev{n, nnz, e->rowptr.p, e->col.p, e->w.p, e->nw.p};
     e->have_graph = true;
-    e->empty_slice = false;
-    e->der_open = false;   // (a derivation begun against the previous graph must not be committed against this one)
+    e->pg.empty_slice = false;
+    e->pg.der_open = false;   // (a derivation begun against the previous graph must not be committed against this one)
     int rc = reserve_features(e, n);
     if (rc) return rc;
     if (!early) {
@@ -1514,12 +1514,12 @@ int gnnvc_upload_graph(gnnvc_engine *e, uint32_t n, const uint64_t *rowptr, cons
     if (nnz >= 0xFFFFFFFFull - GNNVC_COL_PAD)
         return fail(e, GNNVC_ERR_UNSUPPORTED, "nnz %llu does not fit 32-bit row pointers", (unsigned long long)nnz);
     if (nnz && !col) return fail(e, GNNVC_ERR_INVALID, "null column array");
-    e->der_open = false;
+    e->pg.der_open = false;
     HIP_TRY(e, e->rowptr.reserve((size_t)n + 1));
     HIP_TRY(e, e->col.reserve(nnz + GNNVC_COL_PAD));
     HIP_TRY(e, e->w.reserve(n));
     HIP_TRY(e, e->nw.reserve(n));
-    HIP_TRY(e, e->blk_flag.reserve(1));
+    HIP_TRY(e, e->blk.flag.reserve(1));
     // stream-ordered behind earlier forwards; the uint64 row pointers are staged in the scratch
     // buffer and narrowed on the device, and the sanity checks run there too (a host pass over
     // 2e8 column ids costs more than the copy)
@@ -1539,7 +1539,7 @@ int gnnvc_upload_graph(gnnvc_engine *e, uint32_t n, const uint64_t *rowptr, cons
         reset_graph_state(e);
         return rc;
     }
-    if (e->early_open && (e->lt_pb.open || e->c4_pb.open)) {
+    if (e->early_open && (e->pg.lt.pb.open || e->pg.c4.pb.open)) {
         // the column array in pieces: while piece k + 1 crosses the bus the second stream regroups the slices piece k completed
         const uint64_t piece = 16ull << 20;
         for (uint64_t at = 0; at < nnz; at += piece) {
@@ -1603,7 +1603,7 @@ int gnnvc_staged_columns_ready(gnnvc_engine *e, uint64_t first, uint64_t count) 
     if (rc) return rc;
     if (!e->staged_sent) {   // first piece: the device array is about to be overwritten
         e->have_graph = false;
-        e->der_open = false;
+        e->pg.der_open = false;
         HIP_TRY(e, e->col.reserve(e->staged_nnz + GNNVC_COL_PAD));
     }
     HIP_TRY(e, hipMemcpyAsync(e->col.p + first, e->pin_col.p + first, count * sizeof(uint32_t), hipMemcpyHostToDevice,
@@ -1654,7 +1654,7 @@ int gnnvc_commit_staged_graph(gnnvc_engine *e) {
     HIP_TRY(e, e->col.reserve(nnz + GNNVC_COL_PAD));
     HIP_TRY(e, e->w.reserve(n));
     HIP_TRY(e, e->nw.reserve(n));
-    HIP_TRY(e, e->blk_flag.reserve(1));
+    HIP_TRY(e, e->blk.flag.reserve(1));
     if (n && !e->early_open) {   // (an early hand-off sent them with its first piece)
         HIP_TRY(e, hipMemcpyAsync(e->rowptr.p, e->pin_rowptr.p, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(e, hipMemcpyAsync(e->w.p, e->pin_w.p, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
@@ -1684,8 +1684,8 @@ static int attach_common(gnnvc_engine *e, const GraphDev &cand) {
     }
     e->g = cand;
     e->have_graph = true;
-    e->empty_slice = false;
-    e->der_open = false;
+    e->pg.empty_slice = false;
+    e->pg.der_open = false;
     int rc = reserve_features(e, cand.n);
     if (rc) return rc;
     // (a staged hand-off that opened the early builders may have been abandoned or refused before its commit: nothing of it —
@@ -1705,8 +1705,8 @@ static int attach_common(gnnvc_engine *e, const GraphDev &cand) {
 int gnnvc_derive_graph_begin(gnnvc_engine *e, uint32_t n_new, const uint32_t *old_row, const uint32_t *rowptr_new, uint32_t *tail) {
     if (!e) return GNNVC_ERR_INVALID;
     NOT_ON_MULTI(e, "gnnvc_derive_graph_begin");
-    e->der_open = false;
-    if (!e->have_graph || e->g.rowptr != e->rowptr.p || e->g.col != e->col.p || e->g.sliced() || e->empty_slice)
+    e->pg.der_open = false;
+    if (!e->have_graph || e->g.rowptr != e->rowptr.p || e->g.col != e->col.p || e->g.sliced() || e->pg.empty_slice)
         return fail(e, GNNVC_ERR_STATE, "no engine-owned whole graph is resident (hand one over with gnnvc_upload_graph or the staged calls first)");
     if (n_new && (!old_row || !rowptr_new || !tail)) return fail(e, GNNVC_ERR_INVALID, "null arrays");
     int rc = use_device(e);
@@ -1718,17 +1718,17 @@ int gnnvc_derive_graph_begin(gnnvc_engine *e, uint32_t n_new, const uint32_t *ol
     HIP_TRY(e, e->rowptr2.reserve((size_t)n_new + 1));
     HIP_TRY(e, e->der_new_of.reserve(std::max<uint32_t>(e->g.n, 1u)));
     HIP_TRY(e, e->der_tail.reserve(n_new));
-    HIP_TRY(e, e->blk_flag.reserve(1));
+    HIP_TRY(e, e->blk.flag.reserve(1));
     if (n_new) {
         HIP_TRY(e, hipMemcpyAsync(e->der_old_row.p, old_row, (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(e, hipMemcpyAsync(e->rowptr2.p, rowptr_new, ((size_t)n_new + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     } else {
         HIP_TRY(e, hipMemsetAsync(e->rowptr2.p, 0, sizeof(uint32_t), e->stream));
     }
-    HIP_TRY(e, gnnvc::derive_tails(e->g, e->der_old_row.p, n_new, e->rowptr2.p, e->der_new_of.p, e->der_tail.p, e->blk_flag.p, e->stream));
+    HIP_TRY(e, gnnvc::derive_tails(e->g, e->der_old_row.p, n_new, e->rowptr2.p, e->der_new_of.p, e->der_tail.p, e->blk.flag.p, e->stream));
     uint32_t bad = 0;
     if (n_new) HIP_TRY(e, hipMemcpyAsync(tail, e->der_tail.p, (size_t)n_new * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(&bad, e->blk_flag.p, sizeof bad, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(&bad, e->blk.flag.p, sizeof bad, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     if (bad)
         return fail(e, GNNVC_ERR_INVALID, "%s", (bad & 1u) ? "old_row[] names a row the resident graph does not have"
@@ -1737,24 +1737,24 @@ int gnnvc_derive_graph_begin(gnnvc_engine *e, uint32_t n_new, const uint32_t *ol
     e->der_tail_host.assign(tail, tail + n_new);
     uint64_t total = 0;
     for (uint32_t u = 0; u < n_new; ++u) total += tail[u];
-    e->der_n_new = n_new;
-    e->der_nnz_new = nnz_new;
-    e->der_tail_total = total;
-    e->der_open = true;
+    e->pg.der_n_new = n_new;
+    e->pg.der_nnz_new = nnz_new;
+    e->pg.der_tail_total = total;
+    e->pg.der_open = true;
     return GNNVC_OK;
 }
 
 int gnnvc_derive_graph_commit(gnnvc_engine *e, const uint32_t *tail_cols, uint64_t n_tail, const uint32_t *w, const uint32_t *nw) {
     if (!e) return GNNVC_ERR_INVALID;
     NOT_ON_MULTI(e, "gnnvc_derive_graph_commit");
-    if (!e->der_open) return fail(e, GNNVC_ERR_STATE, "gnnvc_derive_graph_begin first");
-    e->der_open = false;
+    if (!e->pg.der_open) return fail(e, GNNVC_ERR_STATE, "gnnvc_derive_graph_begin first");
+    e->pg.der_open = false;
     e->early_open = e->early_declined = false;   // (an abandoned staged hand-off must not pass for this graph's)
-    if (!e->have_graph || e->g.rowptr != e->rowptr.p || e->g.col != e->col.p || e->g.sliced() || e->empty_slice)
+    if (!e->have_graph || e->g.rowptr != e->rowptr.p || e->g.col != e->col.p || e->g.sliced() || e->pg.empty_slice)
         return fail(e, GNNVC_ERR_STATE, "the resident graph changed since gnnvc_derive_graph_begin");
-    const uint32_t n = e->der_n_new;
-    if (n_tail != e->der_tail_total) return fail(e, GNNVC_ERR_INVALID, "expected %llu tail entries, got %llu",
-                                                 (unsigned long long)e->der_tail_total, (unsigned long long)n_tail);
+    const uint32_t n = e->pg.der_n_new;
+    if (n_tail != e->pg.der_tail_total) return fail(e, GNNVC_ERR_INVALID, "expected %llu tail entries, got %llu",
+                                                 (unsigned long long)e->pg.der_tail_total, (unsigned long long)n_tail);
     if ((n_tail && !tail_cols) || (n && (!w || !nw))) return fail(e, GNNVC_ERR_INVALID, "null arrays");
     int rc = use_device(e);
     if (rc) return rc;
@@ -1762,12 +1762,12 @@ int gnnvc_derive_graph_commit(gnnvc_engine *e, const uint32_t *tail_cols, uint64
     for (uint32_t u = 0; u < n; ++u) tptr[u + 1] = tptr[u] + e->der_tail_host[u];
     HIP_TRY(e, e->der_tailptr.reserve((size_t)n + 1));
     HIP_TRY(e, e->der_tailcols.reserve(std::max<uint64_t>(n_tail, 1)));
-    HIP_TRY(e, e->col2.reserve(e->der_nnz_new + GNNVC_COL_PAD));
+    HIP_TRY(e, e->col2.reserve(e->pg.der_nnz_new + GNNVC_COL_PAD));
     HIP_TRY(e, hipMemcpy(e->der_tailptr.p, tptr.data(), tptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (n_tail) HIP_TRY(e, hipMemcpyAsync(e->der_tailcols.p, tail_cols, n_tail * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(e, gnnvc::derive_fill(e->g, e->der_old_row.p, e->der_new_of.p, e->rowptr2.p, e->der_tailptr.p, e->der_tailcols.p, n,
                                   e->col2.p, e->stream));
-    HIP_TRY(e, hipMemsetAsync(e->col2.p + e->der_nnz_new, 0, GNNVC_COL_PAD * sizeof(uint32_t), e->stream));
+    HIP_TRY(e, hipMemsetAsync(e->col2.p + e->pg.der_nnz_new, 0, GNNVC_COL_PAD * sizeof(uint32_t), e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the old arrays are about to change hands)
     std::swap(e->rowptr, e->rowptr2);
     std::swap(e->col, e->col2);
@@ -1778,13 +1778,13 @@ int gnnvc_derive_graph_commit(gnnvc_engine *e, const uint32_t *tail_cols, uint64
         HIP_TRY(e, hipMemcpyAsync(e->w.p, w, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(e, hipMemcpyAsync(e->nw.p, nw, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     }
-    return adopt_uploaded(e, n, e->der_nnz_new);
+    return adopt_uploaded(e, n, e->pg.der_nnz_new);
 }
 
 int gnnvc_graph_row_hashes(gnnvc_engine *e, uint64_t *hashes) {
     if (!e) return GNNVC_ERR_INVALID;
     NOT_ON_MULTI(e, "gnnvc_graph_row_hashes");
-    if (!e->have_graph || e->empty_slice) return fail(e, GNNVC_ERR_STATE, "no graph attached");
+    if (!e->have_graph || e->pg.empty_slice) return fail(e, GNNVC_ERR_STATE, "no graph attached");
     const uint32_t rows = e->g.hi() - e->g.lo();
     if (!rows) return GNNVC_OK;
     if (!hashes) return fail(e, GNNVC_ERR_INVALID, "null output");
@@ -1825,24 +1825,14 @@ int gnnvc_attach_graph_slice(gnnvc_engine *e, uint32_t n_global, uint32_t row_lo
     cand.row_base = row_lo;
     cand.row_end = row_hi ? row_hi : 0;
     if (row_lo == 0 && row_hi == n_global) cand.row_end = 0;   // the whole graph after all
-    e->der_open = false;
-    if (row_hi == 0) {   // an empty slice at the front: nothing to compute, nothing to index
-        e->g = GraphDev{n_global, 0, d_rowptr_local, d_col_local, d_w_local, d_nw_local};
-        e->g.row_base = 0;
-        e->g.row_end = 0;
-        e->have_graph = true;
-        e->n_long = e->n_giant = 0;
-        e->empty_slice = true;
-        reset_graph_state(e);   // (nothing of the previous graph's: its classing least of all — "generic_heavy_rows" reads it)
-        return GNNVC_OK;
-    }
-    e->empty_slice = row_hi == row_lo;
-    if (e->empty_slice) {
+    e->pg.der_open = false;
+    if (row_hi == row_lo) {   // an empty slice: nothing to compute, nothing to index — and nothing of the previous graph's
         e->g = cand;
         e->g.row_end = row_hi;
+        if (row_hi == 0) e->g.nnz = 0;   // (at the front)
         e->have_graph = true;
-        e->n_long = e->n_giant = 0;
         reset_graph_state(e);
+        e->pg.empty_slice = true;
         return GNNVC_OK;
     }
     return attach_common(e, cand);
@@ -1859,21 +1849,21 @@ int gnnvc_stage_forward_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint
     if (stage < 0 || stage >= (int)e->stage_list().size()) return fail(e, GNNVC_ERR_INVALID, "stage %d out of range", stage);
     if (row_lo > row_hi || row_hi > e->g.n) return fail(e, GNNVC_ERR_INVALID, "row range [%u,%u) outside graph of %u", row_lo, row_hi, e->g.n);
     if (row_lo == row_hi) return GNNVC_OK;
-    if (e->empty_slice || row_lo < e->g.lo() || row_hi > e->g.hi())
+    if (e->pg.empty_slice || row_lo < e->g.lo() || row_hi > e->g.hi())
         return fail(e, GNNVC_ERR_INVALID, "rows [%u,%u) are not in the slice [%u,%u) this engine holds", row_lo, row_hi, e->g.lo(),
-                    e->empty_slice ? e->g.lo() : e->g.hi());
+                    e->pg.empty_slice ? e->g.lo() : e->g.hi());
     if (!d_in || !d_out) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
     int rc = use_device(e);
     if (rc) return rc;
-    e->heavy_last_rows = 0;
-    e->ggiant_last_rows = 0;
-    e->ggiant_last_segmented = false;
+    e->call.heavy_last_rows = 0;
+    e->call.ggiant_last_rows = 0;
+    e->call.ggiant_last_segmented = false;
     if (e->generic_on()) {   // (k_stage_any, with k_any_heavy_sums on a graph with heavy rows; a generic stage audits nothing)
         const StagePlan &sp = e->gstages[stage];
         return run_generic_stage(e, sp, d_in, d_out, sp.sigmoid_last ? d_logits : nullptr, row_lo, row_hi);
     }
     if (!audit) return run_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits);
-    e->audit_now = true;
+    e->call.audit_now = true;
     std::string plan;
     rc = run_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits, false, &plan);
     if (rc == GNNVC_OK) rc = audit_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits, plan);
@@ -1891,14 +1881,14 @@ int gnnvc_audit_stage_device(gnnvc_engine *e, int stage, uint32_t row_lo, uint32
     if (stage < 0 || stage >= (int)e->stage_list().size()) return fail(e, GNNVC_ERR_INVALID, "stage %d out of range", stage);
     if (row_lo > row_hi || row_hi > e->g.n) return fail(e, GNNVC_ERR_INVALID, "row range [%u,%u) outside graph of %u", row_lo, row_hi, e->g.n);
     if (row_lo == row_hi) return GNNVC_OK;
-    if (e->empty_slice || row_lo < e->g.lo() || row_hi > e->g.hi())
+    if (e->pg.empty_slice || row_lo < e->g.lo() || row_hi > e->g.hi())
         return fail(e, GNNVC_ERR_INVALID, "rows [%u,%u) are not in the slice [%u,%u) this engine holds", row_lo, row_hi, e->g.lo(),
-                    e->empty_slice ? e->g.lo() : e->g.hi());
+                    e->pg.empty_slice ? e->g.lo() : e->g.hi());
     if (!d_in || !d_out) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
     int rc = use_device(e);
     if (rc) return rc;
-    e->audit_pending.clear();
-    e->audit_now = true;
+    e->call.audit_pending.clear();
+    e->call.audit_now = true;
     std::string plan = e->generic_on() ? "the caller's buffers (k_stage_any's, if gnnvc_stage_forward_device filled them)" : "the caller's buffers";
     rc = audit_stage(e, stage, row_lo, row_hi, d_in, d_out, d_logits, plan, /*hook=*/false);
     rc = audit_finish(e, rc);
@@ -1941,10 +1931,10 @@ static int forward_device_impl(gnnvc_engine *e, const float *d_x, float *d_score
         if (!e->have_graph) return fail(e, GNNVC_ERR_STATE, "no graph attached");
         if (e->layers.empty()) return fail(e, GNNVC_ERR_STATE, "engine was created without a model");
         if (e->stage_list().empty()) return fail(e, GNNVC_ERR_UNSUPPORTED, "model is not fused into stages: there is nothing to audit");
-        e->audit_now = true;
+        e->call.audit_now = true;
     } else {
         // (an unfused model runs the layer-by-layer kernels, a generic-stage model k_stage_any: the period audits nothing)
-        e->audit_now = audit && !e->stages.empty() && !e->generic_on();
+        e->call.audit_now = audit && !e->stages.empty() && !e->generic_on();
     }
     const int rc = audit_finish(e, forward_single(e, d_x, d_scores, d_logits));
     if (audit && e->opt.audit_log) audit_log_line(e, rc);
@@ -1968,16 +1958,16 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     e->live_seen.clear();   // ("generic_live_*_<s>": what THIS forward examines, forward_generic)
     if (e->layers.empty()) return fail(e, GNNVC_ERR_STATE, "engine was created without a model");
     if (n == 0) return GNNVC_OK;
-    if (e->g.sliced() || e->empty_slice)
+    if (e->g.sliced() || e->pg.empty_slice)
         return fail(e, GNNVC_ERR_STATE, "this engine holds a slice of the graph: run it stage by stage (gnnvc_stage_forward_device)");
     if (!d_x || !d_scores) return fail(e, GNNVC_ERR_INVALID, "null feature buffers");
     int rc = use_device(e);
     if (rc) return rc;
-    e->plan_memsets = 0;
+    e->pg.plan_memsets = 0;
     e->generic_ran = e->generic_on();
-    e->heavy_last_rows = 0;
-    e->ggiant_last_rows = 0;
-    e->ggiant_last_segmented = false;   // (run_generic_stage sets it)
+    e->call.heavy_last_rows = 0;
+    e->call.ggiant_last_rows = 0;
+    e->call.ggiant_last_segmented = false;   // (run_generic_stage sets it)
     if (e->generic_ran || e->stages.empty()) {
         rc = ensure_events(e, 2);
         if (rc) return rc;
@@ -1993,42 +1983,42 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     rc = ensure_events(e, ns + 1);
     if (rc) return rc;
     const float *cur = d_x;   // (the pad rows of e->h were zeroed when the graph was handed over: reserve_features)
-    e->c4_fused_for = -1;
-    e->pg.c4_prepared_stage = -1;
-    if (e->pg.fit_pending && hipEventQuery(e->ev_fit) == hipSuccess) {   // the previous forward's verdicts have arrived
-        e->pg.fit_pending = false;
-        const uint32_t before = e->pg.lt_unfit_runs + e->t4_unfit_runs + e->pg.c4_unfit_runs[1] + e->pg.c4_unfit_runs[2];
-        const bool seen1 = e->t4_fit_seen[1], seen2 = e->t4_fit_seen[2];
-        if (e->pg.lt_used && e->pg.lt_ready) {
-            e->pg.lt_unfit_runs = e->fit_pin.p[2] != 0u ? e->pg.lt_unfit_runs + 1 : 0u;
-            if (e->pg.lt_unfit_runs >= (e->lt_mapped ? 1u : 3u)) e->pg.lt_off = true;
+    e->call.c4_fused_for = -1;
+    e->pg.c4.prepared_stage = -1;
+    if (e->pg.c4.fit_pending && hipEventQuery(e->ev_fit) == hipSuccess) {   // the previous forward's verdicts have arrived
+        e->pg.c4.fit_pending = false;
+        const uint32_t before = e->pg.lt.unfit_runs + e->pg.t4.unfit_runs + e->pg.c4.unfit_runs[1] + e->pg.c4.unfit_runs[2];
+        const bool seen1 = e->pg.t4.fit_seen[1], seen2 = e->pg.t4.fit_seen[2];
+        if (e->pg.lt.used && e->pg.lt.ready) {
+            e->pg.lt.unfit_runs = e->fit_pin.p[2] != 0u ? e->pg.lt.unfit_runs + 1 : 0u;
+            if (e->pg.lt.unfit_runs >= (e->pg.lt.mapped ? 1u : 3u)) e->pg.lt.off = true;
         }
-        if (e->t4_used && e->t4_ok) {
+        if (e->pg.t4.used && e->pg.t4.ok) {
             // table tiles: a graph whose first 16-wide stage keeps missing (more than four live columns: sparse graphs) stops paying
             // for the counters, the choice and the launches that leave at once — the first forward on a graph always misses (nobody
             // has chosen columns yet), hence four in a row
-            e->t4_unfit_runs = e->fit_pin.p[3] == 0u ? e->t4_unfit_runs + 1 : 0u;
-            if (e->t4_unfit_runs >= 4u) e->t4_ok = false;
+            e->pg.t4.unfit_runs = e->fit_pin.p[3] == 0u ? e->pg.t4.unfit_runs + 1 : 0u;
+            if (e->pg.t4.unfit_runs >= 4u) e->pg.t4.ok = false;
             // a stage whose table fit the last forward seen gets no gathering kernel behind it (k_stage_t4's solo mode copes with
             // the rare forward that does not fit after all)
-            e->t4_fit_seen[1] = e->fit_pin.p[3] != 0u;
-            e->t4_fit_seen[2] = e->fit_pin.p[4] != 0u;
+            e->pg.t4.fit_seen[1] = e->fit_pin.p[3] != 0u;
+            e->pg.t4.fit_seen[2] = e->fit_pin.p[4] != 0u;
         }
         for (int s = 1; s <= 2; ++s) {
-            if (!e->pg.fit_used[s]) continue;
+            if (!e->pg.c4.fit_used[s]) continue;
             // (a stage whose statistics were to come from a producer that itself fell back had no chance: not its miss)
-            if (s == 2 && e->pg.fit_used[1] && e->fit_pin.p[0] == 0u) continue;
-            e->pg.c4_unfit_runs[s] = e->fit_pin.p[s - 1] == 0u ? e->pg.c4_unfit_runs[s] + 1 : 0u;
-            if (e->pg.c4_unfit_runs[s] >= 3u) e->pg.c4_stage_off[s] = true;
+            if (s == 2 && e->pg.c4.fit_used[1] && e->fit_pin.p[0] == 0u) continue;
+            e->pg.c4.unfit_runs[s] = e->fit_pin.p[s - 1] == 0u ? e->pg.c4.unfit_runs[s] + 1 : 0u;
+            if (e->pg.c4.unfit_runs[s] >= 3u) e->pg.c4.stage_off[s] = true;
         }
-        const uint32_t after = e->pg.lt_unfit_runs + e->t4_unfit_runs + e->pg.c4_unfit_runs[1] + e->pg.c4_unfit_runs[2];
-        const bool calm = after == 0u && before == 0u && seen1 == e->t4_fit_seen[1] && seen2 == e->t4_fit_seen[2];
-        e->pg.fit_calm = calm ? e->pg.fit_calm + 1u : 0u;
+        const uint32_t after = e->pg.lt.unfit_runs + e->pg.t4.unfit_runs + e->pg.c4.unfit_runs[1] + e->pg.c4.unfit_runs[2];
+        const bool calm = after == 0u && before == 0u && seen1 == e->pg.t4.fit_seen[1] && seen2 == e->pg.t4.fit_seen[2];
+        e->pg.c4.fit_calm = calm ? e->pg.c4.fit_calm + 1u : 0u;
     }
-    if (!e->pg.fit_pending) {
-        for (int s = 0; s < 4; ++s) e->pg.fit_used[s] = false;
-        e->pg.lt_used = false;
-        e->t4_used = false;
+    if (!e->pg.c4.fit_pending) {
+        for (int s = 0; s < 4; ++s) e->pg.c4.fit_used[s] = false;
+        e->pg.lt.used = false;
+        e->pg.t4.used = false;
     }
     struct SinkGuard {   // the thread-local sink never outlives this call, whichever way it returns
         ~SinkGuard() { gnnvc::set_kernel_trace(nullptr); }
@@ -2040,11 +2030,11 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     // Table tiles are offered from a graph's SECOND forward on — or from its first, when the engine carries a choice of columns
     // over from its previous graph: a fresh engine's first forward on a graph has no table to gather from, and the counting, the
     // choice and the launches that leave at once would only cost the caller who scores the graph once (ER-100K: 0.14 vs 0.11 ms).
-    e->t4_now = e->t4_ok && (e->t4_choice_live || e->pg.graph_uses >= 1);
+    e->call.t4_now = e->pg.t4.ok && (e->t4.choice_live || e->pg.graph_uses >= 1);
     // Events (option "forward_timing"): none by default — a record costs the stream ~1.8 us, four of them were 5.5 us of a small
     // graph's 31 - 82 us forward (scratch/experiments/r4_gaps.sh) — 1 = the forward's first and last, 2 = one per stage as well.
     // (ev[0] is also what the first-forward plan build on the second stream waits for, below.)
-    const bool build_under_stage0 = ns >= 2 && !e->pg.c4_tried && !e->pg.c4_range_mode && e->aux_stream && e->n_long == 0 && !e->sorted_wanted &&
+    const bool build_under_stage0 = ns >= 2 && !e->pg.c4.tried && !e->pg.c4.range_mode && e->aux_stream && e->pg.rows.n_long == 0 && !e->pg.rows.sorted_wanted &&
                                     e->opt.compact_first_entries && e->g.nnz >= e->opt.compact_first_entries;
     if (e->opt.timing >= 1 || build_under_stage0) HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
     if (e->opt.poison)   // (tests, fuzz: rows 0 .. n - 1 of both feature buffers; the pad row n stays zero)
@@ -2053,11 +2043,11 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
         const bool last = s + 1 == ns;
         float *dst = last ? d_scores : e->h[s & 1].p;
         std::string plan;
-        rc = run_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, /*in_forward=*/true, e->audit_now ? &plan : nullptr);
+        rc = run_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, /*in_forward=*/true, e->call.audit_now ? &plan : nullptr);
         if (rc) break;
-        if (e->audit_now && (rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan)) != GNNVC_OK) break;
+        if (e->call.audit_now && (rc = audit_stage(e, (int)s, 0, n, cur, dst, last ? d_logits : nullptr, plan)) != GNNVC_OK) break;
         if ((e->opt.timing >= 2 || (last && e->opt.timing == 1)) && hipEventRecord(e->ev[s + 1], e->stream) != hipSuccess) { rc = fail(e, GNNVC_ERR_DEVICE, "hipEventRecord failed"); break; }
-        if (s == 0 && build_under_stage0 && !e->pg.c4_tried) {
+        if (s == 0 && build_under_stage0 && !e->pg.c4.tried) {
             // A large graph's first forward: the compact-table plan of the stages to come depends on the graph alone — it is
             // built now, on the second stream, under the kernels of stage 0 that were just queued (the build synchronises with
             // its own stream only; it is complete when it returns).
@@ -2073,24 +2063,24 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     }
     gnnvc::set_kernel_trace(nullptr);
     if (rc) return rc;
-    if (e->t4_now) {   // (the descriptors this forward's table tiles wrote are the next forward's specs)
-        e->t4_parity ^= 1u;
-        e->t4_choice_live = true;
+    if (e->call.t4_now) {   // (the descriptors this forward's table tiles wrote are the next forward's specs)
+        e->t4.parity ^= 1u;
+        e->t4.choice_live = true;
     }
     e->ev_count = e->opt.timing >= 1 ? (int)ns + 1 : 0;
     e->ev_stages = e->opt.timing >= 2;
-    const bool c4_verdicts = (e->pg.fit_used[1] || e->pg.fit_used[2]) && e->pg.c4_ready && e->c4_desc.p;
-    const bool lt_verdict = e->pg.lt_used && e->pg.lt_ready && e->lt_bad.p;
-    const bool t4_verdict = e->t4_now && e->t4_desc.p;
-    if (t4_verdict && !e->pg.fit_pending) e->t4_used = true;
-    if (!e->pg.fit_pending && (c4_verdicts || lt_verdict || t4_verdict)) {   // this forward's verdicts, written out behind it
+    const bool c4_verdicts = (e->pg.c4.fit_used[1] || e->pg.c4.fit_used[2]) && e->pg.c4.ready && e->c4.desc.p;
+    const bool lt_verdict = e->pg.lt.used && e->pg.lt.ready && e->lt.bad.p;
+    const bool t4_verdict = e->call.t4_now && e->t4.desc.p;
+    if (t4_verdict && !e->pg.c4.fit_pending) e->pg.t4.used = true;
+    if (!e->pg.c4.fit_pending && (c4_verdicts || lt_verdict || t4_verdict)) {   // this forward's verdicts, written out behind it
         // ONE small kernel stores the words into page-locked host memory (round 4: they were up to five 4-byte hipMemcpyAsync, ~20 us
         // of a small graph's forward + wait, scratch/experiments/r4_gaps.sh), and once four verdicts in a row have changed nothing
         // only every eighth forward asks — a verdict steers which kernels the NEXT forwards launch, never a result: every plan
         // proves its input on the device in every call.
-        const bool ask = e->pg.fit_calm < 4u || (++e->pg.fit_skip % e->opt.verdict_period) == 0u;
+        const bool ask = e->pg.c4.fit_calm < 4u || (++e->pg.c4.fit_skip % e->opt.verdict_period) == 0u;
         if (!ask) {
-            if (!c4_verdicts) for (int s = 1; s <= 2; ++s) e->pg.fit_used[s] = false;
+            if (!c4_verdicts) for (int s = 1; s <= 2; ++s) e->pg.c4.fit_used[s] = false;
             return GNNVC_OK;
         }
         if (!e->ev_fit) HIP_TRY(e, e->ev_fit.create(hipEventDisableTiming));
@@ -2100,15 +2090,15 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
         }
         gnnvc::VerdictWords vw;
         if (c4_verdicts)
-            for (int s = 1; s <= 2; ++s) vw.src[s - 1] = e->c4_desc.p + gnnvc_engine::kDescWords * (s - 1);
+            for (int s = 1; s <= 2; ++s) vw.src[s - 1] = e->c4.desc.p + gnnvc_engine::kDescWords * (s - 1);
         else
-            for (int s = 1; s <= 2; ++s) e->pg.fit_used[s] = false;
-        if (lt_verdict) vw.src[2] = e->lt_bad.p;
+            for (int s = 1; s <= 2; ++s) e->pg.c4.fit_used[s] = false;
+        if (lt_verdict) vw.src[2] = e->lt.bad.p;
         if (t4_verdict)   // (the parity has flipped: the descriptors this forward wrote are the current ones)
-            for (int s = 1; s <= 2; ++s) vw.src[2 + s] = e->t4_desc_of(s, e->t4_parity) + 8;
+            for (int s = 1; s <= 2; ++s) vw.src[2 + s] = e->t4.desc_of(s, e->t4.parity) + 8;
         HIP_TRY(e, gnnvc::write_verdicts(vw, e->fit_dev, e->stream));
         HIP_TRY(e, hipEventRecord(e->ev_fit, e->stream));
-        e->pg.fit_pending = true;
+        e->pg.c4.fit_pending = true;
     }
     return GNNVC_OK;
 }
@@ -2120,29 +2110,29 @@ int gnnvc_stage_input_ready(gnnvc_engine *e, int stage, const float *d_in, uint3
     if (e->stages.empty()) return fail(e, GNNVC_ERR_UNSUPPORTED, "model is not fused into stages");
     if (stage < 1 || stage >= (int)e->stages.size()) return fail(e, GNNVC_ERR_INVALID, "stage %d has no 16-wide input", stage);
     if (row_lo > row_hi || row_hi > e->g.n) return fail(e, GNNVC_ERR_INVALID, "row range [%u, %u) outside the graph", row_lo, row_hi);
-    e->pg.c4_prepared_stage = -1;
-    if (e->g.n == 0 || row_lo == row_hi || e->empty_slice) return GNNVC_OK;
+    e->pg.c4.prepared_stage = -1;
+    if (e->g.n == 0 || row_lo == row_hi || e->pg.empty_slice) return GNNVC_OK;
     if (!d_in) return fail(e, GNNVC_ERR_INVALID, "null feature buffer");
     int rc = use_device(e);
     if (rc) return rc;
-    const bool same_range = e->pg.c4_range_mode && e->pg.c4_tried && e->c4_base == row_lo && e->c4_end == row_hi;
-    e->pg.c4_range_mode = true;
+    const bool same_range = e->pg.c4.range_mode && e->pg.c4.tried && e->pg.c4.base == row_lo && e->pg.c4.end == row_hi;
+    e->pg.c4.range_mode = true;
     if (!same_range) {
         rc = build_compact(e, row_lo, row_hi);
         if (rc) return rc;
-        if (!e->pg.c4_ready) {   // remember what was tried, so that the next forward does not try again
-            e->c4_base = row_lo;
-            e->c4_end = row_hi;
+        if (!e->pg.c4.ready) {   // remember what was tried, so that the next forward does not try again
+            e->pg.c4.base = row_lo;
+            e->pg.c4.end = row_hi;
         }
     }
-    if (!e->pg.c4_ready || e->n_long > 0) return GNNVC_OK;   // the plan does not apply to this graph: nothing to prepare
-    uint32_t *desc = e->c4_desc.p + gnnvc_engine::kDescWords * (stage - 1);
-    e->c4_last_desc = gnnvc_engine::kDescWords * (stage - 1);
-    HIP_TRY(e, gnnvc::column_counts(d_in, e->g.n, e->c4_counts.p, e->stream));
-    HIP_TRY(e, gnnvc::launch_compact_gather(e->g, compact_plan(e), d_in, e->c4_counts.p, 1, desc, e->c4_table.p, e->c4_acc.p, e->c4_base,
-                                            e->c4_end, e->c4_dirty.p, e->c4_dirty_cap, e->c4_agg16.p, e->stream, /*what=*/1));
-    e->pg.c4_prepared_stage = stage;
-    e->c4_prepared_in = d_in;
+    if (!e->pg.c4.ready || e->pg.rows.n_long > 0) return GNNVC_OK;   // the plan does not apply to this graph: nothing to prepare
+    uint32_t *desc = e->c4.desc.p + gnnvc_engine::kDescWords * (stage - 1);
+    e->pg.c4.last_desc = gnnvc_engine::kDescWords * (stage - 1);
+    HIP_TRY(e, gnnvc::column_counts(d_in, e->g.n, e->c4.counts.p, e->stream));
+    HIP_TRY(e, gnnvc::launch_compact_gather(e->g, compact_plan(e), d_in, e->c4.counts.p, 1, desc, e->c4.table.p, e->c4.acc.p, e->pg.c4.base,
+                                            e->pg.c4.end, e->c4.dirty.p, e->pg.c4.dirty_cap, e->c4.agg16.p, e->stream, /*what=*/1));
+    e->pg.c4.prepared_stage = stage;
+    e->pg.c4.prepared_in = d_in;
     return GNNVC_OK;
 }
 
@@ -2176,7 +2166,7 @@ static int forward_host(gnnvc_engine *e, const float *x, float *scores, float *l
         return GNNVC_OK;
     }
     // (before the copy below: a sliced engine has no feature buffers of its own — e->x may be null or sized for an earlier graph)
-    if (e->g.sliced() || e->empty_slice)
+    if (e->g.sliced() || e->pg.empty_slice)
         return fail(e, GNNVC_ERR_STATE, "this engine holds a slice of the graph: run it stage by stage (gnnvc_stage_forward_device)");
     if (!x || !scores) return fail(e, GNNVC_ERR_INVALID, "null host buffers");
     int rc = use_device(e);
@@ -2211,7 +2201,7 @@ int gnnvc_reduction_flags(gnnvc_engine *e, uint32_t max_degree, uint8_t *flags) 
     if (!e->have_graph) return fail(e, GNNVC_ERR_STATE, "no graph attached");
     const uint32_t n = e->g.n;
     if (n == 0) return GNNVC_OK;
-    if (e->g.sliced() || e->empty_slice) return fail(e, GNNVC_ERR_STATE, "this engine holds a slice of the graph");
+    if (e->g.sliced() || e->pg.empty_slice) return fail(e, GNNVC_ERR_STATE, "this engine holds a slice of the graph");
     if (!flags) return fail(e, GNNVC_ERR_INVALID, "null flags buffer");
     int rc = use_device(e);
     if (rc) return rc;
@@ -2232,10 +2222,10 @@ int gnnvc_live_columns(gnnvc_engine *e, const float *d_feat, uint32_t rows, uint
     if (!d_feat) return fail(e, GNNVC_ERR_INVALID, "null feature buffer");
     int rc = use_device(e);
     if (rc) return rc;
-    HIP_TRY(e, e->blk_flag.reserve(1));
+    HIP_TRY(e, e->blk.flag.reserve(1));
     HIP_TRY(e, e->pin_small.reserve(16));
-    HIP_TRY(e, gnnvc::live_columns(d_feat, rows, e->blk_flag.p, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->pin_small.p, e->blk_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, gnnvc::live_columns(d_feat, rows, e->blk.flag.p, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->pin_small.p, e->blk.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     *mask = e->pin_small.p[0];
     return GNNVC_OK;
@@ -2249,10 +2239,10 @@ int gnnvc_column_counts(gnnvc_engine *e, const float *d_feat, uint32_t rows, uin
     if (!d_feat) return fail(e, GNNVC_ERR_INVALID, "null feature buffer");
     int rc = use_device(e);
     if (rc) return rc;
-    HIP_TRY(e, e->srt_sum.reserve(16));
+    HIP_TRY(e, e->srt.sum.reserve(16));
     HIP_TRY(e, e->pin_small.reserve(64));
-    HIP_TRY(e, gnnvc::column_counts(d_feat, rows, e->srt_sum.p, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->pin_small.p, e->srt_sum.p, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, gnnvc::column_counts(d_feat, rows, e->srt.sum.p, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->pin_small.p, e->srt.sum.p, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     std::memcpy(counts, e->pin_small.p, 16 * sizeof(uint64_t));
     return GNNVC_OK;
@@ -2465,7 +2455,7 @@ int gnnvc_graph_layer_forward(gnnvc_engine *e, uint32_t f, const float *in, floa
     if (f == 0) return fail(e, GNNVC_ERR_INVALID, "zero feature width");
     const uint32_t n = e->g.n;
     if (n == 0) return GNNVC_OK;
-    if (e->g.sliced() || e->empty_slice) return fail(e, GNNVC_ERR_STATE, "this engine holds a slice of the graph");
+    if (e->g.sliced() || e->pg.empty_slice) return fail(e, GNNVC_ERR_STATE, "this engine holds a slice of the graph");
     if (!in || !out) return fail(e, GNNVC_ERR_INVALID, "null host buffers");
     struct Ctx { uint32_t f; } ctx{f};
     return run_host_op(e, (size_t)n * f, in, (size_t)n * (2 * f + 3), out, false,

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gnnvc.h"
@@ -31,7 +32,6 @@ using gnnvc::GraphDev;
 using gnnvc::StagePlan;
 
 namespace gnnvc_eng {
-
 
 enum LayerKind { kLinear = 0, kGraph = 1, kRelu = 2, kSigmoid = 3 };
 
@@ -82,16 +82,13 @@ struct gnnvc_engine {
     const std::vector<StagePlan> &stage_list() const { return generic_on() ? gstages : stages; }   // what the ABI reports and runs
     // Heavy rows of generic stages (gnnvc_set_generic_heavy_rows): rows of at least heavy_from entries (0: none) get a workgroup
     // each for their sums (k_any_heavy_sums), beside or ahead of the light rows' k_stage_any.  The list and the sums are the
-    // engine's; what is known about the current graph is in pg.heavy_*.
+    // engine's; what is known about the current graph is in pg.heavy.
     uint32_t heavy_from = 512;      // the trained path's long-row threshold
-    uint32_t heavy_last_rows = 0;   // gnnvc_get_info "generic_heavy_last_rows": listed rows of the last forward / stage call (0 = one launch)
     // Giant rows of generic stages (gnnvc_set_generic_giant_rows): the listed rows of at least max(ggiant_from, heavy_from) entries
     // (0: none) take the trained path's exact parallel scan instead of k_any_heavy_sums' one chain per column: k_any_giant_gather
-    // into a slab of the engine's own (ag_* below), k_giant_segsum / k_giant_segmap / k_giant_sum, k_any_giant_place.
+    // into a slab of the engine's own (ag_* below; the classing: pg.ggiant), k_giant_segsum / k_giant_segmap / k_giant_sum, k_any_giant_place.
     uint32_t ggiant_from = 16384;   // the trained path's giant_row_threshold
     int ggiant_segments = -1;       // 1 = one stream on several waves, 0 = one wave walks each stream, -1 = by the graph (find_giant's rule)
-    uint32_t ggiant_last_rows = 0;  // "generic_giant_last_rows": giant rows of the last forward / stage call
-    bool ggiant_last_segmented = false;   // "generic_giant_last_segmented": that call used several waves per stream
     int in_width = 1, out_width = 1;
     int max_width = 1;
     bool ends_in_sigmoid = false;
@@ -107,112 +104,23 @@ struct gnnvc_engine {
     bool ev_stages = false;                  // the last forward recorded an event per stage (forward_timing 2)
 
     DevBuf<float> params;
-    // What is known about the CURRENT graph and nothing else: reset_graph_state puts a fresh one in its place, so a member
-    // added here cannot survive into the next graph.  (What a hand-off overwrites before it is read — n_long, lt_bits,
-    // sorted_wanted ... — and what is kept across graphs on purpose — t4_choice_live — is not in here.)
-    struct PerGraph {
-        bool wide_used = false;         // a stage since the hand-off ran on wide tiles
-        // the plans: built (ready) / build attempted (tried) for the current graph
-        // (the column-blocked index is built on the graph's SECOND forward: it costs about as much as it saves on one, and the
-        // reference's driver uses every graph exactly once, src/GNN_VC.cpp:171-192)
-        bool blocked_ready = false, blocked_tried = false;
-        uint32_t graph_uses = 0;        // stage-0 executions on the current graph
-        bool lt_ready = false, lt_tried = false;
-        // (round 4) the device's per-forward verdict on the byte table comes back behind whole forwards like the compact table's: an
-        // input that is not k / ws leaves the plan's launches empty and — in the skewed layout, whose rows below the giant ones are
-        // all the tile kernel's then — makes the stage several times slower than without the plan; one miss there, three on the
-        // consecutive-row layout, switch it off for the graph
-        bool lt_used = false, lt_off = false;
-        uint32_t lt_unfit_runs = 0;
-        bool c4_ready = false, c4_tried = false;
-        bool c4_range_mode = false;         // a driver asked for a range plan (gnnvc_stage_input_ready): no whole-graph plan any more
-        int c4_prepared_stage = -1;         // gnnvc_stage_input_ready: the table holds this stage's input
-        bool c4_seeded[4] = {false, false, false, false};
-        // the verdicts whole forwards copy out behind themselves (fit_pin)
-        bool fit_pending = false, fit_used[4] = {false, false, false, false}, c4_stage_off[4] = {false, false, false, false};
-        uint32_t c4_unfit_runs[4] = {0, 0, 0, 0};
-        uint32_t fit_calm = 0;              // verdicts in a row that changed nothing: from four on, only every eighth forward asks
-        uint32_t fit_skip = 0;
-        int short_from = 0;                 // the stage whose filtered call left short lists (0 = none), see short_min
-        // generic stages: the graph's heavy rows (class_heavy_rows) — known = classed, at the threshold heavy_thresh
-        bool heavy_known = false;
-        uint32_t heavy_rows = 0, heavy_thresh = 0;
-        uint64_t heavy_entries = 0;
-        // ... and the giant ones among them, classed with giant_from / giant_seg as set at the time: rows, gather blocks, segments of
-        // the longest stream (0: one wave walks each stream), the degree from which a listed row is giant (0xFFFFFFFF: none)
-        uint32_t giant_from = 0, giant_rows = 0, giant_blocks = 0, giant_maxseg = 0, giant_min = 0xFFFFFFFFu;
-        int giant_seg = -1;
-        uint64_t giant_entries = 0;
-        double plan_build_ms = 0.0;         // host wall time spent building per-graph plans for the current graph (they end in stream syncs)
-        double early_ms = 0.0;              // host time the hand-off spent classing the graph and queuing builds before the commit
-    };
-    PerGraph pg;
-    // graph
-    GraphDev g;
-    bool have_graph = false;
-    DevBuf<uint32_t> rowptr, col, w, nw;
-    // staged hand-off (gnnvc_graph_staging .. gnnvc_commit_staged_graph)
-    PinBuf<uint32_t> pin_rowptr, pin_col, pin_w, pin_nw;
-    PinBuf<uint32_t> pin_small;   // host side of small device<->host round trips
-    uint32_t staged_n = 0;
-    uint64_t staged_nnz = 0, staged_sent = 0;   // columns [0, staged_sent) are already on their way
-    bool staging = false;
-    // feature buffers
-    DevBuf<float> x, h[2], scores, logits;
-    DevBuf<float> scratch[2];  // layer-level entry points / unfused path / generic stages (ping-pong rows of up to 32 columns)
-    DevBuf<float> live_table;                 // gnnvc_set_generic_live_columns: the compact table (above)
-    DevBuf<unsigned long long> live_desc;     // ... and two words per generic stage: {mask, kept | used << 32}
-
-    // column-blocked plan of the F = 1 stage (built per graph, see gnnvc_kernels.hip)
-    uint32_t blk_count = 0, blk_cols = 0;
-    DevBuf<uint32_t> blk_ptr, blk_col, blk_scratch, blk_flag;
-    DevBuf<float> blk_acc;
-    // LDS-table plan of the F = 1 stage (same timing as the blocked plan: built on the graph's second forward)
-    uint32_t lt_bits = 8;           // width of the plan's table entries: 8, 10 or 16 bits per vertex (by the graph's largest weight)
-    bool lt_mapped = false;              // skewed graphs: rows dealt to slices (lt_rowmap), blocks of equal mass, rows below lt_plan_thresh
-    uint32_t lt_plan_thresh = 0xFFFFFFFFu;
-    DevBuf<uint32_t> lt_rowmap, lt_first, lt_bstart;
-    uint32_t lt_rows = 0, lt_chunks = 0, lt_blocks = 0, lt_steps_total = 0, lt_last_entry = 0;
-    uint32_t lt_base = 0, lt_end = 0;       // the plan's row range: the rows this engine holds when it was built
-    // A plan being put together (round 3).  The expensive passes — counting and regrouping a slice's entries by column block —
-    // need nothing but that slice's rows, so a hand-off runs them piece by piece on the second stream while the rest of the
-    // column array is still crossing the bus (flat layouts: consecutive rows, uniform blocks); begin = eligibility, geometry,
-    // buffers; advance = count + regroup the slices up to a given one; finish = the step records (they need every slice's
-    // counts) and the verdict.
+    // Every member has one of three lifetimes, and where it is declared says which.  The ENGINE's: the model, options, streams and
+    // events above and, below Call, every DevBuf / PinBuf, one struct per owner (blk, lt, c4, t4, srt, gi, prune_buf ...: buffers keep
+    // their capacity across graphs on purpose), plus what is carried across graphs by design, each with its reason.  The RESIDENT
+    // GRAPH's: PerGraph, a nested struct per owner, plain data without a buffer handle — reset_graph_state assigns a fresh one and
+    // does nothing else, and each owner's builder (find_long, prepare_table_tiles, lt_begin, c4_begin, class_heavy_rows) begins by
+    // assigning its own struct.  The CALL's or forward's at hand: Call, never reset as a whole (find_long and c4_begin restart
+    // the member each owns: srt_cur, c4_emit_zero).
+    //
+    // A plan being put together (round 3): the expensive passes — counting and regrouping a slice's entries by column block — need
+    // nothing but that slice's rows, so a hand-off runs them piece by piece on the second stream while the rest of the column array
+    // is still crossing the bus (flat layouts only); begin / advance / finish: see lt_begin .. c4_finish below.
     struct PlanBuild {
         bool open = false, mapped = false;
         uint32_t base = 0, end = 0, slice_rows = 0, slices = 0, chunks = 0, rows = 0, nblocks = 0, bc = 0, slack = 0, done = 0;
-        uint32_t plan_rows = 0, passes = 1;
         uint64_t entry_cap = 0, plan_nnz = 0;
         gnnvc::PlanMap pm;
     };
-    PlanBuild lt_pb, c4_pb;
-    // a host hand-off in progress whose plans are being built while the column array arrives (handoff_early / handoff_progress)
-    bool early_open = false, early_declined = false;
-    gnnvc::Event ev_piece;
-    DevBuf<uint8_t> lt_bytes;
-    DevBuf<uint32_t> lt_entries, lt_segcnt, lt_stepptr, lt_stepcnt, lt_bad;
-    DevBuf<uint4> lt_steps;
-    // compact-table plan of the 16-wide stages (built like the LDS-table plan, on the graph's second forward)
-    uint32_t c4_rows = 0, c4_chunks = 0, c4_steps_total = 0, c4_block = 0, c4_last_entry = 0, c4_nblocks = 0;
-    DevBuf<uint32_t> c4_entries, c4_segcnt, c4_stepptr, c4_stepcnt, c4_desc;
-    uint32_t c4_nslices = 0;
-    DevBuf<uint32_t> c4_map_vertex;   // (scratch of layout_skewed_plan: the LDS-table plan's layout on skewed graphs)
-    DevBuf<uint32_t> map_coarse;      // uint16 per 256 columns: their block (scratch of the skewed-graph plan builders)
-    DevBuf<uint4> c4_map_meta;
-    DevBuf<uint4> c4_steps;
-    DevBuf<float> c4_table, c4_acc, c4_agg16;
-    DevBuf<uint32_t> c4_round_counts;     // next dirty-row slot of each round of the aggregation grid (compact_rounds() words; set by k_c4_choose)
-    std::vector<gnnvc::Event> round_ev;    // "round k's sums are done" (main stream -> aux stream)
-    DevBuf<uint32_t> c4_dirty;
-    uint32_t c4_dirty_cap = 0;
-    DevBuf<unsigned long long> c4_counts, c4_emit_counts;
-    uint32_t plan_memsets = 0;            // memsets the plans' launches queued between kernels since the last whole forward began
-                                          // (gnnvc_get_info "plan_memsets_last_forward": 1 in a steady forward on the plans, the LDS table's flag)
-    bool c4_emit_zero = false;            // the last thing queued on c4_emit_counts was a k_c4_choose that clears them behind its read
-    uint32_t c4_base = 0, c4_end = 0;   // the plan's row range: the whole graph, or the rows a multi-GPU rank computes
-    const float *c4_prepared_in = nullptr;   // gnnvc_stage_input_ready: the table's input (pg.c4_prepared_stage) as found at this address
-    int c4_fused_for = -1;          // stage whose input statistics (and table) the previous stage kernel of this forward produced
     // pruned adjacency of the 16-wide stages (kernels: k_prune_*), one per consumer stage: built from the input the stage
     // sees the second time the graph is scored; every later call proves on the device that its input still fits
     struct PrunePlan {
@@ -222,93 +130,177 @@ struct gnnvc_engine {
         // verified: a forward has run with it and the host has seen that its check passed (if not, the plan is dropped and
         // rebuilt from the input the stage really sees)
         bool predicted = false, verified = false;
-        void forget() { tried = ready = deferred = predicted = verified = false; }
         bool from_prev = false;             // built from the previous stage's kept entries (its set is contained in this one)
         uint64_t kept = 0;                  // entries left
         uint64_t members = 0;               // vertices in the set
-        DevBuf<uint32_t> prp, pcol, heavy;
-        DevBuf<uint32_t> svertex;            // skewed graphs: the engine's rows below the long-row threshold BY ENTRIES LEFT, heaviest first
-        DevBuf<uint4> smeta;                 // ... with their pruned ranges
-        uint32_t sn = 0;
+        uint32_t sn = 0;                    // rows of the list in PruneBufs::svertex
         bool slist = false;
         uint32_t eff_thresh = 0xFFFFFFFFu;   // entries left from which a row goes to the long-row kernel
     };
-    PrunePlan prune[4];
-    DevBuf<uint32_t> prune_flags, prune_scratch, prune_off;   // (off / mask: per chunk of 64 entries, while a plan is built)
-    DevBuf<unsigned long long> prune_mask;   // flags: [stage] = this call's verdict (0 = the pruned adjacency applies), [3] = observe
-    int side_join = 0;               // what the stage at hand joins on: 0 nothing, 1 the long rows' queue, 2 the giant rows' queue
-    // Filtered gather: while a skewed graph's 16-wide stage has no pruned adjacency (the graph's first forward: the reference's
-    // driver never comes back for a second), its kernels look every entry's target up in the bitmap of THIS input's all-zero
-    // rows, written just before them, and fetch the pad row instead (GraphDev::zero_bits; nothing to build, nothing to prove).
-    DevBuf<uint32_t> filter_bits[4];
-    DevBuf<unsigned long long> filter_info;   // [4 * stage]: {degrees of the set's vertices, their number, verdict on an earlier stage's lists}
-    bool filtered[4] = {false, false, false, false};   // the last call of the stage was offered the bitmap
-    bool borrowed[4] = {false, false, false, false};   // the last call of the stage ran on the PREVIOUS stage's predicted plan (gather_view)
-    // ... and the targets a filtered stage found outside its set, left per row in prune[stage].pcol / .prp (the buffers of the
-    // plan that is not built yet), are the adjacency of the NEXT 16-wide stage of the same forward when the device finds that
-    // stage's input to keep the set all zero (GraphDev::keep_col / short_col): pg.short_from = the stage that left them, 0 = none
-    uint32_t short_min = 0, short_max = 0;   // the degrees [min, max) of the rows that have a list
-    bool short_used[4] = {false, false, false, false};   // the last call of the stage was offered an earlier stage's lists
-    // Does the device keep finding a stage's input unfit for the plan (more than its tables' columns live: low-degree graphs)?
-    // Whole forwards copy the verdicts out behind themselves; three misses in a row switch the plan off for that stage of this
-    // graph — its counting, choosing and empty launches cost up to 17 % of a forward that then gathers anyway.
-    PinBuf<uint32_t> fit_pin;
-    gnnvc::Event ev_fit;
-    int c4_last_desc = 0;           // word offset in c4_desc of the plan's last launch (tests / tools)
-    static constexpr int kDescWords = 16;   // per consumer stage (see k_c4_choose); the build flag follows the last stage's
-
-    // Table tiles (round 4; k_stage_t4): graphs too small for the compact-table plan and too large for their feature rows to sit in
-    // an L2 (50 - 400 K vertices: BASELINE configs[1]) gather the 16-wide stages' neighbours from the 16-byte compact table of the
-    // input — written by the kernel that produces the input, for the columns the previous forward chose — inside whole forwards.
-    bool t4_ok = false;                      // the current graph qualifies
-    bool t4_used = false;                    // the forward whose verdicts are on their way ran with the table tiles offered
-    bool t4_fit_seen[4] = {false, false, false, false};   // the stage's table fit in the last forward whose verdict has arrived
-    uint32_t t4_unfit_runs = 0;              // forwards in a row whose first 16-wide stage left the launch to the gathering kernel
-    uint32_t *fit_dev = nullptr;             // fit_pin as the device sees it (the verdict words are WRITTEN there by one small kernel)
-    bool t4_now = false;                     // the forward at hand runs with the table tiles offered
-    bool t4_choice_live = false;             // a forward with table tiles has run on this engine: the descriptors hold a choice (kept across graphs)
-    uint32_t t4_parity = 0;                  // which of a stage's two descriptors the producers read in the forward at hand
-    DevBuf<float> t4_table[2];               // [0]: the table of stage 1's input, [1]: of stage 2's (a stage gathers from one while emitting the other)
-    DevBuf<uint32_t> t4_desc;                // [stage - 1][parity][16 words]
-    DevBuf<unsigned long long> t4_counts[2]; // the producers' per-column counters: [stage - 1], two sets of kEmitCounters each (by parity, like the descriptors)
-    unsigned long long *t4_counts_of(int stage, uint32_t parity) { return t4_counts[stage - 1].p + (size_t)parity * gnnvc::kEmitCounters; }
-    uint32_t *t4_desc_of(int stage, uint32_t parity) { return t4_desc.p + ((size_t)(stage - 1) * 2 + parity) * 16; }
-
-    // degree-sorted tile order (16-wide stages, skewed graphs); built per row range on demand
-    uint32_t thresh_f16 = 0xFFFFFFFFu;        // rows >= this go to k_long_f16 (>= long_thresh, the list's threshold)
-    bool interleave = false;           // deal natural tiles round-robin (work is unevenly spread over the row range)
-    bool sorted_wanted = false;        // decided per graph from the measured tile waste
-    // A few row ranges are cached: a vertex-partitioned caller alternates between its own rows and (for a replicated
-    // stage) the whole graph, or between the pieces of a pipelined stage — each range is sorted once per graph.
+    // A few row ranges of the degree-sorted tile order are cached: a vertex-partitioned caller alternates between its own rows and
+    // (for a replicated stage) the whole graph, or between the pieces of a pipelined stage — each range is sorted once per graph.
     struct SortedRange {
         bool valid = false, use = false;
         uint32_t lo = 0, hi = 0, n = 0;
         uint64_t stamp = 0;
-        DevBuf<uint32_t> vertex;
-        DevBuf<uint4> meta;
     };
     static constexpr int kSortedRanges = 6;
-    SortedRange srt[kSortedRanges];
-    int srt_cur = -1;                  // the entry ensure_sorted selected for the call in progress
-    uint64_t srt_clock = 0;
-    double srt_waste = 0.0, srt_tail = 0.0;
-    DevBuf<uint32_t> srt_hist;
-    DevBuf<unsigned long long> srt_sum;
+    struct PerGraph {
+        uint32_t graph_uses = 0;        // stage-0 executions on the current graph
+        bool wide_used = false;         // a stage since the hand-off ran on wide tiles
+        // memsets the plans' launches queued between kernels since the last whole forward on this graph began (gnnvc_get_info
+        // "plan_memsets_last_forward": 1 in a steady forward on the plans, the LDS table's flag; no forward on this graph yet: 0)
+        uint32_t plan_memsets = 0;
+        double plan_build_ms = 0.0;     // host wall time spent building per-graph plans for the current graph (they end in stream syncs)
+        double early_ms = 0.0;          // host time the hand-off spent classing the graph and queuing builds before the commit
+        double handoff_build_ms = 0.0;  // ... and prepare_plans' share of plan_build_ms
+        bool empty_slice = false;       // gnnvc_attach_graph_slice with no rows: every stage call is a no-op
+        // the next graph derived from this one (gnnvc_derive_graph_begin / _commit); every hand-off ends an open derivation
+        bool der_open = false;
+        uint32_t der_n_new = 0;
+        uint64_t der_nnz_new = 0, der_tail_total = 0;
+        // row classes (find_long / find_giant).  Long rows (degree >= long_thresh): one workgroup each, on aux_stream beside the
+        // tile kernel; giant rows (degree >= giant_thresh, a subset of them): CSR-order sums evaluated in parallel (exact_sum.h)
+        struct Rows {
+            uint32_t n_long = 0, long_thresh = 0xFFFFFFFFu;
+            uint32_t thresh_f16 = 0xFFFFFFFFu;   // 16-wide stages: rows >= this go to k_long_f16 (>= long_thresh, the list's threshold)
+            uint64_t long_entries = 0;           // entries of the listed rows
+            uint32_t n_giant = 0, giant_thresh = 0xFFFFFFFFu, giant_blocks = 0, maxseg = 0;
+            uint64_t giant_entries = 0;
+            bool giant_walk_bound = false;       // (walk_bound: the longest stream's walk is what a stage waits for, find_giant)
+            bool interleave = false;             // deal natural tiles round-robin (work is unevenly spread over the row range)
+            bool sorted_wanted = false;          // degree-sorted tile order, decided from the measured tile waste
+            double waste = 0.0, tail = 0.0;
+        } rows;
+        SortedRange sorted[kSortedRanges];       // (the lists themselves: srt.range[])
+        // column-blocked plan of the F = 1 stage: built (ready) / build attempted (tried) — on the graph's SECOND forward: it costs
+        // about as much as it saves on one, and the reference's driver uses every graph exactly once, src/GNN_VC.cpp:171-192
+        struct Blk {
+            bool ready = false, tried = false;
+            uint32_t count = 0, cols = 0;
+        } blk;
+        // LDS-table plan of the F = 1 stage (same timing as the blocked plan).  LtPlan is what lt_begin starts afresh ...
+        struct LtPlan {
+            bool ready = false, tried = false;
+            uint32_t bits = 8;              // width of the plan's table entries: 8, 10 or 16 bits per vertex (by the graph's largest weight)
+            bool mapped = false;            // skewed graphs: rows dealt to slices (lt.rowmap), blocks of equal mass, rows below plan_thresh
+            uint32_t plan_thresh = 0xFFFFFFFFu;
+            uint32_t rows = 0, chunks = 0, blocks = 0, steps_total = 0, last_entry = 0;
+            uint32_t base = 0, end = 0;     // the plan's row range: the rows this engine holds when it was built
+            PlanBuild pb;
+        };
+        // ... and the rest outlives a rebuild on the same graph.  (round 4) The device's per-forward verdict on the byte table comes
+        // back behind whole forwards like the compact table's: an input that is not k / ws leaves the plan's launches empty and — in
+        // the skewed layout, whose rows below the giant ones are all the tile kernel's then — makes the stage several times slower
+        // than without the plan; one miss there, three on the consecutive-row layout, switch it off for the graph
+        struct Lt : LtPlan {
+            bool used = false, off = false;
+            uint32_t unfit_runs = 0;
+        } lt;
+        // compact-table plan of the 16-wide stages (built like the LDS-table plan); C4Plan is what c4_begin starts afresh
+        struct C4Plan {
+            bool ready = false, tried = false;
+            int prepared_stage = -1;             // gnnvc_stage_input_ready: the table holds this stage's input ...
+            const float *prepared_in = nullptr;  // ... as found at this address
+            bool seeded[4] = {false, false, false, false};
+            uint32_t rows = 0, chunks = 0, steps_total = 0, block = 0, last_entry = 0, nblocks = 0, nslices = 0;
+            uint32_t base = 0, end = 0;          // the plan's row range: the whole graph, or the rows a multi-GPU rank computes
+            uint32_t dirty_cap = 0;
+            PlanBuild pb;
+        };
+        // Does the device keep finding a stage's input unfit for the plan (more than its tables' columns live: low-degree graphs)?
+        // Whole forwards copy the verdicts out behind themselves (fit_pin); three misses in a row switch the plan off for that stage
+        // of this graph — its counting, choosing and empty launches cost up to 17 % of a forward that then gathers anyway.
+        struct C4 : C4Plan {
+            bool range_mode = false;             // a driver asked for a range plan (gnnvc_stage_input_ready): no whole-graph plan any more
+            bool fit_pending = false, fit_used[4] = {false, false, false, false}, stage_off[4] = {false, false, false, false};
+            uint32_t unfit_runs[4] = {0, 0, 0, 0};
+            uint32_t fit_calm = 0;               // verdicts in a row that changed nothing: from four on, only every eighth forward asks
+            uint32_t fit_skip = 0;
+            int last_desc = 0;                   // word offset in c4.desc of the plan's last launch (tests / tools)
+        } c4;
+        // Table tiles (round 4; k_stage_t4): graphs too small for the compact-table plan and too large for their feature rows to sit
+        // in an L2 (50 - 400 K vertices: BASELINE configs[1]) gather the 16-wide stages' neighbours from the 16-byte compact table of
+        // the input — written by the kernel that produces the input, for the columns the previous forward chose — inside whole forwards.
+        struct T4 {
+            bool ok = false;                     // the current graph qualifies
+            bool used = false;                   // the forward whose verdicts are on their way ran with the table tiles offered
+            bool fit_seen[4] = {false, false, false, false};   // the stage's table fit in the last forward whose verdict has arrived
+            uint32_t unfit_runs = 0;             // forwards in a row whose first 16-wide stage left the launch to the gathering kernel
+        } t4;
+        PrunePlan prune[4];
+        // Filtered gather: while a skewed graph's 16-wide stage has no pruned adjacency (the graph's first forward: the reference's
+        // driver never comes back for a second), its kernels look every entry's target up in the bitmap of THIS input's all-zero
+        // rows, written just before them, and fetch the pad row instead (GraphDev::zero_bits; nothing to build, nothing to prove).
+        struct Filter {
+            bool filtered[4] = {false, false, false, false};   // the last call of the stage was offered the bitmap
+            bool borrowed[4] = {false, false, false, false};   // the last call of the stage ran on the PREVIOUS stage's predicted plan (gather_view)
+            // ... and the targets a filtered stage found outside its set, left per row in prune_buf[stage].pcol / .prp (the buffers of
+            // the plan that is not built yet), are the adjacency of the NEXT 16-wide stage of the same forward when the device finds
+            // that stage's input to keep the set all zero (GraphDev::keep_col / short_col)
+            bool short_used[4] = {false, false, false, false};   // the last call of the stage was offered an earlier stage's lists
+            uint32_t short_min = 0, short_max = 0;   // the degrees [min, max) of the rows that have a list
+            int short_from = 0;                  // the stage whose filtered call left them (0 = none)
+        } filter;
+        // generic stages: the graph's heavy rows (class_heavy_rows) — known = classed, at the threshold thresh
+        struct Heavy {
+            bool known = false;
+            uint32_t rows = 0, thresh = 0;
+            uint64_t entries = 0;
+        } heavy;
+        // ... and the giant ones among them, classed with from / seg as set at the time: rows, gather blocks, segments of the
+        // longest stream (0: one wave walks each stream), the degree from which a listed row is giant (0xFFFFFFFF: none)
+        struct GGiant {
+            uint32_t from = 0, rows = 0, blocks = 0, maxseg = 0, min = 0xFFFFFFFFu;
+            int seg = -1;
+            uint64_t entries = 0;
+        } ggiant;
+    };
+    PerGraph pg;
+    uint32_t giant_f16() const {
+        if (!pg.rows.n_giant) return 0xFFFFFFFFu;
+        // by the graph: a 65 536-entry row's add chain in k_long_f16 is ~0.26 ms — lost in the stages of a graph with 64 M entries
+        // and more (R-MAT-22 2.98 -> 2.88 ms, R-MAT-24 12.6 -> 11.6 ms), what the stages of a smaller one would wait for (R-MAT-20
+        // 0.99 -> 1.05 ms, power-law 1.03 -> 1.30 ms).  (16 streams per row: three times a long row's traffic — worth it only for
+        // the rows whose add chain a stage would wait for)
+        if (opt.giant_f16_auto && g.nnz < (64ull << 20)) return pg.rows.giant_thresh;
+        return std::max(pg.rows.giant_thresh, opt.giant_f16);
+    }
 
-    // long rows (degree >= long_thresh): one workgroup each, on aux_stream beside the tile kernel
-    uint32_t long_thresh = 0xFFFFFFFFu, n_long = 0;
-    DevBuf<uint32_t> long_list, long_count;
-    // generic stages' heavy rows (heavy_from above): find_long_rows' list and count words, and the sums — rows x the widest stage input
-    DevBuf<uint32_t> heavy_list, heavy_count;
-    DevBuf<float> heavy_sum;
-    // generic stages' giant rows: {row, first entry, degree, first gather block} heaviest first, each row's slab offset and position
-    // in heavy_list, the slab (per row: the widest stage input x the degree rounded up to giant_window() floats), the aggregates
-    // (rows x f of the stage at hand) and, with several waves per stream, the segments' sums and maps.  Not the trained path's gi_*.
-    DevBuf<uint4> ag_meta, ag_segmap;
-    DevBuf<unsigned long long> ag_off;
-    DevBuf<uint32_t> ag_pos;
-    DevBuf<float> ag_slab, ag_agg, ag_segsum;
-    // what classify_hand_off learned about a graph in its one round trip, for the find_long that follows it
+    // the call's or forward's at hand: written by the call that reads it; no hand-off resets them (the read-outs below outlive one)
+    struct AuditCheck {
+        int stage;
+        uint32_t lo, hi;
+        std::string plan;                    // what produced the stage (StageChoice, views, side queues)
+    };
+    struct Call {
+        int c4_fused_for = -1;          // stage whose input statistics (and table) the previous stage kernel of this forward produced
+        bool c4_emit_zero = false;      // the last thing queued on c4.emit_counts was a k_c4_choose that clears them behind its read
+        int side_join = 0;              // what the stage at hand joins on: 0 nothing, 1 the long rows' queue, 2 the giant rows' queue
+        bool stage_wide = false;        // the last launch_main ran the stage on wide tiles (audit reports)
+        int srt_cur = -1;               // the entry of pg.sorted ensure_sorted selected for the call in progress
+        bool t4_now = false;            // the forward at hand runs with the table tiles offered
+        uint32_t heavy_last_rows = 0;   // gnnvc_get_info "generic_heavy_last_rows": listed rows of the last forward / stage call (0 = one launch)
+        uint32_t ggiant_last_rows = 0;  // "generic_giant_last_rows": giant rows of the last forward / stage call
+        bool ggiant_last_segmented = false;   // "generic_giant_last_segmented": that call used several waves per stream
+        bool audit_now = false;         // the call at hand is audited
+        std::vector<AuditCheck> audit_pending;   // the checks of the call at hand: record i of audit_rec is check i's
+    };
+    Call call;
+
+    // the engine's again.  The resident graph itself: every hand-off writes g / have_graph before it resets pg
+    GraphDev g;
+    bool have_graph = false;
+    DevBuf<uint32_t> rowptr, col, w, nw;
+    // staged hand-off (gnnvc_graph_staging .. gnnvc_commit_staged_graph)
+    PinBuf<uint32_t> pin_rowptr, pin_col, pin_w, pin_nw;
+    PinBuf<uint32_t> pin_small;   // host side of small device<->host round trips
+    // What describes a CANDIDATE graph on its way in and is consumed by its hand-off: the staging counters; early_* (handoff_early:
+    // plans begun while the column array arrives; set while pg still describes the previous graph); pre / pre_armed (below)
+    uint32_t staged_n = 0;
+    uint64_t staged_nnz = 0, staged_sent = 0;   // columns [0, staged_sent) are already on their way
+    bool staging = false;
+    bool early_open = false, early_declined = false;
     struct PreClass {
         bool valid = false, cuts = false, waste = false, longs = false;
         uint32_t lo = 0, hi = 0, waste_thresh = 0, heavy_from = 0, long_thresh = 0;
@@ -320,7 +312,88 @@ struct gnnvc_engine {
     DevBuf<uint32_t> cls_dev;                // classify_graph's 16 words of device scratch
     PinBuf<uint32_t> cls_pin;                // ... and its 24 result words
     uint32_t *cls_pin_dev = nullptr;
-    uint64_t long_entries = 0;       // entries of the listed rows
+    gnnvc::Event ev_piece;
+    // the next graph derived from the resident one (pg.der_*)
+    DevBuf<uint32_t> rowptr2, col2, der_old_row, der_new_of, der_tail, der_tailptr, der_tailcols;
+    DevBuf<unsigned long long> hash_buf;
+    std::vector<uint32_t> der_tail_host;
+    // feature buffers
+    DevBuf<float> x, h[2], scores, logits;
+    DevBuf<float> scratch[2];  // layer-level entry points / unfused path / generic stages (ping-pong rows of up to 32 columns)
+    DevBuf<float> live_table;                 // gnnvc_set_generic_live_columns: the compact table (above)
+    DevBuf<unsigned long long> live_desc;     // ... and two words per generic stage: {mask, kept | used << 32}
+    struct BlockedBufs {   // column-blocked plan (pg.blk; see gnnvc_kernels.hip)
+        DevBuf<uint32_t> ptr, col, scratch, flag;
+        DevBuf<float> acc;
+    } blk;
+    struct LdsTableBufs {   // LDS-table plan (pg.lt)
+        DevBuf<uint32_t> rowmap, first, bstart;
+        DevBuf<uint8_t> bytes;
+        DevBuf<uint32_t> entries, segcnt, stepptr, stepcnt, bad;
+        DevBuf<uint4> steps;
+        // scratch of layout_skewed_plan (skewed graphs): the degree-sorted row list, released behind the dealing, and coarse = a
+        // uint16 per 256 columns, their block
+        DevBuf<uint32_t> skew_vertex, skew_coarse;
+        DevBuf<uint4> skew_meta;
+    } lt;
+    struct CompactBufs {   // compact-table plan (pg.c4)
+        DevBuf<uint32_t> entries, segcnt, stepptr, stepcnt, desc;
+        DevBuf<uint4> steps;
+        DevBuf<float> table, acc, agg16;
+        DevBuf<uint32_t> round_counts;     // next dirty-row slot of each round of the aggregation grid (compact_rounds() words; set by k_c4_choose)
+        DevBuf<uint32_t> dirty;
+        DevBuf<unsigned long long> counts, emit_counts;
+    } c4;
+    std::vector<gnnvc::Event> round_ev;    // "round k's sums are done" (main stream -> aux stream)
+    static constexpr int kDescWords = 16;   // per consumer stage (see k_c4_choose); the build flag follows the last stage's
+    PinBuf<uint32_t> fit_pin;                // the verdicts whole forwards copy out behind themselves (pg.c4.fit_*, pg.lt, pg.t4)
+    uint32_t *fit_dev = nullptr;             // fit_pin as the device sees it (the verdict words are WRITTEN there by one small kernel)
+    gnnvc::Event ev_fit;
+    struct PruneBufs {   // pruned adjacency (pg.prune[])
+        DevBuf<uint32_t> prp, pcol, heavy;
+        DevBuf<uint32_t> svertex;            // skewed graphs: the engine's rows below the long-row threshold BY ENTRIES LEFT, heaviest first
+        DevBuf<uint4> smeta;                 // ... with their pruned ranges
+    } prune_buf[4];
+    DevBuf<uint32_t> prune_flags, prune_scratch, prune_off;   // (off / mask: per chunk of 64 entries, while a plan is built)
+    DevBuf<unsigned long long> prune_mask;   // flags: [stage] = this call's verdict (0 = the pruned adjacency applies), [3] = observe
+    DevBuf<uint32_t> filter_bits[4];          // filtered gather (pg.filter)
+    DevBuf<unsigned long long> filter_info;   // [4 * stage]: {degrees of the set's vertices, their number, verdict on an earlier stage's lists}
+    struct TableTileBufs {   // table tiles (pg.t4)
+        // Carried across graphs by design (prepare_table_tiles says why): choice_live = a forward with table tiles has run on this
+        // engine, the descriptors hold a choice; parity = which of a stage's two descriptors the producers read in the forward at hand
+        bool choice_live = false;
+        uint32_t parity = 0;
+        DevBuf<float> table[2];               // [0]: the table of stage 1's input, [1]: of stage 2's (a stage gathers from one while emitting the other)
+        DevBuf<uint32_t> desc;                // [stage - 1][parity][16 words]
+        DevBuf<unsigned long long> counts[2]; // the producers' per-column counters: [stage - 1], two sets of kEmitCounters each (by parity, like the descriptors)
+        unsigned long long *counts_of(int stage, uint32_t par) { return counts[stage - 1].p + (size_t)par * gnnvc::kEmitCounters; }
+        uint32_t *desc_of(int stage, uint32_t par) { return desc.p + ((size_t)(stage - 1) * 2 + par) * 16; }
+    } t4;
+    struct SortedBufs {   // degree-sorted tile order (16-wide stages, skewed graphs); built per row range on demand (pg.sorted[])
+        struct {
+            DevBuf<uint32_t> vertex;
+            DevBuf<uint4> meta;
+        } range[kSortedRanges];
+        uint64_t clock = 0;                // stamps only order the ranges of one graph: it may run on
+        DevBuf<uint32_t> hist;
+        DevBuf<unsigned long long> sum;
+    } srt;
+    DevBuf<uint32_t> long_list, long_count;   // long rows (pg.rows)
+    struct GiantBufs {   // giant rows (pg.rows): (segsum / segmap: one stream on several waves, see k_giant_segmap)
+        DevBuf<uint4> meta, segmap;
+        DevBuf<unsigned long long> off;
+        DevBuf<float> slab, agg, segsum;
+    } gi;
+    // generic stages' heavy rows (heavy_from above): find_long_rows' list and count words, and the sums — rows x the widest stage input
+    DevBuf<uint32_t> heavy_list, heavy_count;
+    DevBuf<float> heavy_sum;
+    // generic stages' giant rows: {row, first entry, degree, first gather block} heaviest first, each row's slab offset and position
+    // in heavy_list, the slab (per row: the widest stage input x the degree rounded up to giant_window() floats), the aggregates
+    // (rows x f of the stage at hand) and, with several waves per stream, the segments' sums and maps.  Not the trained path's gi.
+    DevBuf<uint4> ag_meta, ag_segmap;
+    DevBuf<unsigned long long> ag_off;
+    DevBuf<uint32_t> ag_pos;
+    DevBuf<float> ag_slab, ag_agg, ag_segsum;
     gnnvc::Event ev_fork, ev_join;
     // (the long rows' and the giant rows' stream handles: the side queue again, not owned — ensure_side_streams — with join events of their own)
     hipStream_t long_stream = nullptr;
@@ -329,55 +402,23 @@ struct gnnvc_engine {
     bool side_beside = false;        // ... and whether one did (info "side_queue_runs_beside")
     hipStream_t giant_stream = nullptr;  // giant rows: three dependent launches, the side work's long pole -> a high-priority stream of its own
     gnnvc::Event ev_giant;
-    // giant rows (degree >= giant_thresh, a subset of the long rows): CSR-order sums evaluated in parallel (exact_sum.h)
     gnnvc::KernelTraceSink ktrace;
-    // the next graph derived from the resident one (gnnvc_derive_graph_begin / _commit)
-    DevBuf<uint32_t> rowptr2, col2, der_old_row, der_new_of, der_tail, der_tailptr, der_tailcols;
-    DevBuf<unsigned long long> hash_buf;
-    std::vector<uint32_t> der_tail_host;
-    uint32_t der_n_new = 0;
-    uint64_t der_nnz_new = 0, der_tail_total = 0;
-    bool der_open = false;
-    bool empty_slice = false;            // gnnvc_attach_graph_slice with no rows: every stage call is a no-op
-    uint32_t giant_thresh = 0xFFFFFFFFu, n_giant = 0, giant_blocks = 0;
-    bool giant_walk_bound = false;   // (walk_bound: the longest stream's walk is what a stage waits for, find_giant)
-    uint32_t giant_f16() const {
-        if (!n_giant) return 0xFFFFFFFFu;
-        // by the graph: a 65 536-entry row's add chain in k_long_f16 is ~0.26 ms — lost in the stages of a graph with 64 M entries
-        // and more (R-MAT-22 2.98 -> 2.88 ms, R-MAT-24 12.6 -> 11.6 ms), what the stages of a smaller one would wait for (R-MAT-20
-        // 0.99 -> 1.05 ms, power-law 1.03 -> 1.30 ms)
-        if (opt.giant_f16_auto && g.nnz < (64ull << 20)) return giant_thresh;
-        return std::max(giant_thresh, opt.giant_f16);
-    }   // (16 streams per row: three times a
-                                        // long row's traffic — worth it only for the rows whose add chain a stage would wait for)
-    uint64_t giant_entries = 0;
-    DevBuf<uint4> gi_meta;
-    DevBuf<unsigned long long> gi_off;
-    DevBuf<float> gi_slab, gi_agg, gi_segsum;   // (segsum / segmap: one stream on several waves, see k_giant_segmap)
-    DevBuf<uint4> gi_segmap;
-    uint32_t gi_maxseg = 0;
     PinBuf<uint32_t> pin_info;   // small device -> host results that outlive the call that asked for them (never reallocated)
     DevBuf<uint32_t> dev_info;
-    double handoff_build_ms = 0.0;
 
-    // on-device audit (options "audit_*", gnnvc_options.h)
+    // on-device audit (options "audit_*", gnnvc_options.h): counters since the engine was made
     uint64_t audit_calls = 0;                // forward entry-point calls since the period was set
-    bool audit_now = false;                  // the call at hand is audited
-    struct AuditCheck {
-        int stage;
-        uint32_t lo, hi;
-        std::string plan;                    // what produced the stage (StageChoice, views, side queues)
-    };
-    std::vector<AuditCheck> audit_pending;   // the checks of the call at hand: record i of audit_rec is check i's
     DevBuf<unsigned long long> audit_rec;
     PinBuf<unsigned long long> audit_pin;
     uint64_t audit_runs = 0, audit_failures = 0, audit_repairs = 0, audit_nan_pairs = 0;
     long audit_last_stage = -1, audit_last_row = -1, audit_last_col = -1, audit_last_mismatches = 0;
     uint32_t audit_last_fused = 0, audit_last_plain = 0;
-    bool stage_wide = false;                 // the last launch_main ran the stage on wide tiles (audit reports)
 
     std::string err;
 };
+
+static_assert(std::is_trivially_destructible_v<gnnvc_engine::PerGraph>);   // e->pg = PerGraph{} can neither free nor leak anything
+static_assert(std::is_trivially_copyable_v<gnnvc_engine::PerGraph>);
 
 namespace gnnvc_eng {
 

@@ -32,7 +32,7 @@ AT_HANDOFF = ["long_rows", "giant_rows", "giant_entries", "giant_segments", "lds
 AFTER_FORWARDS = ["wide_tiles_used", "lds_table_last_ok", "compact_gather_last_ok", "pruned_last_ok_stage1", "pruned_entries_stage1",
                   "table_tiles_fit_stage1", "table_tiles_fit_stage2"]
 FORWARDS_BEFORE_READOUT = 3
-# What an engine keeps across graphs on purpose (gnnvc_engine_state.h: t4_choice_live): once a forward has run on table tiles, the
+# What an engine keeps across graphs on purpose (gnnvc_engine_state.h: t4.choice_live): once a forward has run on table tiles, the
 # next graph that qualifies for them is offered them from its FIRST forward, on the columns chosen last, where a fresh engine's first
 # forward runs without (on wide tiles, up to "wide_tiles_max_n_f16" vertices) and its tiles fit a forward later.  Same bits either
 # way; these read-outs of the first three forwards are then not a fresh engine's, and are left out of both state checks for a
