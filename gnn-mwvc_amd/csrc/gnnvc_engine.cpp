@@ -1223,6 +1223,7 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
         if (!gnnvc::multi_sum_info(e->multi, key, value)) return GNNVC_ERR_INVALID;
     }
     else if (k == "generic_stages" || k == "plans_at_handoff" || k == "mfma_dense") (void)gnnvc::read_option(e->opt, key, value);   // (as set)
+    else if (backward_info(e, k, value)) {}   // the backward pass's read-outs, spelled out where it lives (gnnvc_backward.cpp)
     else if (k == "generic_stages_model") *value = e->generic_on() ? 1 : 0;   // would a forward run k_stage_any now
     else if (k == "generic_stages_active") *value = e->generic_ran ? 1 : 0;   // did the last one
     else if (k == "generic_max_dense_layers") *value = gnnvc::kMaxDenseLayers;

@@ -4,6 +4,7 @@
 //   gnnvc_plans.cpp   what is built per GRAPH: row classes (long / giant rows, tile order), the LDS-table, compact-table and
 //                     column-blocked plans, the pruned adjacency, and when (hand-off / first forwards)
 //   gnnvc_multi.cpp   several devices behind one handle (public ABI only)
+//   gnnvc_backward.cpp the backward pass: training forward, model- and layer-level backward (kernels: gnnvc_backward.hip)
 //   gnnvc_kernels.hip the gfx950 kernels and their launchers
 //   gnnvc_device_mem.h the owning handles every buffer, event and stream below is held by (DevBuf, PinBuf, Event, Stream)
 //   gnnvc_options.h   what gnnvc_set_option sets (gnnvc_engine::opt) and the table of its keys — no HIP in it
@@ -255,6 +256,12 @@ struct gnnvc_engine {
             int seg = -1;
             uint64_t entries = 0;
         } ggiant;
+        // backward pass (gnnvc_backward.cpp): symmetric = is the adjacency symmetric with multiplicities (-1: not checked yet; the
+        // check runs once per resident graph, on the device); saved = the engine's train buffers hold a training forward on THIS graph
+        struct Train {
+            int symmetric = -1;
+            bool saved = false;
+        } train;
     };
     PerGraph pg;
     uint32_t giant_f16() const {
@@ -402,8 +409,24 @@ struct gnnvc_engine {
     bool side_beside = false;        // ... and whether one did (info "side_queue_runs_beside")
     hipStream_t giant_stream = nullptr;  // giant rows: three dependent launches, the side work's long pole -> a high-priority stream of its own
     gnnvc::Event ev_giant;
+    // Backward pass (gnnvc_train_forward* / gnnvc_backward*, gnnvc_backward.cpp): the saved forward and the gradients' scratch, grown
+    // on demand and kept across graphs like every buffer; whether they hold a forward of the resident graph is pg.train.saved.
+    struct TrainBufs {
+        DevBuf<float> params;            // the parameters the saved forward ran with (the model's own, or the caller's)
+        DevBuf<float> acts;              // every layer's input and the last layer's output, back to back (act_off, in floats)
+        std::vector<size_t> act_off;     // layers.size() + 2 offsets
+        DevBuf<float> grad[2];           // gradient rows, ping-pong: n x the widest layer
+        DevBuf<float> partials;          // k_bwd_linear_dw: row blocks x (k + 1) x m of the largest layer
+        DevBuf<float> host_in, host_out; // the host forms' device side: scores gradient in, parameter gradient (+ grad_x) out
+        DevBuf<uint8_t> row_ascends;     // the symmetry check's scratch
+        DevBuf<uint32_t> sym_flag;
+        size_t bytes() const {
+            return (params.cap + acts.cap + grad[0].cap + grad[1].cap + partials.cap + host_in.cap + host_out.cap + sym_flag.cap) *
+                       sizeof(float) + row_ascends.cap;
+        }
+    } train;
     gnnvc::KernelTraceSink ktrace;
-    PinBuf<uint32_t> pin_info;   // small device -> host results that outlive the call that asked for them (never reallocated)
+    PinBuf<uint32_t> pin_info;  // small device -> host results that outlive the call that asked for them (never reallocated)
     DevBuf<uint32_t> dev_info;
 
     // on-device audit (options "audit_*", gnnvc_options.h): counters since the engine was made
@@ -482,6 +505,9 @@ inline bool giant_gather_first() {
     }();
     return on;
 }
+
+// ---- gnnvc_backward.cpp: the backward pass's gnnvc_get_info keys ("graph_symmetric", "backward_workspace_bytes"); false = not one of them
+bool backward_info(const gnnvc_engine *e, const std::string &key, long *value);
 
 // ---- gnnvc_plans.cpp: what is built per graph -------------------------------------------------------------------------
 int find_long(gnnvc_engine *e);                              // row classes of a new graph (long / giant rows, tile waste)

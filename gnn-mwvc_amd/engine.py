@@ -35,10 +35,15 @@ ABI_SYMBOLS = [
     "gnnvc_reduction_flags", "gnnvc_score_keys", "gnnvc_synchronize", "gnnvc_last_forward_ms",
     "gnnvc_graph_layer_forward", "gnnvc_linear_forward", "gnnvc_relu_forward",
     "gnnvc_sigmoid_forward", "gnnvc_sgemm", "gnnvc_stream_sum", "gnnvc_kernel_trace",
+    "gnnvc_num_params", "gnnvc_get_params", "gnnvc_train_forward", "gnnvc_train_forward_device", "gnnvc_backward",
+    "gnnvc_backward_device", "gnnvc_graph_layer_backward", "gnnvc_linear_backward", "gnnvc_relu_backward",
+    "gnnvc_sigmoid_backward",
 ]
 COL_PAD = 64
 PATTERN_PROLOGUE, PATTERN_OPEN_END = 1, 2   # GNNVC_PATTERN_*: the bits of Engine.set_generic_patterns
 GENERIC_DEFAULT = 0xFFFFFFFF   # GNNVC_GENERIC_DEFAULT: a threshold of gnnvc_generic_config left at the engine's default
+GRAD_BLOCK_ROWS = 4096   # GNNVC_GRAD_BLOCK_ROWS: rows per block of a parameter gradient's sum (part of the ABI's numerics)
+ERR_STATE, ERR_UNSUPPORTED = -4, -5   # GNNVC_ERR_STATE, GNNVC_ERR_UNSUPPORTED
 ERR_AUDIT = -6   # GNNVC_ERR_AUDIT: the on-device audit (option "audit_period") found a fused stage's values wrong
 
 # gnnvc_get_info keys of the on-device audit (Engine.audit_report)
@@ -170,6 +175,16 @@ def load_library():
                               f32p, u32]
     L.gnnvc_kernel_trace.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     L.gnnvc_stream_sum.argtypes = [vp, f32p, u32, u32, C.c_int, f32p]
+    L.gnnvc_num_params.argtypes = [vp, C.POINTER(u64)]
+    L.gnnvc_get_params.argtypes = [vp, f32p]
+    L.gnnvc_train_forward.argtypes = [vp, f32p, f32p, f32p]
+    L.gnnvc_train_forward_device.argtypes = [vp, f32p, f32p, f32p]
+    L.gnnvc_backward.argtypes = [vp, f32p, f32p, f32p, C.c_int]
+    L.gnnvc_backward_device.argtypes = [vp, f32p, f32p, f32p, C.c_int]
+    L.gnnvc_graph_layer_backward.argtypes = [vp, u32, f32p, f32p]
+    L.gnnvc_linear_backward.argtypes = [vp, u32, u32, u32, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int]
+    L.gnnvc_relu_backward.argtypes = [vp, C.c_size_t, f32p, f32p, f32p]
+    L.gnnvc_sigmoid_backward.argtypes = [vp, C.c_size_t, f32p, f32p, f32p]
     for name in ABI_SYMBOLS:
         if name not in ("gnnvc_strerror", "gnnvc_last_error", "gnnvc_destroy"):
             getattr(L, name).restype = C.c_int
@@ -557,6 +572,99 @@ class Engine:
         self._check(self._L.gnnvc_sgemm(self._h, int(trans_a), int(trans_b), m, n, k, _np_ptr(A),
                                         A.shape[1], _np_ptr(B), B.shape[1], C.c_float(beta),
                                         _np_ptr(out), n))
+        return out
+
+
+    # -- backward (include/gnnvc.h "backward"; the order rules: DESIGN.md section 3)
+    def num_params(self) -> int:
+        v = C.c_uint64(0)
+        self._check(self._L.gnnvc_num_params(self._h, C.byref(v)))
+        return int(v.value)
+
+    def params(self) -> np.ndarray:
+        """The model's parameters in the order of the model text: per Linear_Layer, W (k x m, row-major), then the bias."""
+        out = np.empty(self.num_params(), dtype=np.float32)
+        self._check(self._L.gnnvc_get_params(self._h, _np_ptr(out)))
+        return out
+
+    def train_forward(self, x: np.ndarray, params: "np.ndarray | None" = None) -> np.ndarray:
+        """scores[n, out_width] of a forward that keeps what `backward` needs (gnnvc_train_forward).  params: a flat array in
+        params()'s order to run with instead of the model's own; the engine's inference parameters are never touched."""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n, self.in_width)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+            if params.size != self.num_params():
+                raise ValueError(f"params: {params.size} values, the model has {self.num_params()}")
+        scores = np.empty((self.n, self.out_width), dtype=np.float32)
+        self._check(self._L.gnnvc_train_forward(self._h, _np_ptr(params) if params is not None else None, _np_ptr(x), _np_ptr(scores)))
+        return scores
+
+    def backward(self, grad_scores: np.ndarray, want_grad_x: bool = False, accumulate_into: "np.ndarray | None" = None):
+        """Gradients of sum(grad_scores * scores) for the last train_forward on the resident graph (gnnvc_backward): the flat
+        parameter gradient in params()'s order — accumulate_into (a C-contiguous float32 array of num_params() values) is
+        added to in place and returned — or (grad_params, grad_x[n, in_width]) with want_grad_x.  GnnvcError -4 without a
+        training forward on this graph, -5 on a graph that is not symmetric, a sliced engine or a multi-device handle."""
+        gs = np.ascontiguousarray(grad_scores, dtype=np.float32).reshape(self.n, self.out_width)
+        if accumulate_into is not None:
+            gp = accumulate_into
+            if gp.dtype != np.float32 or gp.size != self.num_params() or not gp.flags.c_contiguous:
+                raise ValueError("accumulate_into must be a C-contiguous float32 array of num_params() values")
+        else:
+            gp = np.empty(self.num_params(), dtype=np.float32)
+        gx = np.empty((self.n, self.in_width), dtype=np.float32) if want_grad_x else None
+        self._check(self._L.gnnvc_backward(self._h, _np_ptr(gs), _np_ptr(gp), _np_ptr(gx) if want_grad_x else None,
+                                           1 if accumulate_into is not None else 0))
+        return (gp, gx) if want_grad_x else gp
+
+    def train_forward_device(self, x_ptr: int, scores_ptr: int, params_ptr: int = 0):
+        self._check(self._L.gnnvc_train_forward_device(self._h, params_ptr or None, x_ptr or None, scores_ptr or None))
+
+    def backward_device(self, grad_scores_ptr: int, grad_params_ptr: int, grad_x_ptr: int = 0, accumulate: bool = False):
+        self._check(self._L.gnnvc_backward_device(self._h, grad_scores_ptr or None, grad_params_ptr or None, grad_x_ptr or None,
+                                                  1 if accumulate else 0))
+
+    def graph_layer_backward(self, grad_out: np.ndarray) -> np.ndarray:
+        """grad_in[n, f] of the graph layer from grad_out[n, 2f + 3] on the resident (symmetric) graph."""
+        go = np.ascontiguousarray(grad_out, dtype=np.float32).reshape(self.n, -1)
+        f = (go.shape[1] - 3) // 2
+        if f < 1 or 2 * f + 3 != go.shape[1]:
+            raise ValueError("grad_out must have 2 f + 3 columns")
+        out = np.empty((self.n, f), dtype=np.float32)
+        self._check(self._L.gnnvc_graph_layer_backward(self._h, f, _np_ptr(go), _np_ptr(out)))
+        return out
+
+    def linear_backward(self, h: np.ndarray, W: np.ndarray, grad_out: np.ndarray, want=("in", "W", "bias"), accumulate_into=None):
+        """(grad_in, grad_W, grad_bias) of out = h W + bias, None for what `want` leaves out.  accumulate_into = (grad_W,
+        grad_bias) old values: the totals are added to copies of them (one rounded add each)."""
+        h = np.ascontiguousarray(h, dtype=np.float32)
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        go = np.ascontiguousarray(grad_out, dtype=np.float32)
+        n, k, m = h.shape[0], W.shape[0], W.shape[1]
+        gi = np.empty((n, k), dtype=np.float32) if "in" in want else None
+        gw = gb = None
+        if "W" in want:
+            gw = (np.empty((k, m), dtype=np.float32) if accumulate_into is None
+                  else np.ascontiguousarray(accumulate_into[0], dtype=np.float32).reshape(k, m).copy())
+        if "bias" in want:
+            gb = (np.empty(m, dtype=np.float32) if accumulate_into is None
+                  else np.ascontiguousarray(accumulate_into[1], dtype=np.float32).reshape(m).copy())
+        ptr = lambda a: _np_ptr(a) if a is not None else None
+        self._check(self._L.gnnvc_linear_backward(self._h, n, k, m, _np_ptr(h), _np_ptr(W), _np_ptr(go), ptr(gi), ptr(gw), ptr(gb),
+                                                  0 if accumulate_into is None else 1))
+        return gi, gw, gb
+
+    def relu_backward(self, z: np.ndarray, grad_out: np.ndarray) -> np.ndarray:
+        z = np.ascontiguousarray(z, dtype=np.float32)
+        go = np.ascontiguousarray(grad_out, dtype=np.float32)
+        out = np.empty_like(z)
+        self._check(self._L.gnnvc_relu_backward(self._h, z.size, _np_ptr(z), _np_ptr(go), _np_ptr(out)))
+        return out
+
+    def sigmoid_backward(self, s: np.ndarray, grad_out: np.ndarray) -> np.ndarray:
+        s = np.ascontiguousarray(s, dtype=np.float32)
+        go = np.ascontiguousarray(grad_out, dtype=np.float32)
+        out = np.empty_like(s)
+        self._check(self._L.gnnvc_sigmoid_backward(self._h, s.size, _np_ptr(s), _np_ptr(go), _np_ptr(out)))
         return out
 
 

@@ -833,6 +833,70 @@ int gnnvc_sgemm(gnnvc_engine *e, int trans_a, int trans_b, uint32_t m, uint32_t 
                 const float *A, uint32_t lda, const float *B, uint32_t ldb, float beta,
                 float *C, uint32_t ldc);
 
+/* ---- backward -----------------------------------------------------------------
+ * Input and parameter gradients of the function the engine computes — the column layout of the graph layer included (DESIGN.md
+ * §3) — for callers that retrain: the reference's weights came from a backprop-and-SGD trainer (reference
+ * old_files/src/lib/gnn_training.cpp).  Every sum has one stated order, so a gradient depends on neither the device, the grid nor
+ * the run ("Backward"):
+ *   ReLU          grad_in = (z >= 0.0f) ? grad_out : 0.0f on the layer's input z (-0.0 passes, NaN gives 0: the trainer's rule);
+ *   sigmoid       grad_in = (s * (1.0f - s)) * grad_out, rounded in that order, on the layer's OUTPUT s;
+ *   linear        grad_in[i][kk]: one fmaf chain over j = 0 .. m - 1 of grad_out[i][j] * W[kk][j] from +0.0f (gnnvc_sgemm with
+ *                 trans_b).  grad_W[kk][j]: rows are cut into blocks of GNNVC_GRAD_BLOCK_ROWS; a block's partial is one fmaf chain
+ *                 over its rows in ascending order of in[i][kk] * grad_out[i][j] from +0.0f; the partials are added in ascending
+ *                 block order, one rounded add each, from +0.0f; with `accumulate` that total is then added to the old value in
+ *                 one rounded add.  grad_bias[j]: the same with in = 1.  Up to GNNVC_GRAD_BLOCK_ROWS rows this is gnnvc_sgemm with
+ *                 trans_a and beta = accumulate ? 1 : 0 bit for bit (but where a chain underflows to -0.0f, which the add to
+ *                 +0.0f turns into +0.0f);
+ *   graph layer   (in n x f, out n x (2f+3)) grad_in[v][j] = (sum over u in adj(v) of grad_out[u][j], stored order, one rounded
+ *                 add each from +0.0f) + own, own = grad_out[v][f + j] — but +0.0f where column f + j is one of f+1 .. f+3, which
+ *                 the forward overwrites with the degree and the weights: h[1 .. min(3, f-1)] get no own term.  Degree, W / ws
+ *                 and NW / ws are constants.  (This departs from the old trainer's graph_layer_training::backward, which hands
+ *                 every own column its gradient as if the forward had not overwritten three of them: the gradient here is that
+ *                 of the forward that runs.)  The neighbour term is the transposed sum written over adj(v): right only for a
+ *                 SYMMETRIC adjacency (every graph of the reference is).  The engine checks that exactly, with multiplicities,
+ *                 once per resident graph, on the device (gnnvc_get_info "graph_symmetric": -1 before the check, then 0 or 1;
+ *                 the first call that needs the answer waits for its stream; neighbour lists that ascend are searched, others are
+ *                 scanned, and a graph with a list of more than 65 536 entries that does not ascend is refused like one that is
+ *                 not symmetric, its answer left at -1: sort the lists); a graph that is not symmetric gets
+ *                 GNNVC_ERR_UNSUPPORTED from gnnvc_backward, gnnvc_backward_device and gnnvc_graph_layer_backward.
+ * GNNVC_GRAD_BLOCK_ROWS is part of the ABI: changing it changes bits. */
+#define GNNVC_GRAD_BLOCK_ROWS 4096
+
+/* The model's parameters in the order of the model text: per Linear_Layer, W as k x m row-major, then the bias of m floats.
+ * `params` holds *count floats.  These work on any handle. */
+int gnnvc_num_params(const gnnvc_engine *e, uint64_t *count);
+int gnnvc_get_params(const gnnvc_engine *e, float *params);
+
+/* The model level.  A training forward runs the model layer by layer on the resident graph and keeps, in a workspace of the
+ * engine's own (gnnvc_get_info "backward_workspace_bytes"), every layer's input, the output and a copy of the parameters it ran
+ * with; gnnvc_backward then gives the gradient of sum(grad_scores * scores) for that forward.
+ *   params / d_params   the parameters to run with, in gnnvc_get_params' order; NULL = the model's own.  The engine's inference
+ *                       parameters and plans are never touched: a trainer keeps its weights on its side and holds one engine
+ *                       with a resident graph.  With NULL the scores are the bits of gnnvc_forward's;
+ *   x, scores           n x in_width, n x out_width;
+ *   grad_scores         n x out_width;  grad_params: gnnvc_num_params floats, written — or, with accumulate != 0, added to (may be
+ *                       NULL: only grad_x is wanted);  grad_x: n x in_width, optional (NULL), never accumulated.
+ * The saved forward belongs to the resident graph: every hand-off (upload, staged commit, attach, derive) discards it.
+ * gnnvc_backward* without a training forward on the resident graph: GNNVC_ERR_STATE (no graph at all: too).  A sliced engine or a
+ * multi-device handle: GNNVC_ERR_UNSUPPORTED.  n = 0: GNNVC_OK, the parameter gradients are +0.0f (untouched when accumulating).
+ * Ordinary forwards between a training forward and its backward change neither.  The _device forms take device pointers and are
+ * asynchronous on the engine's stream (but for the one wait of the symmetry check, above); several backwards may follow one
+ * training forward. */
+int gnnvc_train_forward(gnnvc_engine *e, const float *params, const float *x, float *scores);
+int gnnvc_train_forward_device(gnnvc_engine *e, const float *d_params, const float *d_x, float *d_scores);
+int gnnvc_backward(gnnvc_engine *e, const float *grad_scores, float *grad_params, float *grad_x, int accumulate);
+int gnnvc_backward_device(gnnvc_engine *e, const float *d_grad_scores, float *d_grad_params, float *d_grad_x, int accumulate);
+
+/* The layer level (host pointers, like the layer-level forwards above).  gnnvc_graph_layer_backward runs on the resident graph:
+ * grad_out n x (2f+3), grad_in n x f; errors as at the model level.  gnnvc_linear_backward: in n x k, W k x m, grad_out n x m;
+ * grad_in (n x k), grad_W (k x m) and grad_bias (m) may each be NULL; accumulate applies to grad_W and grad_bias; n = 0 gives +0.0f
+ * (untouched when accumulating).  gnnvc_relu_backward takes the ReLU's input z, gnnvc_sigmoid_backward the sigmoid's output s. */
+int gnnvc_graph_layer_backward(gnnvc_engine *e, uint32_t f, const float *grad_out, float *grad_in);
+int gnnvc_linear_backward(gnnvc_engine *e, uint32_t n, uint32_t k, uint32_t m, const float *in, const float *W,
+                          const float *grad_out, float *grad_in, float *grad_W, float *grad_bias, int accumulate);
+int gnnvc_relu_backward(gnnvc_engine *e, size_t count, const float *z, const float *grad_out, float *grad_in);
+int gnnvc_sigmoid_backward(gnnvc_engine *e, size_t count, const float *s, const float *grad_out, float *grad_in);
+
 #ifdef __cplusplus
 }
 #endif
