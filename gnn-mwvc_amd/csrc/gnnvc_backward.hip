@@ -242,6 +242,10 @@ void dw_launch(uint32_t n, uint32_t k, uint32_t m, uint32_t ke, const float *in,
     hipLaunchKernelGGL((k_bwd_linear_dw<TK, TM>), dim3(grad_blocks(n), tiles), dim3(256), 0, stream, n, k, m, ke, in, gout, partials);
 }
 
+// The tile per side: 4 above 48 values, 3 above 32, 2 above 16, else 1 — here for m, in launch_bwd_linear_dw for ke.
+// tests/test_backward_reference.py (test_tables_cover_every_kernel_form) restates this rule, the LDS limit of
+// launch_bwd_linear_dx and the group sizes of launch_bwd_graph as arithmetic on the shapes of the tests' tables, and asserts
+// that they reach all sixteen (TK, TM), both k_bwd_linear_dx and every k_bwd_graph with f > 64: change it with the rule.
 template <int TK>
 void dw_launch_m(uint32_t n, uint32_t k, uint32_t m, uint32_t ke, const float *in, const float *gout, float *partials, hipStream_t stream) {
     if (m > 48) dw_launch<TK, 4>(n, k, m, ke, in, gout, partials, stream);

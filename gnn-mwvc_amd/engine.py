@@ -599,21 +599,28 @@ class Engine:
         self._check(self._L.gnnvc_train_forward(self._h, _np_ptr(params) if params is not None else None, _np_ptr(x), _np_ptr(scores)))
         return scores
 
-    def backward(self, grad_scores: np.ndarray, want_grad_x: bool = False, accumulate_into: "np.ndarray | None" = None):
+    def backward(self, grad_scores: np.ndarray, want_grad_x: bool = False, accumulate_into: "np.ndarray | None" = None,
+                 want_grad_params: bool = True):
         """Gradients of sum(grad_scores * scores) for the last train_forward on the resident graph (gnnvc_backward): the flat
         parameter gradient in params()'s order — accumulate_into (a C-contiguous float32 array of num_params() values) is
-        added to in place and returned — or (grad_params, grad_x[n, in_width]) with want_grad_x.  GnnvcError -4 without a
-        training forward on this graph, -5 on a graph that is not symmetric, a sliced engine or a multi-device handle."""
+        added to in place and returned — or (grad_params, grad_x[n, in_width]) with want_grad_x.  want_grad_params = False
+        hands gnnvc_backward NULL for the parameter gradient: grad_x alone with want_grad_x, None without (the call is still
+        made, and still checked).  GnnvcError -4 without a training forward on this graph, -5 where a graph layer has to be
+        walked on a graph that is not symmetric, on a sliced engine or a multi-device handle."""
+        if not want_grad_params and accumulate_into is not None:
+            raise ValueError("accumulate_into without want_grad_params: there is no parameter gradient to add to")
         gs = np.ascontiguousarray(grad_scores, dtype=np.float32).reshape(self.n, self.out_width)
         if accumulate_into is not None:
             gp = accumulate_into
             if gp.dtype != np.float32 or gp.size != self.num_params() or not gp.flags.c_contiguous:
                 raise ValueError("accumulate_into must be a C-contiguous float32 array of num_params() values")
         else:
-            gp = np.empty(self.num_params(), dtype=np.float32)
+            gp = np.empty(self.num_params(), dtype=np.float32) if want_grad_params else None
         gx = np.empty((self.n, self.in_width), dtype=np.float32) if want_grad_x else None
-        self._check(self._L.gnnvc_backward(self._h, _np_ptr(gs), _np_ptr(gp), _np_ptr(gx) if want_grad_x else None,
-                                           1 if accumulate_into is not None else 0))
+        self._check(self._L.gnnvc_backward(self._h, _np_ptr(gs), _np_ptr(gp) if want_grad_params else None,
+                                           _np_ptr(gx) if want_grad_x else None, 1 if accumulate_into is not None else 0))
+        if not want_grad_params:
+            return gx
         return (gp, gx) if want_grad_x else gp
 
     def train_forward_device(self, x_ptr: int, scores_ptr: int, params_ptr: int = 0):

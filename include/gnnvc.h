@@ -858,7 +858,10 @@ int gnnvc_sgemm(gnnvc_engine *e, int trans_a, int trans_b, uint32_t m, uint32_t 
  *                 the first call that needs the answer waits for its stream; neighbour lists that ascend are searched, others are
  *                 scanned, and a graph with a list of more than 65 536 entries that does not ascend is refused like one that is
  *                 not symmetric, its answer left at -1: sort the lists); a graph that is not symmetric gets
- *                 GNNVC_ERR_UNSUPPORTED from gnnvc_backward, gnnvc_backward_device and gnnvc_graph_layer_backward.
+ *                 GNNVC_ERR_UNSUPPORTED from gnnvc_backward, gnnvc_backward_device and gnnvc_graph_layer_backward.  At the model
+ *                 level the check is made, and the refusal given, only when a graph layer lies in the range of layers the call
+ *                 walks: a model without one, or a call without grad_x whose first linear layer lies above every graph layer,
+ *                 runs on any graph and leaves the answer as it was.
  * GNNVC_GRAD_BLOCK_ROWS is part of the ABI: changing it changes bits. */
 #define GNNVC_GRAD_BLOCK_ROWS 4096
 
