@@ -7,5 +7,5 @@ Layout:
   engine.py  ctypes binding of the C ABI (include/gnnvc.h) for tests and the bench
   data/      the trained model in the reference's text format
 """
-from .engine import (ERR_AUDIT, Engine, EngineRowCodec, GnnvcError, build_library, default_model_text,  # noqa: F401
+from .engine import (ERR_AUDIT, Engine, EngineRowCodec, FitStats, GnnvcError, build_library, default_model_text,  # noqa: F401
                      library_path, load_library)

@@ -1,6 +1,7 @@
 // gnnvc_backward.cpp — the backward pass of include/gnnvc.h: the training forward that keeps what a gradient needs, the model-level
 // backward over it, and the layer-level backward entry points.  All arithmetic happens in the kernels of gnnvc_backward.hip, in
-// the orders DESIGN.md §3 ("Backward") states; there is no CPU fallback here.
+// the orders DESIGN.md §3 ("Backward") states; there is no CPU fallback here.  At the end, the loss and the optimizer step a trainer
+// runs between a backward and the next forward (gnnvc_mse*, gnnvc_sgd_step*; kernels: gnnvc_fit.hip).
 //
 // The engine's inference side is never touched: the parameters a training forward ran with are a copy of their own
 // (gnnvc_engine::TrainBufs::params), its activations and the gradients' scratch live beside them, and an ordinary forward between
@@ -177,6 +178,25 @@ int activation_backward(gnnvc_engine *e, size_t count, const float *saved, const
     return GNNVC_OK;
 }
 
+// what the loss and the step ask first: `bad` = the argument rule the caller found broken (null: none)
+int fit_args(gnnvc_engine *e, const char *what, const char *bad) {
+    if (bad) return fail(e, GNNVC_ERR_INVALID, "%s: %s", what, bad);
+    if (e->multi) return fail(e, GNNVC_ERR_UNSUPPORTED, "%s is not available on a multi-device handle", what);
+    return use_device(e);
+}
+
+// rows > 0, device pointers; d_grad or d_stats may be null.  The block partials and counts are the engine's (train.fit_*).
+int mse_run(gnnvc_engine *e, uint32_t rows, uint32_t width, const float *d_x, const float *d_y, float *d_grad, gnnvc_fit_stats *d_stats) {
+    auto &t = e->train;
+    if (d_stats) {
+        const size_t blocks = gnnvc::grad_blocks(rows);
+        HIP_TRY(e, t.fit_partials.reserve(blocks + 64));
+        HIP_TRY(e, t.fit_counts.reserve(3 * blocks + 64));
+    }
+    HIP_TRY(e, gnnvc::launch_fit_mse(rows, width, d_x, d_y, d_grad, t.fit_partials.p, t.fit_counts.p, d_stats, e->stream));
+    return GNNVC_OK;
+}
+
 }  // namespace
 
 bool gnnvc_eng::backward_info(const gnnvc_engine *e, const std::string &key, long *value) {
@@ -348,6 +368,65 @@ int gnnvc_relu_backward(gnnvc_engine *e, size_t count, const float *z, const flo
 
 int gnnvc_sigmoid_backward(gnnvc_engine *e, size_t count, const float *s, const float *grad_out, float *grad_in) {
     return activation_backward(e, count, s, grad_out, grad_in, true);
+}
+
+// ---- loss and step (kernels: gnnvc_fit.hip): no resident graph is needed, the _device forms never wait ----
+
+int gnnvc_mse_device(gnnvc_engine *e, uint32_t rows, uint32_t width, const float *d_scores, const float *d_target, float *d_grad,
+                     gnnvc_fit_stats *d_stats) {
+    if (!e) return GNNVC_ERR_INVALID;
+    int rc = fit_args(e, "gnnvc_mse_device", width == 0 ? "zero width" : (!d_grad && !d_stats) ? "neither a gradient nor stats asked for" : nullptr);
+    if (rc || !rows) return rc;
+    if (!d_scores || !d_target) return fail(e, GNNVC_ERR_INVALID, "null device buffers");
+    return mse_run(e, rows, width, d_scores, d_target, d_grad, d_stats);
+}
+
+int gnnvc_mse(gnnvc_engine *e, uint32_t rows, uint32_t width, const float *scores, const float *target, float *grad,
+              gnnvc_fit_stats *stats) {
+    if (!e) return GNNVC_ERR_INVALID;
+    int rc = fit_args(e, "gnnvc_mse", width == 0 ? "zero width" : (!grad && !stats) ? "neither a gradient nor stats asked for" : nullptr);
+    if (rc || !rows) return rc;
+    if (!scores || !target) return fail(e, GNNVC_ERR_INVALID, "null host buffers");
+    const size_t count = (size_t)rows * width;
+    HostOp op{e};
+    DevBuf<float> dx, dy, dg;
+    DevBuf<gnnvc_fit_stats> ds;
+    if ((rc = op.up(dx, scores, count)) || (rc = op.up(dy, target, count)) || (grad && (rc = op.up(dg, nullptr, count)))) return rc;
+    if (stats) {
+        HIP_TRY(e, ds.reserve(1));
+        HIP_TRY(e, hipMemcpyAsync(ds.p, stats, sizeof *stats, hipMemcpyHostToDevice, e->stream));
+    }
+    if ((rc = mse_run(e, rows, width, dx.p, dy.p, grad ? dg.p : nullptr, stats ? ds.p : nullptr))) return rc;
+    if ((rc = op.down(grad, dg.p, count))) return rc;
+    if (stats) HIP_TRY(e, hipMemcpyAsync(stats, ds.p, sizeof *stats, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return GNNVC_OK;
+}
+
+int gnnvc_sgd_step_device(gnnvc_engine *e, uint64_t count, float *d_params, float *d_vel, float *d_grad, uint64_t batch, float lr,
+                          float momentum, float weight_decay, int zero_grad) {
+    if (!e) return GNNVC_ERR_INVALID;
+    int rc = fit_args(e, "gnnvc_sgd_step_device", batch == 0 ? "zero batch" : nullptr);
+    if (rc || !count) return rc;
+    if (!d_params || !d_vel || !d_grad) return fail(e, GNNVC_ERR_INVALID, "null device buffers");
+    HIP_TRY(e, gnnvc::launch_fit_sgd_step(count, d_params, d_vel, d_grad, (float)batch, lr, momentum, weight_decay, zero_grad != 0, e->stream));
+    return GNNVC_OK;
+}
+
+int gnnvc_sgd_step(gnnvc_engine *e, uint64_t count, float *params, float *vel, float *grad, uint64_t batch, float lr, float momentum,
+                   float weight_decay, int zero_grad) {
+    if (!e) return GNNVC_ERR_INVALID;
+    int rc = fit_args(e, "gnnvc_sgd_step", batch == 0 ? "zero batch" : nullptr);
+    if (rc || !count) return rc;
+    if (!params || !vel || !grad) return fail(e, GNNVC_ERR_INVALID, "null host buffers");
+    HostOp op{e};
+    DevBuf<float> dw, dv, dg;
+    if ((rc = op.up(dw, params, count)) || (rc = op.up(dv, vel, count)) || (rc = op.up(dg, grad, count))) return rc;
+    HIP_TRY(e, gnnvc::launch_fit_sgd_step(count, dw.p, dv.p, dg.p, (float)batch, lr, momentum, weight_decay, zero_grad != 0, e->stream));
+    if ((rc = op.down(params, dw.p, count)) || (rc = op.down(vel, dv.p, count))) return rc;
+    if (zero_grad && (rc = op.down(grad, dg.p, count))) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return GNNVC_OK;
 }
 
 }  // extern "C"

@@ -1,10 +1,12 @@
 // gnnvc_backward.h — launch interface between the engine's backward pass (gnnvc_backward.cpp) and its gfx950 kernels
-// (gnnvc_backward.hip).  Internal; the public boundary is include/gnnvc.h, the order rules are DESIGN.md §3 "Backward".
+// (gnnvc_backward.hip; the loss and the optimizer step: gnnvc_fit.hip).  Internal; the public boundary is include/gnnvc.h, the order
+// rules are DESIGN.md §3 "Backward".
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/gnnvc.h"
 #include "gnnvc_kernels.h"
 
 namespace gnnvc {
@@ -43,5 +45,18 @@ hipError_t launch_bwd_graph(const GraphDev &g, uint32_t f, const float *grad_out
 constexpr uint32_t kSymmetryScanLimit = 65536;
 hipError_t launch_bwd_row_ascends(const GraphDev &g, uint8_t *row_ascends, uint32_t *info, hipStream_t stream);
 hipError_t launch_bwd_symmetry(const GraphDev &g, const uint8_t *row_ascends, uint32_t *info, hipStream_t stream);
+
+// ---- loss and step (gnnvc_fit.hip; include/gnnvc.h "loss and step") ----
+// x, y: rows x width.  With grad: grad[i][j] = (2.0f * (x[i][j] - y[i][j])) / (float)width; grad may be x or y itself.  With stats
+// (device memory): k_mse_block leaves one loss partial and three counts per block of kGradBlockRows rows in `partials`
+// (grad_blocks(rows) floats) and `counts` (3 * grad_blocks(rows) words), k_mse_finish adds them in block order onto *stats.  Up to
+// kGradBlockRows rows the total added to loss_sum is the reference's MSE_loss chain, loss += se / width over the rows, before its
+// division by the height, bit for bit.  rows == 0: nothing is launched.
+hipError_t launch_fit_mse(uint32_t rows, uint32_t width, const float *x, const float *y, float *grad, float *partials, uint32_t *counts,
+                          gnnvc_fit_stats *stats, hipStream_t stream);
+// SGD_step over count parameters: g = grad (+ (2 weight_decay) w where weight_decay > 0), vel = (momentum vel) + (g / batch),
+// w = w - (lr vel); with zero_grad grad becomes +0.0f, else it is not written.  batch: the divisor, already a float.
+hipError_t launch_fit_sgd_step(size_t count, float *params, float *vel, float *grad, float batch, float lr, float momentum,
+                               float weight_decay, bool zero_grad, hipStream_t stream);
 
 }  // namespace gnnvc

@@ -4,7 +4,8 @@
 //   gnnvc_plans.cpp   what is built per GRAPH: row classes (long / giant rows, tile order), the LDS-table, compact-table and
 //                     column-blocked plans, the pruned adjacency, and when (hand-off / first forwards)
 //   gnnvc_multi.cpp   several devices behind one handle (public ABI only)
-//   gnnvc_backward.cpp the backward pass: training forward, model- and layer-level backward (kernels: gnnvc_backward.hip)
+//   gnnvc_backward.cpp the backward pass: training forward, model- and layer-level backward (kernels: gnnvc_backward.hip), and the
+//                     loss and the optimizer step around it (kernels: gnnvc_fit.hip)
 //   gnnvc_kernels.hip the gfx950 kernels and their launchers
 //   gnnvc_device_mem.h the owning handles every buffer, event and stream below is held by (DevBuf, PinBuf, Event, Stream)
 //   gnnvc_options.h   what gnnvc_set_option sets (gnnvc_engine::opt) and the table of its keys — no HIP in it
@@ -420,9 +421,11 @@ struct gnnvc_engine {
         DevBuf<float> host_in, host_out; // the host forms' device side: scores gradient in, parameter gradient (+ grad_x) out
         DevBuf<uint8_t> row_ascends;     // the symmetry check's scratch
         DevBuf<uint32_t> sym_flag;
+        DevBuf<float> fit_partials;      // k_mse_block: a loss partial per block of kGradBlockRows rows
+        DevBuf<uint32_t> fit_counts;     // ... and its three counts
         size_t bytes() const {
-            return (params.cap + acts.cap + grad[0].cap + grad[1].cap + partials.cap + host_in.cap + host_out.cap + sym_flag.cap) *
-                       sizeof(float) + row_ascends.cap;
+            return (params.cap + acts.cap + grad[0].cap + grad[1].cap + partials.cap + host_in.cap + host_out.cap + sym_flag.cap +
+                    fit_partials.cap + fit_counts.cap) * sizeof(float) + row_ascends.cap;
         }
     } train;
     gnnvc::KernelTraceSink ktrace;

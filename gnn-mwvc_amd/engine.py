@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "gnnvc_num_params", "gnnvc_get_params", "gnnvc_train_forward", "gnnvc_train_forward_device", "gnnvc_backward",
     "gnnvc_backward_device", "gnnvc_graph_layer_backward", "gnnvc_linear_backward", "gnnvc_relu_backward",
     "gnnvc_sigmoid_backward",
+    "gnnvc_mse_device", "gnnvc_mse", "gnnvc_sgd_step_device", "gnnvc_sgd_step",
 ]
 COL_PAD = 64
 PATTERN_PROLOGUE, PATTERN_OPEN_END = 1, 2   # GNNVC_PATTERN_*: the bits of Engine.set_generic_patterns
@@ -67,6 +68,25 @@ class GenericConfig(C.Structure):
                 raise ValueError(f"generic: unknown key {k!r} (one of {', '.join(cls.KEYS)})")
             setattr(c, k, v)
         return c
+
+
+class FitStats(C.Structure):
+    """gnnvc_fit_stats: what gnnvc_mse* adds to (40 bytes; zero it to start a read-out).  The three read-outs are run_model's
+    formulas (reference old_files/src/apps/gnn_train.cpp), NaN where the divisor is zero."""
+    _fields_ = [("loss_sum", C.c_double), ("rows", C.c_uint64), ("positives", C.c_uint64), ("positive_hits", C.c_uint64),
+                ("negative_hits", C.c_uint64)]
+
+    @property
+    def loss(self) -> float:
+        return self.loss_sum / self.rows if self.rows else float("nan")
+
+    @property
+    def total_accuracy(self) -> float:
+        return (self.positive_hits + self.negative_hits) / self.rows if self.rows else float("nan")
+
+    @property
+    def true_accuracy(self) -> float:
+        return self.positive_hits / self.positives if self.positives else float("nan")
 
 
 class GnnvcError(RuntimeError):
@@ -185,6 +205,10 @@ def load_library():
     L.gnnvc_linear_backward.argtypes = [vp, u32, u32, u32, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int]
     L.gnnvc_relu_backward.argtypes = [vp, C.c_size_t, f32p, f32p, f32p]
     L.gnnvc_sigmoid_backward.argtypes = [vp, C.c_size_t, f32p, f32p, f32p]
+    L.gnnvc_mse_device.argtypes = [vp, u32, u32, f32p, f32p, f32p, vp]
+    L.gnnvc_mse.argtypes = [vp, u32, u32, f32p, f32p, f32p, C.POINTER(FitStats)]
+    L.gnnvc_sgd_step_device.argtypes = [vp, u64, f32p, f32p, f32p, u64, C.c_float, C.c_float, C.c_float, C.c_int]
+    L.gnnvc_sgd_step.argtypes = [vp, u64, f32p, f32p, f32p, u64, C.c_float, C.c_float, C.c_float, C.c_int]
     for name in ABI_SYMBOLS:
         if name not in ("gnnvc_strerror", "gnnvc_last_error", "gnnvc_destroy"):
             getattr(L, name).restype = C.c_int
@@ -673,6 +697,38 @@ class Engine:
         out = np.empty_like(s)
         self._check(self._L.gnnvc_sigmoid_backward(self._h, s.size, _np_ptr(s), _np_ptr(go), _np_ptr(out)))
         return out
+
+    # -- loss and step (include/gnnvc.h "loss and step"; the order rules: DESIGN.md section 3)
+    def mse(self, scores: np.ndarray, target: np.ndarray, want_grad: bool = True, stats: "FitStats | None" = None):
+        """The MSE gradient (2 (x - y)) / width of scores[rows, width] against target (gnnvc_mse), None without want_grad; with
+        `stats` the loss total and run_model's counts of these rows are ADDED to it (a FitStats; a fresh one is all zeros)."""
+        x = np.ascontiguousarray(scores, dtype=np.float32)
+        x = x.reshape(x.shape[0], int(np.prod(x.shape[1:]))) if x.ndim > 1 else x.reshape(-1, 1)
+        y = np.ascontiguousarray(target, dtype=np.float32).reshape(x.shape)
+        grad = np.empty_like(x) if want_grad else None
+        self._check(self._L.gnnvc_mse(self._h, x.shape[0], x.shape[1], _np_ptr(x), _np_ptr(y), _np_ptr(grad) if want_grad else None,
+                                      C.byref(stats) if stats is not None else None))
+        return grad
+
+    def mse_device(self, rows: int, width: int, scores_ptr: int, target_ptr: int, grad_ptr: int = 0, stats_ptr: int = 0):
+        """gnnvc_mse_device: device pointers (stats_ptr: 40 bytes of device memory laid out as FitStats), asynchronous."""
+        self._check(self._L.gnnvc_mse_device(self._h, rows, width, scores_ptr or None, target_ptr or None, grad_ptr or None,
+                                             stats_ptr or None))
+
+    def sgd_step(self, params: np.ndarray, vel: np.ndarray, grad: np.ndarray, batch: int, lr: float, momentum: float,
+                 weight_decay: float = 0.0, zero_grad: bool = False):
+        """One momentum SGD step with L2 decay (gnnvc_sgd_step) IN PLACE on three C-contiguous float32 arrays of one size:
+        params and vel are updated, grad becomes +0.0f with zero_grad and is left as it is without."""
+        for a in (params, vel, grad):
+            if a.dtype != np.float32 or not a.flags.c_contiguous or not a.flags.writeable or a.size != params.size:
+                raise ValueError("params, vel and grad must be writeable C-contiguous float32 arrays of one size")
+        self._check(self._L.gnnvc_sgd_step(self._h, params.size, _np_ptr(params), _np_ptr(vel), _np_ptr(grad), batch, lr, momentum,
+                                           weight_decay, 1 if zero_grad else 0))
+
+    def sgd_step_device(self, count: int, params_ptr: int, vel_ptr: int, grad_ptr: int, batch: int, lr: float, momentum: float,
+                        weight_decay: float = 0.0, zero_grad: bool = False):
+        self._check(self._L.gnnvc_sgd_step_device(self._h, count, params_ptr or None, vel_ptr or None, grad_ptr or None, batch, lr,
+                                                  momentum, weight_decay, 1 if zero_grad else 0))
 
 
 class EngineRowCodec:

@@ -900,6 +900,50 @@ int gnnvc_linear_backward(gnnvc_engine *e, uint32_t n, uint32_t k, uint32_t m, c
 int gnnvc_relu_backward(gnnvc_engine *e, size_t count, const float *z, const float *grad_out, float *grad_in);
 int gnnvc_sigmoid_backward(gnnvc_engine *e, size_t count, const float *s, const float *grad_out, float *grad_in);
 
+/* ---- loss and step --------------------------------------------------------------
+ * What the reference's old trainer does between a forward and the next one (reference old_files/src/lib/gnn_training.cpp: MSE_grad,
+ * MSE_loss, SGD_step; old_files/src/apps/gnn_train.cpp: run_model's counters), on the device, so that a training step can stay
+ * there.  Every operation is one fp32 operation rounded on its own, in the order written: no fused multiply-add, no reciprocal in
+ * place of a division ("Loss and step").  Neither call needs a resident graph.
+ *
+ * gnnvc_mse: scores x and target y are rows x width.
+ *   grad (optional)   grad[i][j] = (2.0f * (x[i][j] - y[i][j])) / (float)width — MSE_grad: not divided by the number of rows.  grad
+ *                     may be the scores or the target buffer itself (the gradient in place: every element is read before it is
+ *                     written); it must not overlap either in any other way.
+ *   stats (optional)  every call ADDS to *stats; zero it to start a read-out.  The row value is se_i / (float)width, se_i one chain
+ *                     over j = 0 .. width - 1 from +0.0f of se = se + d * d with d = x[i][j] - y[i][j].  Rows are cut into blocks of
+ *                     GNNVC_GRAD_BLOCK_ROWS; a block's partial is one chain over its row values in ascending order from +0.0f, one
+ *                     rounded add each; the call's total is one chain over the partials in ascending block order from +0.0f, and
+ *                     loss_sum = loss_sum + (double)total.  Up to GNNVC_GRAD_BLOCK_ROWS rows the total is MSE_loss's own chain,
+ *                     loss += se / width over the rows, before its division by the height, bit for bit.  The counts are run_model's,
+ *                     on column 0 alone: positives = rows with y[i][0] > 0.5f (num_true), positive_hits = those of them with
+ *                     x[i][0] > 0.5f (true_accuracy), negative_hits = rows with !(y[i][0] > 0.5f) and x[i][0] < 0.5f
+ *                     (total_accuracy); a NaN counts where these comparisons put it.  rows = the rows seen.  From them run_model
+ *                     reports loss_sum / rows, (positive_hits + negative_hits) / rows and positive_hits / positives.
+ * gnnvc_sgd_step: SGD_step over count parameters, per element
+ *                     g = grad[i];  if (weight_decay > 0.0f) g = g + ((2.0f * weight_decay) * w[i]);
+ *                     v = (momentum * vel[i]) + (g / (float)batch);  vel[i] = v;  w[i] = w[i] - (lr * v);
+ *                     with zero_grad != 0 then grad[i] = +0.0f, else grad is not written (the decayed value is not stored back).
+ *                     params, vel and grad must not overlap.
+ * Checks, in this order: a NULL engine, width == 0, batch == 0, grad and stats both NULL: GNNVC_ERR_INVALID.  A multi-device handle:
+ * GNNVC_ERR_UNSUPPORTED.  rows == 0 or count == 0: GNNVC_OK, nothing is read or written.  Then a NULL scores, target, params, vel
+ * or grad buffer: GNNVC_ERR_INVALID.  The _device forms take device pointers (the stats too: 8-byte aligned device memory), are
+ * asynchronous on the engine's stream and never wait; no atomics are used, so a result depends on neither the grid nor the run.
+ * The host forms copy in and out (the stats as found, so they add up across calls too) and wait for the stream. */
+typedef struct gnnvc_fit_stats {     /* 40 bytes; zero it to start a read-out; every call adds to it */
+    double   loss_sum;               /* sum of the calls' fp32 totals, each the sum over rows of se / width */
+    uint64_t rows, positives, positive_hits, negative_hits;
+} gnnvc_fit_stats;
+
+int gnnvc_mse_device(gnnvc_engine *e, uint32_t rows, uint32_t width, const float *d_scores, const float *d_target,
+                     float *d_grad /* may be NULL */, gnnvc_fit_stats *d_stats /* device memory, may be NULL */);
+int gnnvc_mse(gnnvc_engine *e, uint32_t rows, uint32_t width, const float *scores, const float *target,
+              float *grad, gnnvc_fit_stats *stats);            /* host pointers; waits for the stream */
+int gnnvc_sgd_step_device(gnnvc_engine *e, uint64_t count, float *d_params, float *d_vel, float *d_grad,
+                          uint64_t batch, float lr, float momentum, float weight_decay, int zero_grad);
+int gnnvc_sgd_step(gnnvc_engine *e, uint64_t count, float *params, float *vel, float *grad,
+                   uint64_t batch, float lr, float momentum, float weight_decay, int zero_grad);
+
 #ifdef __cplusplus
 }
 #endif
