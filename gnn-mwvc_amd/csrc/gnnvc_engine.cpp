@@ -263,6 +263,8 @@ struct StageChoice {
     bool rounds = false;        // kCompactWhole, last stage: sums one round at a time, dense kernel of round k under round k + 1
     bool emit = false;          // this stage's VALU epilogue counts / compacts its output rows for stage `stage + 1`
     bool emit_t4 = false;       // ... for the table tiles of stage `stage + 1` (k_stage_t4)
+    bool elide = false;         // emit, and the kernel may leave out the full rows of waves whose table rows carry no flag (gnnvc::kSkipElide)
+    bool elided_in = false;     // kCompactWhole: this stage's input was produced that way in this forward (gnnvc::CompactElide, kSkipRebuild)
     uint32_t long_thresh = 0xFFFFFFFFu;   // rows of at least this degree belong to the side streams
     gnnvc::SortedOrder sorted;  // n != 0: tiles from the degree-sorted list of this row range
 };
@@ -279,10 +281,22 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
     // writes) the stage kernel that produces the next 16-wide stage's input also counts its non-zeros and writes
     // its compact rows, so that stage can skip its two passes over the input.  Only the VALU variants emit.
     const int fused_in = in_forward ? e->call.c4_fused_for : -1;   // is THIS stage's input covered by the previous kernel?
+    const bool elided_in = in_forward && fused_in == stage && e->call.c4_elided_for == stage;
     e->call.c4_fused_for = -1;
+    e->call.c4_elided_for = -1;
     const bool may_emit = in_forward && e->pg.c4.ready && !e->pg.c4.range_mode && e->pg.c4.base == 0 && e->pg.c4.end == e->g.n && !longs &&
                           (size_t)stage + 1 < e->stages.size() && e->stages[stage + 1].f == 16 && lo == 0 && hi == e->g.n &&
                           e->opt.mfma != 1 && !e->pg.c4.stage_off[stage + 1];
+    // Elided rows: the producer may leave out full rows only if everything that runs on them in this forward is the compact-table
+    // route of a whole forward on the engine's own buffers — whose kernels read a vertex's full row only where its table row is
+    // flagged, and whose preparation puts the rows back on the device if it does not take the table as written.  So: may_emit
+    // (a whole forward, the whole-graph plan, no long rows, the consumer's plan not switched off), no audit in this call (it
+    // compares full rows), the consumer's first layer may leave out zero terms (else its dense kernel is handed no table), no
+    // slice, no table tiles and no sorted tiles in this forward (the consumer's choice below would not be kCompactWhole — which
+    // also means no pruned or filtered view and no plan builder that reads features, gather_view), and the last verdict seen for
+    // the consumer said that its table was taken as written.  The consumer's choice is checked below: elided_in.
+    const bool may_elide = may_emit && gnnvc::compact_elides_rows() && !e->call.audit_now && !e->call.t4_now && !e->g.sliced() && !e->pg.rows.sorted_wanted &&
+                           e->opt.dense_skip && (e->stages[stage + 1].skip_ok & 1u) && e->pg.c4.elide_ok[stage + 1];
     c.long_thresh = (sp.f == 16) ? e->pg.rows.thresh_f16 : e->pg.rows.long_thresh;
     c.mfma = e->opt.mfma == 1 || (e->opt.mfma == 2 && sp.f == 16);
     const bool t4 = in_forward && e->call.t4_now && lo == 0 && hi == e->g.n;   // table tiles: whole forwards on a graph that qualifies
@@ -312,6 +326,7 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
         if (lt_fits && in_forward) e->pg.lt.used = true;
         if (lt_fits && e->pg.lt.mapped) c.long_thresh = e->pg.lt.plan_thresh;   // the plan holds every row below the giant ones
         c.emit = may_emit;
+        c.elide = may_elide;
         if (c.sums != StageChoice::kGather) return GNNVC_OK;   // (those two bring their own tile order)
     } else if (sp.f == 16 && t4) {
         c.sums = StageChoice::kTableTiles;
@@ -345,8 +360,12 @@ int choose_stage(gnnvc_engine *e, int stage, uint32_t lo, uint32_t hi, const flo
             const uint32_t nrounds = ((hi - 1 - e->pg.c4.base) / e->pg.c4.rows - (lo - e->pg.c4.base) / e->pg.c4.rows) / 256u + 1u;
             c.rounds = e->opt.overlap && sp.variant == 2 && e->opt.mfma != 1 && nrounds <= gnnvc::compact_rounds();
             c.emit = may_emit;   // this stage's own (aggregate-only, VALU) kernel produces for the next one
+            c.elide = may_elide;
+            c.elided_in = elided_in;
         }
     }
+    if (elided_in && !c.elided_in)   // (the rule above is this choice, made a stage early: they must agree)
+        return fail(e, GNNVC_ERR_STATE, "stage %d: its input was written without full rows, but the compact-table plan does not run it", stage);
     // degree-sorted tiles on skewed graphs (every stage; the list is cached per row range)
     int rc = ensure_sorted(e, lo, hi);
     if (rc) return rc;
@@ -431,7 +450,10 @@ int launch_side_rows(gnnvc_engine *e, const gnnvc::StageCall &call, uint32_t thr
 }
 
 // call: the stage on the view of the graph the gathering kernels take (gather_view); the plans' launches see the graph itself
-int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &call, const gnnvc::SortedOrder &so_p, int stage) {
+int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &call_in, const gnnvc::SortedOrder &so_p, int stage) {
+    gnnvc::StageCall call = call_in;   // (with the two bits of `skip` that belong to elided rows: every launch below copies this one)
+    if (c.emit && c.elide) call.skip |= gnnvc::kSkipElide;
+    if (c.elided_in) call.skip |= gnnvc::kSkipRebuild;
     const gnnvc::StagePlan &sp = *call.sp;
     const GraphDev &gv = *call.g;
     const uint32_t lo = call.row_lo, hi = call.row_hi;
@@ -454,6 +476,10 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         emit.table = e->c4.table.p;
         emit.counts = e->c4.emit_counts.p;
         e->call.c4_fused_for = stage + 1;
+        if (c.elide) {
+            e->call.c4_elided_for = stage + 1;
+            ++e->pg.c4.elided_last;
+        }
         return GNNVC_OK;
     };
     // First use of the compact-table plan on this graph: no earlier forward has said which four columns the NEXT stage's
@@ -535,9 +561,15 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
         // where it is the one that reads them)
         if (fused) e->call.c4_emit_zero = false;
         if (!(what & 1)) ++e->pg.plan_memsets;   // (no k_c4_choose in this call: launch_compact_gather clears desc[5] with a memset)
+        // (a forward's own rows: k_c4_choose leaves its verdict on the producer's table, and has elided rows put back where it
+        // does not take that table — `in` is e->h[] then, written by nobody else)
+        gnnvc::CompactElide el;
+        if (fused && stage >= 1 && stage <= 2 && e->c4.elide.p)
+            el = {.words = e->c4.elide.p + gnnvc::kElideWords * (stage - 1), .rows = const_cast<float *>(in), .elided = c.elided_in};
+        if (c.elided_in && !el.words) return fail(e, GNNVC_ERR_STATE, "stage %d: elided rows without their words", stage);
         HIP_TRY(e, gnnvc::launch_compact_gather(e->g, compact_plan(e), in, fused ? e->c4.emit_counts.p : e->c4.counts.p, fused ? 64 : 1,
                                                 desc, e->c4.table.p, e->c4.acc.p, lo, hi, e->c4.dirty.p, e->pg.c4.dirty_cap,
-                                                e->c4.agg16.p, e->stream, what, c.rounds ? e->c4.round_counts.p : nullptr, 256u * e->pg.c4.rows, fused));
+                                                e->c4.agg16.p, e->stream, what, c.rounds ? e->c4.round_counts.p : nullptr, 256u * e->pg.c4.rows, fused, el));
         if (fused) e->call.c4_emit_zero = true;
     }
     if (c.sums != StageChoice::kLdsTable && c.sums != StageChoice::kBlocked) {
@@ -584,7 +616,7 @@ int launch_main(gnnvc_engine *e, const StageChoice &c, const gnnvc::StageCall &c
             HIP_TRY(e, hipStreamWaitEvent(e->aux_stream, e->round_ev[k], 0));
         }
         HIP_TRY(e, gnnvc::compact_fix(e->g, in, desc, e->c4.dirty.p, e->pg.c4.dirty_cap, e->c4.agg16.p, count, slot_base, ds,
-                                      /*blocks=*/64));
+                                      /*blocks=*/64, c.elided_in ? e->c4.table.p : nullptr));
         gnnvc::StageCall round = plain;
         round.row_lo = ra;
         round.row_hi = rb;
@@ -1224,6 +1256,7 @@ int gnnvc_get_info(const gnnvc_engine *e, const char *key, long *value) {
     }
     else if (k == "generic_stages" || k == "plans_at_handoff" || k == "mfma_dense") (void)gnnvc::read_option(e->opt, key, value);   // (as set)
     else if (backward_info(e, k, value)) {}   // the backward pass's read-outs, spelled out where it lives (gnnvc_backward.cpp)
+    else if (plan_info(e, k, value)) {}       // ... and the plans' (gnnvc_plans.cpp)
     else if (k == "generic_stages_model") *value = e->generic_on() ? 1 : 0;   // would a forward run k_stage_any now
     else if (k == "generic_stages_active") *value = e->generic_ran ? 1 : 0;   // did the last one
     else if (k == "generic_max_dense_layers") *value = gnnvc::kMaxDenseLayers;
@@ -1965,6 +1998,7 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
     int rc = use_device(e);
     if (rc) return rc;
     e->pg.plan_memsets = 0;
+    e->pg.c4.elided_last = 0;
     e->generic_ran = e->generic_on();
     e->call.heavy_last_rows = 0;
     e->call.ggiant_last_rows = 0;
@@ -2005,15 +2039,20 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
             e->pg.t4.fit_seen[1] = e->fit_pin.p[3] != 0u;
             e->pg.t4.fit_seen[2] = e->fit_pin.p[4] != 0u;
         }
+        bool elide_moved = false;
         for (int s = 1; s <= 2; ++s) {
             if (!e->pg.c4.fit_used[s]) continue;
+            // (elided rows: was the producer's table taken as written?  k_c4_choose's word, whatever else became of the stage)
+            const bool ok = e->fit_pin.p[4 + s] != 0u;
+            elide_moved = elide_moved || ok != e->pg.c4.elide_ok[s];
+            e->pg.c4.elide_ok[s] = ok;
             // (a stage whose statistics were to come from a producer that itself fell back had no chance: not its miss)
             if (s == 2 && e->pg.c4.fit_used[1] && e->fit_pin.p[0] == 0u) continue;
             e->pg.c4.unfit_runs[s] = e->fit_pin.p[s - 1] == 0u ? e->pg.c4.unfit_runs[s] + 1 : 0u;
             if (e->pg.c4.unfit_runs[s] >= 3u) e->pg.c4.stage_off[s] = true;
         }
         const uint32_t after = e->pg.lt.unfit_runs + e->pg.t4.unfit_runs + e->pg.c4.unfit_runs[1] + e->pg.c4.unfit_runs[2];
-        const bool calm = after == 0u && before == 0u && seen1 == e->pg.t4.fit_seen[1] && seen2 == e->pg.t4.fit_seen[2];
+        const bool calm = after == 0u && before == 0u && seen1 == e->pg.t4.fit_seen[1] && seen2 == e->pg.t4.fit_seen[2] && !elide_moved;
         e->pg.c4.fit_calm = calm ? e->pg.c4.fit_calm + 1u : 0u;
     }
     if (!e->pg.c4.fit_pending) {
@@ -2091,7 +2130,10 @@ static int forward_single(gnnvc_engine *e, const float *d_x, float *d_scores, fl
         }
         gnnvc::VerdictWords vw;
         if (c4_verdicts)
-            for (int s = 1; s <= 2; ++s) vw.src[s - 1] = e->c4.desc.p + gnnvc_engine::kDescWords * (s - 1);
+            for (int s = 1; s <= 2; ++s) {
+                vw.src[s - 1] = e->c4.desc.p + gnnvc_engine::kDescWords * (s - 1);
+                if (e->c4.elide.p) vw.src[4 + s] = e->c4.elide.p + gnnvc::kElideWords * (s - 1) + 5;
+            }
         else
             for (int s = 1; s <= 2; ++s) e->pg.c4.fit_used[s] = false;
         if (lt_verdict) vw.src[2] = e->lt.bad.p;

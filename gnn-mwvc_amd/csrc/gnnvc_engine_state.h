@@ -220,6 +220,12 @@ struct gnnvc_engine {
             uint32_t fit_calm = 0;               // verdicts in a row that changed nothing: from four on, only every eighth forward asks
             uint32_t fit_skip = 0;
             int last_desc = 0;                   // word offset in c4.desc of the plan's last launch (tests / tools)
+            // Elided rows (gnnvc::CompactElide): elide_ok[s] = the last verdict seen for consumer stage s said that its producer's
+            // table was taken as written — only then is the producer of its input allowed to leave out full rows; any other
+            // verdict withdraws it until the stage fits again.  elided_last = producers launched that way in the last whole forward
+            // ("elided_row_stages_last_forward").
+            bool elide_ok[4] = {false, false, false, false};
+            uint32_t elided_last = 0;
         } c4;
         // Table tiles (round 4; k_stage_t4): graphs too small for the compact-table plan and too large for their feature rows to sit
         // in an L2 (50 - 400 K vertices: BASELINE configs[1]) gather the 16-wide stages' neighbours from the 16-byte compact table of
@@ -283,6 +289,7 @@ struct gnnvc_engine {
     };
     struct Call {
         int c4_fused_for = -1;          // stage whose input statistics (and table) the previous stage kernel of this forward produced
+        int c4_elided_for = -1;         // ... and whose input that kernel was allowed to write without the full rows of unflagged vertices
         bool c4_emit_zero = false;      // the last thing queued on c4.emit_counts was a k_c4_choose that clears them behind its read
         int side_join = 0;              // what the stage at hand joins on: 0 nothing, 1 the long rows' queue, 2 the giant rows' queue
         bool stage_wide = false;        // the last launch_main ran the stage on wide tiles (audit reports)
@@ -351,6 +358,7 @@ struct gnnvc_engine {
         DevBuf<uint32_t> round_counts;     // next dirty-row slot of each round of the aggregation grid (compact_rounds() words; set by k_c4_choose)
         DevBuf<uint32_t> dirty;
         DevBuf<unsigned long long> counts, emit_counts;
+        DevBuf<uint32_t> elide;            // gnnvc::kElideWords words per consumer stage (k_c4_choose writes them, k_c4_compact and the verdicts read them)
     } c4;
     std::vector<gnnvc::Event> round_ev;    // "round k's sums are done" (main stream -> aux stream)
     static constexpr int kDescWords = 16;   // per consumer stage (see k_c4_choose); the build flag follows the last stage's
@@ -511,6 +519,8 @@ inline bool giant_gather_first() {
 
 // ---- gnnvc_backward.cpp: the backward pass's gnnvc_get_info keys ("graph_symmetric", "backward_workspace_bytes"); false = not one of them
 bool backward_info(const gnnvc_engine *e, const std::string &key, long *value);
+// ---- gnnvc_plans.cpp: the plans' read-outs that are spelled out there ("elided_row_stages_last_forward"); false = not one of them
+bool plan_info(const gnnvc_engine *e, const std::string &key, long *value);
 
 // ---- gnnvc_plans.cpp: what is built per graph -------------------------------------------------------------------------
 int find_long(gnnvc_engine *e);                              // row classes of a new graph (long / giant rows, tile waste)

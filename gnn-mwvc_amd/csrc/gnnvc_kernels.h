@@ -133,10 +133,18 @@ struct StageCall {
     float *live_table = nullptr;
     void *live_desc = nullptr;
 };
+// ... and two bits of `skip` that are no layer's (whole forwards on the compact-table route only, set by the engine's launch_main):
+// kSkipElide = this kernel, as the producer of the next stage's input, stores a wave's full rows only if one of the table rows
+// the wave writes carries a flag; kSkipRebuild = this kernel's own input was produced that way: route C takes the own row of a
+// lane without a flag from its table row (CompactElide)
+constexpr uint32_t kSkipElide = 1u << 8, kSkipRebuild = 1u << 9;
 
 // Producer side of the compact-table plan: a stage kernel whose dense layers run on the VALU can count the
 // non-zeros of the rows it writes (64 slots x 17 counters, zeroed by the caller) and write their compact form for
 // the columns chosen at the previous forward (spec = that forward's desc), see c4_emit.  All null = off.
+// With kSkipElide in the call's `skip` (k_stage_f1's VALU epilogue and k_dense_f16's only) and spec[0] == 1, a wave whose table
+// rows carry no flag stores no full rows: the table is then all there is of them until the consumer's preparation has taken it
+// as written or put them back (CompactElide).  The counters and the table rows are the same either way.
 struct EmitArgs {
     const uint32_t *spec = nullptr;
     float *table = nullptr;
@@ -495,6 +503,18 @@ struct CompactPlan {   // the per-graph part of the plan, as the launches need i
     const uint32_t *entries = nullptr;
     const uint32_t *rowmap = nullptr;    // null: slices of consecutive rows
 };
+// Elided rows: inside a whole forward the kernel that produced `in` (and its table: EmitArgs) may have been allowed to store the
+// full row of a vertex only where the vertex's table row carries a flag (kSkipElide).  words = kElideWords device words of this
+// consumer stage (k_c4_choose writes them on every exit, k_c4_compact reads them: [0] put the rows back, [1..4] from these
+// columns, [5] the table was taken as written); rows = `in`, writable; elided = the producer WAS allowed to in this forward.
+// With words set k_c4_fix reads a neighbour's table row first and its full row only if that is flagged.  words null = off.
+constexpr int kElideWords = 8;
+bool compact_elides_rows();   // was the library built with GNNVC_ELIDE_ROWS (the default)?  0: the engine never offers elision, the read-out stays 0
+struct CompactElide {
+    uint32_t *words = nullptr;
+    float *rows = nullptr;
+    bool elided = false;
+};
 // table: max_passes x (n + 1) rows of 16 bytes, acc4: max_passes x n
 hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const float *in, unsigned long long *counts,
                                  int count_slots, uint32_t *desc, float *table, float *acc4, uint32_t row_lo, uint32_t row_hi,
@@ -502,7 +522,8 @@ hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const
                                  int what = 3 /* 1 = prepare, 2 = sums, 3 = both */,
                                  uint32_t *round_counts = nullptr /* compact_rounds() words the preparation sets as well ... */,
                                  uint32_t round_stride = 0 /* ... word k to k * round_stride, round k's first dirty-row slot */,
-                                 bool clear_counts = false /* the preparation clears `counts` once it has read them */);
+                                 bool clear_counts = false /* the preparation clears `counts` once it has read them */,
+                                 const CompactElide &el = {});
 // (the preparation — k_c4_choose — clears desc[5], the stage's dirty-row counter; a call with what == 2 clears it itself)
 
 hipError_t compact_choose(unsigned long long *counts, int count_slots, uint32_t rows, uint32_t *desc, uint32_t max_passes,
@@ -514,7 +535,8 @@ hipError_t compact_sums(const GraphDev &g, const CompactPlan &cp, uint32_t *desc
                         uint32_t row_hi, uint32_t *dirty_rows, uint32_t dirty_cap, hipStream_t stream,
                         uint32_t *round_count = nullptr);
 hipError_t compact_fix(const GraphDev &g, const float *in, uint32_t *desc, const uint32_t *dirty_rows, uint32_t dirty_cap,
-                       float *agg16, const uint32_t *dirty_count, uint32_t slot_base, hipStream_t stream, uint32_t blocks = 1024);
+                       float *agg16, const uint32_t *dirty_count, uint32_t slot_base, hipStream_t stream, uint32_t blocks = 1024,
+                       const float *table = nullptr /* CompactElide: neighbours without a flag are taken from their table rows */);
 
 // The next graph derived from the resident one (see the k_derive_* kernels): new_of is scratch of
 // old_g.n words, tail receives per new row the number of entries the device cannot derive, *bad != 0 afterwards means

@@ -444,9 +444,18 @@ __device__ __forceinline__ void c4_count_cols(const float (&x)[16], unsigned lon
         c4_count_cols<J + 1>(x, mm, tcols, my, stray);
     }
 }
-__device__ __forceinline__ void c4_emit_regs(const float (&x)[16], const float *trow, uint32_t u, bool mine, int lane,
+// Elided rows (GNNVC_ELIDE_ROWS, `elide` = the engine's offer, kSkipElide): on the compact-table route the consumer of these rows
+// reads a vertex's 64-byte row only where its table row carries a flag (k_c4_fix, k_dense_f16's route C; everything else reads the
+// table), so a wave that wrote table rows (spec[0] == 1) and flagged none of them need not store its full rows at all.  Returns,
+// uniform in the wave, whether the caller has to store them.  When the consumer's k_c4_choose does not take the table as written,
+// k_c4_compact first puts every elided row back from the table (see there).
+#ifndef GNNVC_ELIDE_ROWS
+#define GNNVC_ELIDE_ROWS 1   // k_stage_f1's VALU epilogue and k_dense_f16's may leave out a wave's full-row stores (A/B: 0 = every row is stored,
+                             // the engine offers no elision — compact_elides_rows() — and "elided_row_stages_last_forward" stays 0)
+#endif
+__device__ __forceinline__ bool c4_emit_regs(const float (&x)[16], const float *trow, uint32_t u, bool mine, int lane,
                                              const uint32_t *__restrict__ spec, c4row *__restrict__ table,
-                                             unsigned long long *__restrict__ counts) {
+                                             unsigned long long *__restrict__ counts, bool elide) {
     const uint32_t ok = spec[0];
     const uint32_t s0 = ok == 1u ? spec[1] : 0u, s1 = ok == 1u ? spec[2] : 0u, s2 = ok == 1u ? spec[3] : 0u, s3 = ok == 1u ? spec[4] : 0u;
     const uint32_t tcols = (1u << (s0 & 31u)) | (1u << (s1 & 31u)) | (1u << (s2 & 31u)) | (1u << (s3 & 31u));
@@ -456,29 +465,35 @@ __device__ __forceinline__ void c4_emit_regs(const float (&x)[16], const float *
     c4_count_cols<0>(x, mm, tcols, my, stray);   // (unrolled by hand: the lane of a v_writelane is an immediate)
     my = put_lane<16>(my, (uint32_t)__popcll(mm));
     if (lane <= 16 && my) atomicAdd(&counts[(blockIdx.x & (kEmitSlots - 1)) * kEmitStride + lane], (unsigned long long)my);
+    bool flagged = false;
     if (ok == 1u && mine) {   // (a plan of several passes writes its tables in k_c4_compact)
         const float a = trow[s0], b = trow[s1], c = trow[s2], d = trow[s3];
         c4row out = {a == 0.0f ? 0.0f : a, b == 0.0f ? 0.0f : b, c == 0.0f ? 0.0f : c, d == 0.0f ? 0.0f : d};
         const bool odd = !(a >= 0.0f) || !(b >= 0.0f) || !(c >= 0.0f) || !(d >= 0.0f);   // (see c4_emit_with)
-        if (odd || (stray >> lane & 1ull)) out[0] = __uint_as_float(__float_as_uint(out[0]) | 0x80000000u);   // stray non-zeros: flag the vertex
+        flagged = odd || (stray >> lane & 1ull);
+        if (flagged) out[0] = __uint_as_float(__float_as_uint(out[0]) | 0x80000000u);   // stray non-zeros: flag the vertex
         if (odd) out[1] = __uint_as_float(__float_as_uint(out[1]) | 0x80000000u);
         table[u] = out;
     }
+    if constexpr (GNNVC_ELIDE_ROWS) return !(elide && ok == 1u) || __any(flagged);
+    return true;
 }
 
 #ifndef GNNVC_EMIT_REGS
 #define GNNVC_EMIT_REGS 1   // k_stage_f1 and k_dense_f16 emit from the registers (A/B: 0 = through the per-lane non-zero word)
 #endif
-__device__ __forceinline__ void c4_emit_row(const float (&x)[16], const float *trow, uint32_t u, bool mine, int lane,
+// (returns whether the wave has to store its full rows: c4_emit_regs; the other form never elides)
+__device__ __forceinline__ bool c4_emit_row(const float (&x)[16], const float *trow, uint32_t u, bool mine, int lane,
                                             const uint32_t *__restrict__ spec, c4row *__restrict__ table,
-                                            unsigned long long *__restrict__ counts) {
+                                            unsigned long long *__restrict__ counts, bool elide) {
     if constexpr (GNNVC_EMIT_REGS) {
-        c4_emit_regs(x, trow, u, mine, lane, spec, table, counts);
+        return c4_emit_regs(x, trow, u, mine, lane, spec, table, counts, elide);
     } else {
         uint32_t nz = 0;
 #pragma unroll
         for (int j = 0; j < 16; ++j) nz |= (x[j] != 0.0f ? 1u : 0u) << j;
         c4_emit(trow, nz, u, mine, lane, spec, table, counts);
+        return true;
     }
 }
 
@@ -975,21 +990,48 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
             for (int j = 0; j < N1 / 2; ++j) acc[j] = f32x2{0.0f, 0.0f};
             live_terms<16, N1>(acc, s, W1, all);
         }
+        // The own row: a lane whose table row is flagged reads it (its producer wave stored it); with own_table every other lane
+        // builds it from the table row read first (`t`: table_in may alias emit_table) — the four values in their columns, +0
+        // elsewhere, +0 for a -0 the row held: what routes A / B rest on, under the same skip bit — since its producer may have
+        // left the row out (kSkipElide).  (no table, several passes: every lane counts as flagged)
+        const bool own_table = GNNVC_ELIDE_ROWS && (skip & kSkipRebuild) != 0 && !stray;
         size_t own = (size_t)u * 4;
         {   // k = 16 .. 19: h[0], degree, W/ws, NW/ws
-            float s[4] = {fin[own].x, f_deg, f_w, f_nw};
+            float s[4] = {0u == d0 ? t.x : 0u == d1 ? t.y : 0u == d2 ? t.z : 0u == d3 ? t.w : 0.0f, f_deg, f_w, f_nw};
+            if (!own_table) s[0] = fin[own].x;
             live_terms<4, N1>(acc, s, W1 + 16 * N1, all);
         }
         {   // k = 20 .. 31: h[4..15], fetched only now (the row's index goes through a register the compiler cannot see through,
             // behind the pins of the groups before it: nothing hoists these loads over the first twenty terms)
             asm volatile("" : "+v"(own));
-            const float4 h1 = fin[own + 1], h2 = fin[own + 2], h3 = fin[own + 3];
-            float s[12] = {h1.x, h1.y, h1.z, h1.w, h2.x, h2.y, h2.z, h2.w, h3.x, h3.y, h3.z, h3.w};
+            float s[12];
+#pragma unroll
+            for (uint32_t k = 4; k < 16; ++k) s[k - 4] = k == d0 ? t.x : k == d1 ? t.y : k == d2 ? t.z : k == d3 ? t.w : 0.0f;
+            if (!own_table) {
+                const float4 h1 = fin[own + 1], h2 = fin[own + 2], h3 = fin[own + 3];
+                const float hh[12] = {h1.x, h1.y, h1.z, h1.w, h2.x, h2.y, h2.z, h2.w, h3.x, h3.y, h3.z, h3.w};
+#pragma unroll
+                for (int k = 0; k < 12; ++k) s[k] = hh[k];
+            }
             live_terms<12, N1>(acc, s, W1 + 20 * N1, all);
         }
         live1 = bias_relu<N1>(acc, x1, b1);   // (rows 32..34 of W1 meet exact zeros)
     } else {                   // (C, the form before GNNVC_ROUTE_C_GROUPS: all 32 inputs built first, then one dense_live)
-        const float4 h0 = fin[(size_t)u * 4], h1 = fin[(size_t)u * 4 + 1], h2 = fin[(size_t)u * 4 + 2], h3 = fin[(size_t)u * 4 + 3];
+        // (the own row: read by a lane whose table row is flagged, built from the table row by every other one — see the form above)
+        const bool own_table = GNNVC_ELIDE_ROWS && (skip & kSkipRebuild) != 0 && !stray;
+        float4 h0, h1, h2, h3;
+        {
+            float b[16];
+#pragma unroll
+            for (uint32_t k = 0; k < 16; ++k) b[k] = k == d0 ? t.x : k == d1 ? t.y : k == d2 ? t.z : k == d3 ? t.w : 0.0f;
+            h0 = make_float4(b[0], b[1], b[2], b[3]);
+            h1 = make_float4(b[4], b[5], b[6], b[7]);
+            h2 = make_float4(b[8], b[9], b[10], b[11]);
+            h3 = make_float4(b[12], b[13], b[14], b[15]);
+        }
+        if (!own_table) {
+            h0 = fin[(size_t)u * 4]; h1 = fin[(size_t)u * 4 + 1]; h2 = fin[(size_t)u * 4 + 2]; h3 = fin[(size_t)u * 4 + 3];
+        }
         // first-layer inputs in k order: 0..15 aggregate, 16 = h[0], 17 = degree, 18 = W/ws, 19 = NW/ws, 20..31 = h[4..15]
         float x0[32];
 #pragma unroll
@@ -1036,16 +1078,19 @@ __global__ __launch_bounds__(kBlock) void k_dense_f16(GraphDev g, float ws, cons
         float *T = lds[threadIdx.x >> 6];
 #pragma unroll
         for (int j = 0; j < 16; ++j) T[lane * kOutPitch + j] = x3[j];
-        if (emit_counts) c4_emit_row(x3, &T[lane * kOutPitch], u, mine, lane, emit_spec, emit_table, emit_counts);
+        bool full_rows = true;   // (uniform; false: no row of this wave carries a flag in the table it wrote, and nobody reads their full form)
+        if (emit_counts) full_rows = c4_emit_row(x3, &T[lane * kOutPitch], u, mine, lane, emit_spec, emit_table, emit_counts, (skip & kSkipElide) != 0);
         wave_lds_sync();
         const int q = lane >> 2, c = lane & 3;
+        if (full_rows) {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int src_lane = 16 * p + q;
-            const float *src = &T[src_lane * kOutPitch + 4 * c];
-            const float4 o = make_float4(src[0], src[1], src[2], src[3]);
-            const uint32_t row = __shfl(u, src_lane);
-            if (__shfl((int)mine, src_lane)) reinterpret_cast<float4 *>(fout)[(size_t)row * 4 + c] = o;
+            for (int p = 0; p < 4; ++p) {
+                const int src_lane = 16 * p + q;
+                const float *src = &T[src_lane * kOutPitch + 4 * c];
+                const float4 o = make_float4(src[0], src[1], src[2], src[3]);
+                const uint32_t row = __shfl(u, src_lane);
+                if (__shfl((int)mine, src_lane)) reinterpret_cast<float4 *>(fout)[(size_t)row * 4 + c] = o;
+            }
         }
     }
 }
@@ -1697,6 +1742,7 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
     else live1 = dense_relu_live<5, N1>(x0, x1, W1, b1);
     static_assert(N3 == 16, "feature stages emit 16 floats per vertex");
     const int q = lane >> 2, c = lane & 3;
+    bool full_rows = true;
     wave_lds_sync();  // index stage is dead; reuse the region
     if constexpr (MFMA) {
         // layer-1 activations through LDS into the matrix-core layout, layers 2-3 as MFMA
@@ -1730,9 +1776,10 @@ __global__ __launch_bounds__(kBlock) void k_stage_f1(
         dense_live<N2, N3, 0, true>(x2, x3, W3, b3, (skip & 4u) != 0, live2);
 #pragma unroll
         for (int j = 0; j < 16; ++j) T[lane * kOutPitch + j] = x3[j];
-        if (emit_counts) c4_emit_row(x3, &T[lane * kOutPitch], u, mine, lane, emit_spec, emit_table, emit_counts);
+        if (emit_counts) full_rows = c4_emit_row(x3, &T[lane * kOutPitch], u, mine, lane, emit_spec, emit_table, emit_counts, (skip & kSkipElide) != 0);
     }
     wave_lds_sync();
+    if (!full_rows) return;   // (uniform: no row of this wave carries a flag in the table it wrote, and nobody reads their full form)
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const uint32_t row = __shfl(u, 16 * p + q);   // (= v0 + 16 p + q in natural order)
@@ -3420,7 +3467,13 @@ static_assert(kC4SliceRows < kC4NoRow - 1u, "row field too narrow");
 // with clear_counts, the producer's counters — it is their only reader, and clears them once it has read them.
 __global__ __launch_bounds__(64) void k_c4_choose(unsigned long long *__restrict__ counts, int slots, uint32_t n,
                                                   uint32_t *__restrict__ desc, uint32_t max_passes, uint32_t *__restrict__ round_counts,
-                                                  uint32_t round_stride, int clear_counts) {
+                                                  uint32_t round_stride, int clear_counts, uint32_t *__restrict__ elide_words,
+                                                  int elided) {
+    // elide_words (kElideWords words of the consumer stage, all sixteen desc words being in use; null = none) / elided = the
+    // producer of this input was allowed to leave out full rows (kSkipElide), which it did iff its spec — desc as found here —
+    // said 1.  On EVERY exit: [0] = 1 iff it may have and the table in place is not taken as written for this forward's choice
+    // (k_c4_compact, launched behind this kernel, then first puts those rows back), [1..4] = the columns they were written with,
+    // [5] = 1 iff the table was taken as written (the verdict the host offers the next elision on).
     // one wave, everything in registers: lane i < 17 ends up with the total of counter i (16 columns + the rows seen)
     const int lane = threadIdx.x;
     unsigned long long mine = 0;
@@ -3454,10 +3507,18 @@ __global__ __launch_bounds__(64) void k_c4_choose(unsigned long long *__restrict
     if (lane == 0) desc[5] = 0u;
     const bool prev_ok = desc[0] == 1u;
     const uint32_t p1 = desc[1], p2 = desc[2], p3 = desc[3], p4 = desc[4];
+    if (elide_words && lane < 4) elide_words[1 + lane] = lane == 0 ? p1 : lane == 1 ? p2 : lane == 2 ? p3 : p4;
     if (rows != n) {   // no (complete) statistics for this input
         if (lane == 0) {
             desc[0] = 0;
             desc[6] = 0;
+            // (nothing to put back: only the emitting kernels count rows, and each of them does all n rows of a whole forward or
+            // none — rows != n means that the kernel that was allowed to elide left at once and the gathering kernel, which
+            // stores every row and writes no table, produced this input; rebuilding from the stale table would destroy it)
+            if (elide_words) {
+                elide_words[0] = 0u;
+                elide_words[5] = 0u;
+            }
         }
         return;
     }
@@ -3495,11 +3556,40 @@ __global__ __launch_bounds__(64) void k_c4_choose(unsigned long long *__restrict
     if (lane == 0) {
         desc[0] = np;
         desc[6] = (np && !table_written) ? 1u : 0u;
+        if (elide_words) {
+            elide_words[0] = (elided && prev_ok && !table_written) ? 1u : 0u;   // (no fit at all: np == 0, the table not taken either)
+            elide_words[5] = table_written ? 1u : 0u;
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void k_c4_compact(const float4 *__restrict__ feat, uint32_t n, uint32_t *__restrict__ desc,
-                                                    f32x4 *__restrict__ table) {
+// The four values of a table row `t` (flag clear) as columns k .. k + 3 of the full row they were taken from: each in its column
+// (cols: the table's four, 0xFFFFFFFF = none), +0 elsewhere.  The row itself may have held -0 where this gives +0, nothing else.
+__device__ __forceinline__ float4 c4_row_part(float4 t, uint32_t k, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+    float r[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) r[j] = (k + j == c0) ? t.x : (k + j == c1) ? t.y : (k + j == c2) ? t.z : (k + j == c3) ? t.w : 0.0f;
+    return make_float4(r[0], r[1], r[2], r[3]);
+}
+
+// elide_words (k_c4_choose; null = none): [0] != 0 = the producer left out the full rows of the vertices whose table row carries
+// no flag, and this forward does not take that table as written — they are put back first, from that table and the columns it
+// was written with ([1..4]); a flagged vertex's row was stored and is left alone.  Every thread then finds full rows in `feat`
+// for the vertices it goes on to read (the same ones: both loops stride alike), and so does every kernel behind this one.
+__global__ __launch_bounds__(256) void k_c4_compact(float4 *feat, uint32_t n, uint32_t *__restrict__ desc,
+                                                    f32x4 *__restrict__ table, const uint32_t *__restrict__ elide_words) {
+    if constexpr (GNNVC_ELIDE_ROWS) {
+        if (elide_words && elide_words[0]) {
+            const uint32_t c0 = elide_words[1], c1 = elide_words[2], c2 = elide_words[3], c3 = elide_words[4];
+            for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) {
+                const f32x4 tv = table[v];
+                if ((__float_as_uint(tv[0]) >> 31) != 0) continue;
+                const float4 t = make_float4(tv[0], tv[1], tv[2], tv[3]);
+#pragma unroll 1   // (unrolled, the sixty-four uniform compares are kept as scalar masks across the loop: fifty spilled SGPRs)
+                for (uint32_t q = 0; q < 4; ++q) feat[v * 4 + q] = c4_row_part(t, 4 * q, c0, c1, c2, c3);
+            }
+        }
+    }
     if (!desc[0] || !desc[6]) return;   // not fit, or the producing kernel wrote the table already
     // (a block that finds a negative value below clears desc[0] for the kernels that follow)
     // table of pass q at table + q * (n + 1): its four columns (0xFFFFFFFF = none: +0.0f); the sign bit of a vertex's
@@ -3759,8 +3849,22 @@ __global__ __launch_bounds__(1024) void k_c4_agg(const uint32_t *__restrict__ st
 // order, one quad of lanes per row (lane c: columns 4c .. 4c+3) -> agg16[slot]
 __global__ __launch_bounds__(256) void k_c4_fix(GraphDev g, const float4 *__restrict__ fin, uint32_t *__restrict__ desc,
                                                 const uint32_t *__restrict__ dirty_rows, uint32_t dirty_cap,
-                                                float4 *__restrict__ agg16, const uint32_t *__restrict__ dirty_count, uint32_t slot_base) {
+                                                float4 *__restrict__ agg16, const uint32_t *__restrict__ dirty_count, uint32_t slot_base,
+                                                const float4 *__restrict__ table) {
+    // table (null = every neighbour's full row is read): the input's producer may have left out the full rows of vertices
+    // whose table row carries no flag (kSkipElide), and ANY vertex can be a dirty row's neighbour: a neighbour's 16-byte table
+    // row is read first, and only a flagged one's full row after it; the others add their four table values in the table's
+    // columns and +0 elsewhere — same CSR order, same adds, and x + (+-0) == x with the sums starting at +0: the same bits.
+    // (one pass only: with several, a vertex without a flag may hold non-zeros in a later pass's columns — and k_c4_compact,
+    // which wrote those tables, has put every row back)
     if (!desc[0]) return;
+    const bool by_table = GNNVC_ELIDE_ROWS && table != nullptr && desc[0] == 1u;
+    const uint32_t c0 = desc[1], c1 = desc[2], c2 = desc[3], c3 = desc[4];
+    // (the table row `t` of neighbour v, already loaded: its part of the full row, which is read only behind a flag)
+    auto part = [&](float4 t, uint32_t v, uint32_t c) -> float4 {
+        if ((__float_as_uint(t.x) >> 31) == 0) return c4_row_part(t, 4 * c, c0, c1, c2, c3);
+        return fin[(size_t)v * 4 + c];
+    };
     // the slots k_c4_agg handed out from the same counter: [slot_base, *dirty_count).  A round's count is added to desc[5]
     // here, once, so that desc[5] ends up as the call's number of dirty rows whichever way its sums ran.
     const uint32_t first = min(slot_base, dirty_cap);
@@ -3772,14 +3876,33 @@ __global__ __launch_bounds__(256) void k_c4_fix(GraphDev g, const float4 *__rest
         uint32_t e = g.rowptr[u];
         const uint32_t end = g.rowptr[u + 1];
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (; e + 1 < end; e += 2) {   // two rows in flight, added in order
-            const float4 r0 = fin[(size_t)g.col[e] * 4 + c], r1 = fin[(size_t)g.col[e + 1] * 4 + c];
-            a.x += r0.x; a.y += r0.y; a.z += r0.z; a.w += r0.w;
-            a.x += r1.x; a.y += r1.y; a.z += r1.z; a.w += r1.w;
-        }
-        if (e < end) {
-            const float4 r0 = fin[(size_t)g.col[e] * 4 + c];
-            a.x += r0.x; a.y += r0.y; a.z += r0.z; a.w += r0.w;
+        if (by_table) {
+            // four table rows in flight (16 bytes a neighbour, one request a quad), added in order; a flagged neighbour's full row
+            // — a dirty row has one, seldom more — is a load behind its table row's
+            for (; e + 3 < end; e += 4) {
+                const uint32_t v0 = g.col[e], v1 = g.col[e + 1], v2 = g.col[e + 2], v3 = g.col[e + 3];
+                const float4 t0 = table[v0], t1 = table[v1], t2 = table[v2], t3 = table[v3];
+                const float4 r0 = part(t0, v0, c), r1 = part(t1, v1, c), r2 = part(t2, v2, c), r3 = part(t3, v3, c);
+                a.x += r0.x; a.y += r0.y; a.z += r0.z; a.w += r0.w;
+                a.x += r1.x; a.y += r1.y; a.z += r1.z; a.w += r1.w;
+                a.x += r2.x; a.y += r2.y; a.z += r2.z; a.w += r2.w;
+                a.x += r3.x; a.y += r3.y; a.z += r3.z; a.w += r3.w;
+            }
+            for (; e < end; ++e) {
+                const uint32_t v0 = g.col[e];
+                const float4 r0 = part(table[v0], v0, c);
+                a.x += r0.x; a.y += r0.y; a.z += r0.z; a.w += r0.w;
+            }
+        } else {
+            for (; e + 1 < end; e += 2) {   // two rows in flight, added in order
+                const float4 r0 = fin[(size_t)g.col[e] * 4 + c], r1 = fin[(size_t)g.col[e + 1] * 4 + c];
+                a.x += r0.x; a.y += r0.y; a.z += r0.z; a.w += r0.w;
+                a.x += r1.x; a.y += r1.y; a.z += r1.z; a.w += r1.w;
+            }
+            if (e < end) {
+                const float4 r0 = fin[(size_t)g.col[e] * 4 + c];
+                a.x += r0.x; a.y += r0.y; a.z += r0.z; a.w += r0.w;
+            }
         }
         agg16[(size_t)slot * 4 + c] = a;
     }
@@ -5655,6 +5778,7 @@ hipError_t launch_stage0_lds_table(const StageCall &c, const LdsTablePlan &lp, u
 
 // ---- compact-table plan of the 16-wide stages -----------------------------------------------
 uint32_t compact_max_rows() { return kC4MaxRows; }
+bool compact_elides_rows() { return GNNVC_ELIDE_ROWS != 0; }
 uint32_t compact_block() { return kC4Block; }
 uint32_t compact_shift() { return kC4Shift; }
 uint32_t compact_slices() { return kC4Slices; }
@@ -5667,15 +5791,18 @@ uint32_t compact_rounds() { return kC4Rounds; }
 hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const float *in, unsigned long long *counts,
                                  int count_slots, uint32_t *desc, float *table, float *acc4, uint32_t row_lo, uint32_t row_hi,
                                  uint32_t *dirty_rows, uint32_t dirty_cap, float *agg16, hipStream_t stream, int what,
-                                 uint32_t *round_counts, uint32_t round_stride, bool clear_counts) {
+                                 uint32_t *round_counts, uint32_t round_stride, bool clear_counts, const CompactElide &el) {
     if (row_hi <= row_lo || g.nnz == 0 || row_lo < cp.plan_base || row_hi > cp.plan_end) return hipErrorInvalidValue;
+    if (el.words && (!(what & 1) || el.rows != in)) return hipErrorInvalidValue;   // (the rows are put back by the preparation, in place)
     if (cp.rows_per_chunk == 0 || cp.rows_per_chunk > kC4MaxRows || cp.rows_per_chunk % kC4Slices) return hipErrorInvalidValue;
     if (cp.max_passes < 1 || cp.max_passes > kC4MaxPasses) return hipErrorInvalidValue;
     if (what & 1) {   // prepare: choose the columns and (unless the producing kernel did) write the table(s)
         GNNVC_LAUNCH(k_c4_choose, dim3(1), dim3(64), 0, stream, counts, count_slots, g.n, desc, cp.max_passes, round_counts,
-                     round_stride, clear_counts ? 1 : 0);
+                     round_stride, clear_counts ? 1 : 0, el.words, el.elided ? 1 : 0);
+        // (feat is written only where el.words says so: el.rows, the engine's own buffer; otherwise the kernel only reads it)
         GNNVC_LAUNCH(k_c4_compact, dim3(std::min<unsigned>((g.n + 256) / 256, 4096u)), dim3(256), 0, stream,
-                           reinterpret_cast<const float4 *>(in), g.n, desc, reinterpret_cast<f32x4 *>(table));
+                           el.words ? reinterpret_cast<float4 *>(el.rows) : reinterpret_cast<float4 *>(const_cast<float *>(in)), g.n, desc,
+                           reinterpret_cast<f32x4 *>(table), (const uint32_t *)el.words);
     }
     if (!(what & 2)) return hipGetLastError();
     hipError_t rc0 = hipSuccess;
@@ -5683,14 +5810,14 @@ hipError_t launch_compact_gather(const GraphDev &g, const CompactPlan &cp, const
     if (rc0 != hipSuccess) return rc0;
     rc0 = compact_sums(g, cp, desc, table, acc4, row_lo, row_hi, dirty_rows, dirty_cap, stream);
     if (rc0 != hipSuccess) return rc0;
-    return compact_fix(g, in, desc, dirty_rows, dirty_cap, agg16, desc + 5, 0, stream);
+    return compact_fix(g, in, desc, dirty_rows, dirty_cap, agg16, desc + 5, 0, stream, 1024, el.elided ? table : nullptr);
 }
 
 // the choice of table columns alone, from counters that cover `rows` rows (a pilot over the first rows of a stage's output)
 hipError_t compact_choose(unsigned long long *counts, int count_slots, uint32_t rows, uint32_t *desc, uint32_t max_passes,
                           hipStream_t stream, bool clear_counts) {
     GNNVC_LAUNCH(k_c4_choose, dim3(1), dim3(64), 0, stream, counts, count_slots, rows, desc, max_passes, (uint32_t *)nullptr,
-                 0u, clear_counts ? 1 : 0);
+                 0u, clear_counts ? 1 : 0, (uint32_t *)nullptr, 0);
     return hipGetLastError();
 }
 
@@ -5739,10 +5866,11 @@ hipError_t compact_sums(const GraphDev &g, const CompactPlan &cp, uint32_t *desc
 // it started from (desc + 5 and 0 for a call done in one launch); `blocks`: a small grid when the kernel runs beside the aggregation grid (it
 // strides over what it has to do)
 hipError_t compact_fix(const GraphDev &g, const float *in, uint32_t *desc, const uint32_t *dirty_rows, uint32_t dirty_cap,
-                       float *agg16, const uint32_t *dirty_count, uint32_t slot_base, hipStream_t stream, uint32_t blocks) {
+                       float *agg16, const uint32_t *dirty_count, uint32_t slot_base, hipStream_t stream, uint32_t blocks,
+                       const float *table) {
     GNNVC_LAUNCH(k_c4_fix, dim3(std::min<uint32_t>((dirty_cap + 63) / 64, blocks)), dim3(256), 0, stream, g,
                        reinterpret_cast<const float4 *>(in), desc, dirty_rows, dirty_cap, reinterpret_cast<float4 *>(agg16), dirty_count,
-                       slot_base);
+                       slot_base, reinterpret_cast<const float4 *>(table));
     return hipGetLastError();
 }
 

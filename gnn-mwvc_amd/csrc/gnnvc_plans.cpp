@@ -726,6 +726,13 @@ int build_lds_table_impl(gnnvc_engine *e) {
 // entry mass (hub columns sit in narrow blocks), and an input may take up to three tables — the long and giant rows
 // stay with their own kernels beside the plan.
 // c4_begin: eligibility, geometry, buffers (on e->stream); leaves pg.c4.pb.open set if there is a plan to build.
+bool plan_info(const gnnvc_engine *e, const std::string &key, long *value) {
+    // producers of a 16-wide stage's input that the last whole forward allowed to leave out full rows (0, 1 or 2: launch_main)
+    if (key == "elided_row_stages_last_forward") *value = (long)e->pg.c4.elided_last;
+    else return false;
+    return true;
+}
+
 int c4_begin(gnnvc_engine *e, uint32_t base, uint32_t end) {
     static_cast<gnnvc_engine::PerGraph::C4Plan &>(e->pg.c4) = {};   // (range_mode and the verdicts stay: pg.c4's own members)
     e->pg.c4.tried = true;
@@ -798,6 +805,9 @@ int c4_begin(gnnvc_engine *e, uint32_t base, uint32_t end) {
     HIP_TRY(e, e->c4.dirty.reserve(e->pg.c4.dirty_cap));
     HIP_TRY(e, e->c4.agg16.reserve((size_t)e->pg.c4.dirty_cap * 16));
     HIP_TRY(e, hipMemsetAsync(e->c4.desc.p, 0, (kFlagWord + 8) * sizeof(uint32_t), e->stream));
+    HIP_TRY(e, e->c4.elide.reserve(2 * gnnvc::kElideWords));
+    HIP_TRY(e, hipMemsetAsync(e->c4.elide.p, 0, 2 * gnnvc::kElideWords * sizeof(uint32_t), e->stream));
+    for (bool &ok : e->pg.c4.elide_ok) ok = false;   // (a new plan, new descriptors: no verdict on them yet)
     HIP_TRY(e, hipMemsetAsync(e->c4.entries.p, 0, entry_cap * sizeof(uint32_t), e->stream));   // (pad slots are read, never used)
     pb.open = true;
     pb.base = base;

@@ -385,7 +385,9 @@ int gnnvc_get_stream(gnnvc_engine *e, void **hip_stream);
  * "pruned_last_ok_stage1|2" (did the last call of that stage use its pruned adjacency),
  * "compact_gather_last_ok", "compact_gather_last_passes", "compact_gather_last_dirty",
  * "compact_gather_blocks", "compact_gather_steps", "plan_build_us", "plan_memsets_last_forward" (the memsets the LDS-table and
- * compact-table plans queued between the kernels of the last gnnvc_forward_device, stage calls since included: 1 in a steady forward, the LDS table's flag).
+ * compact-table plans queued between the kernels of the last gnnvc_forward_device, stage calls since included: 1 in a steady forward, the LDS table's flag),
+ * "elided_row_stages_last_forward" (0, 1 or 2: the stage kernels of the last gnnvc_forward_device that were allowed to store a
+ * wave's full 64-byte feature rows only where the compact table flags one of its vertices; results are the same either way).
  * gnnvc_get_info keys: "compact_gather_active", "compact_gather_chunks", "lds_table_active", "lds_table_chunks", "lds_table_steps", "mfma_dense", "sorted_tiles_active", "tile_waste_x100", "blocked_stage0_active", "blocked_blocks", "block_cols", "long_rows",
  * "long_row_threshold", "giant_rows", "giant_entries", "giant_row_threshold". */
 int gnnvc_set_option(gnnvc_engine *e, const char *key, long value);

@@ -60,7 +60,7 @@ def main():
         eng.synchronize()
         if a.first and i == 0:
             break
-    print("probe done", g.n, g.nnz)
+    print("probe done", g.n, g.nnz, "elided row stages in the last forward:", eng.get_info("elided_row_stages_last_forward"))
     eng.close()
 
 
